@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Throughput of the Compressor encode+decode hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -11,11 +11,15 @@ A "step" = `encode` (images -> codes) followed by `decode` (codes -> pixels) of 
 coder).  Inputs are resident in HBM before the timed region.  Image batches shard across ranks with no
 data-path collective ("weak" scaling: 32 images per GPU); RCCL is used only for the barrier / max-time reduce.
 
-Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel `conv_mfma_kernel` (fp32 MFMA bound):
+Rank 0 prints ONE JSON line.  A plain run sets up, runs W warm-up and K timed steps and prints the headline (`value` images/s,
+`ms_per_step`) with the run's configuration; `--dump-outputs DIR` then writes what the last timed step returned (see
+dump_outputs()).  Everything else below is measured only with `--full`.
+
+`roofline` (--full) is for the dominant kernel `conv_mfma_kernel` (fp32 MFMA bound):
 algorithmic FLOPs of the conv launches in the timed steps / the time during which a conv kernel was in flight
 (union of the per-launch [start, end] intervals, HIP events on the launch streams), both measured live in the timed
-region -- on every conv launch of its first 8 steps (`roofline.event_steps`; the default run has 5): keeping ~130 k HIP
-events alive over a 200-step run slowed the launches themselves by 3 %.  `cpu_baseline` times the CPU oracle (oracle/mcquic_ref.py, a plain PyTorch
+region of a --full run -- on every conv launch of its first 8 steps (`roofline.event_steps`; the default run has 5): keeping ~130 k HIP
+events alive over a 200-step run slowed the launches themselves by 3 %.  `cpu_baseline` (--full) times the CPU oracle (oracle/mcquic_ref.py, a plain PyTorch
 restatement of the reference proven bit-equal to it) on this host's cores on a bounded sample.
 """
 from __future__ import annotations
@@ -719,17 +723,41 @@ def secondary_in_child(args, cpu_codes, cpu_pix, timeout=420):
             os.remove(handle)
 
 
+DUMP_SAMPLE = 1 << 22          # float32 elements kept of an output larger than this: 16 MB (the codes of a 32-image step are 0.5 MB)
+
+
+def dump_outputs(directory, codes, pixels):
+    """`--dump-outputs DIR`: what a caller of the timed path received from its last step, as float32 .npy files --
+    `codes<l>.npy` (level l's indices [n, m, h, w], exact in float32 below 2**24) and `pixels.npy` (the reconstructions,
+    flattened).  A reconstruction of more than DUMP_SAMPLE values is written as the DUMP_SAMPLE of them at the positions
+    a torch.Generator seeded 0 draws (the same positions for the same shape, so two builds compare value for value)."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for lv, c in enumerate(codes):
+        np.save(os.path.join(directory, f"codes{lv}.npy"), c.detach().cpu().numpy().astype(np.float32))
+    flat = pixels.detach().reshape(-1)
+    if flat.numel() > DUMP_SAMPLE:
+        pick = torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        flat = flat[pick.to(flat.device)]
+    np.save(os.path.join(directory, "pixels.npy"), flat.float().cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--batch", type=int, default=BATCH_PER_GPU, help="images per GPU per step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: roofline (events on the timed steps' conv launches), "
+                         "encode / decode on their own, CPU baseline + parity, the `secondary` figures in child processes")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the codes and reconstructions of the last one to DIR/*.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no `cpu_baseline` / `parity`")
     ap.add_argument("--cpu-batch", type=int, default=4, help="images in the CPU-oracle sample (SURVEY 8(d): batch 4)")
     ap.add_argument("--graphs", action="store_true", help="replay encode/decode as captured hipGraphs (small-batch latency)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` measurements (opt-in Winograd mode, training step, VQ config #4, batch-1 latency; ~40 s)")
+                    help="with --full: skip the `secondary` measurements (opt-in Winograd mode, training step, VQ config #4, batch-1 latency; ~40 s)")
     ap.add_argument("--secondary-child", default=None, metavar="FILE",
                     help="internal: run ONLY the `secondary` measurements (FILE = optional torch file with the oracle's codes / pixels "
                          "for the parity leg) and print their JSON object; bench.py starts this as a child process")
@@ -740,6 +768,8 @@ def main():
                     help="OPT-IN experiment, never the headline: large 3x3 stride-1 layers in a Winograd form (not the reference's arithmetic); "
                          "1 = F(2, 3) along x, 2 = F(2x2, 3x3) where the layer allows it")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.two_core_child:
         return two_core_child(args)
     if args.secondary_child is not None:
@@ -787,17 +817,25 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    prof = ConvProfiler().install()
+    prof = ConvProfiler().install() if args.full else None
     barrier()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        prof.next_step()
-        step()
+    for i in range(args.steps):
+        if prof is not None:
+            prof.next_step()
+        if i == args.steps - 1:
+            last = step()                                     # (only the last step's outputs are kept: --dump-outputs)
+        else:
+            step()
     torch.cuda.synchronize()
     own = time.perf_counter() - t0                            # this rank's K steps, before it waits for the others
     barrier()
     dt = time.perf_counter() - t0
-    prof.remove()
+    if prof is not None:
+        prof.remove()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
+    del last
     rank_ms = None
     if use_dist:
         t = torch.tensor([dt, own], dtype=torch.float64, device=dev)
@@ -806,25 +844,16 @@ def main():
         dt = max(float(v[0].item()) for v in every)           # the contract's figure: barrier to barrier, MAX over ranks
         rank_ms = [round(float(v[1].item()) / args.steps * 1e3, 3) for v in every]
 
-    # secondary: each direction on its own (Mpps as in the reference's README), untimed region
-    e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-    e[0].record(); codes = model.encode(x); e[1].record(); pix = model.decode(codes); e[2].record()
-    torch.cuda.synchronize()
-    enc_ms, dec_ms = e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
+    if args.full:
+        # secondary: each direction on its own (Mpps as in the reference's README), untimed region
+        e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        e[0].record(); codes = model.encode(x); e[1].record(); pix = model.decode(codes); e[2].record()
+        torch.cuda.synchronize()
+        enc_ms, dec_ms = e[0].elapsed_time(e[1]), e[1].elapsed_time(e[2])
 
     if rank == 0:
-        conv = prof.summary()
         images = world * args.batch * args.steps
         value = images / dt
-        # the profiler sees Python-side launches only: under --graphs the step is one graph replay and there is nothing to
-        # bracket -- the per-kernel fields are then null (never 0.0); whole_step_frac still holds
-        seen = conv["launches"] > 0 and conv["ms"] > 0
-        # roofline.achieved counts the MFMA work actually ISSUED (= the algorithmic FLOPs in the default direct form; in the
-        # opt-in Winograd modes 16/36 resp. 12/18 of them on the layers that run transformed), so frac is a true pipe
-        # utilisation and cannot exceed 1; the direct-form-equivalent rate is reported beside it
-        achieved_tf = conv["mfma_flops"] / (conv["ms"] * 1e-3) / 1e12 if seen else None
-        equivalent_tf = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if seen else None
-        pmc = pmc_traffic()
         step_s = dt / args.steps
         out = {
             "metric": "images/sec encode+decode, 768x512 Kodak-shape batch, qp=2",
@@ -843,6 +872,20 @@ def main():
             "config": {"workload": f"qp=2 reference model Compressor(128, 2, [8192, 2048, 512]), batch={args.batch} "
                                    f"768x512 random images per GPU, encode+decode tensor path (BASELINE configs[1])",
                        "images_per_gpu": args.batch, "parallelism": f"dp{world} (independent image shards, no data-path collective)"},
+        }
+
+    if rank == 0 and args.full:
+        conv = prof.summary()
+        # the profiler sees Python-side launches only: under --graphs the step is one graph replay and there is nothing to
+        # bracket -- the per-kernel fields are then null (never 0.0); whole_step_frac still holds
+        seen = conv["launches"] > 0 and conv["ms"] > 0
+        # roofline.achieved counts the MFMA work actually ISSUED (= the algorithmic FLOPs in the default direct form; in the
+        # opt-in Winograd modes 16/36 resp. 12/18 of them on the layers that run transformed), so frac is a true pipe
+        # utilisation and cannot exceed 1; the direct-form-equivalent rate is reported beside it
+        achieved_tf = conv["mfma_flops"] / (conv["ms"] * 1e-3) / 1e12 if seen else None
+        equivalent_tf = conv["flops"] / (conv["ms"] * 1e-3) / 1e12 if seen else None
+        pmc = pmc_traffic()
+        out.update({
             "encode_ms": round(enc_ms, 3), "decode_ms": round(dec_ms, 3),
             "encode_mpps": round(args.batch * H * W / 1e3 / enc_ms, 3), "decode_mpps": round(args.batch * H * W / 1e3 / dec_ms, 3),
             "roofline": {
@@ -866,7 +909,7 @@ def main():
                 "whole_step_frac": round((conv["mfma_flops"] / conv["steps"] + 3.435e9 * args.batch if seen and args.winograd else 536.63e9 * args.batch)
                                          / step_s / (FP32_MATRIX_PEAK_TFLOPS * 1e12), 4),
             },
-        }
+        })
         if world == 1 and not args.no_cpu_baseline:
             nb = min(args.cpu_batch, args.batch)
             sd_cpu = {k: v.detach().cpu() for k, v in model.state_dict().items()}
@@ -877,7 +920,7 @@ def main():
         else:
             sd_cpu = cpu_codes = cpu_pix = None
         # (not under a launcher: the secondary's hipGraph captures do not mix with RCCL's watchdog thread -- a capture in global
-        #  mode is invalidated by its event queries; the driver's N = 1 run is the plain command)
+        #  mode is invalidated by its event queries; an N = 1 run with --full is the command without a launcher)
         if world == 1 and not use_dist and not args.no_secondary and not args.winograd and not args.graphs:
             del model, codes, pix                 # (the child builds its own model on the same GPU)
             torch.cuda.empty_cache()

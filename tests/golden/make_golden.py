@@ -264,6 +264,89 @@ def capture_neon(C, RQ, dense: bool, fname: str, cfg=(32, 256, [8, 4, 2, 2]), hw
     np.savez_compressed(os.path.join(OUT, fname), **f10)
 
 
+def _tree(sd) -> dict:
+    """state_dict names in order, and their shapes padded with -1 to 4 dimensions."""
+    shapes = np.full((len(sd), 4), -1, dtype=np.int32)
+    for i, v in enumerate(sd.values()):
+        shapes[i, :v.dim()] = list(v.shape)
+    return {"keys": np.array(list(sd)), "shapes": shapes}
+
+
+def capture_f16(C):
+    """F16: what tests/test_oracle_vs_reference.py and the compiled-coder case of tests/test_entropy_coder.py compare
+    against -- the reference's module trees, outputs, metric handlers and native rANS coder on those tests' own seeds.
+    Float outputs are stored whole, in files of their own (f16b_*: the compressor's decode per image, f16c: Neon's outputs)."""
+    f16 = {}
+    for key, val in _tree(ref_harness.reference_compressor(8, 2, [32, 16, 8]).state_dict()).items():
+        f16["compressor_" + key] = val
+    sd = R.make_state_dict(8, 2, [32, 16, 8], seed=3)
+    model = ref_harness.reference_compressor(8, 2, [32, 16, 8], sd)
+    x = R.make_images(2, 130, 250, seed=9)
+    with torch.inference_mode():
+        rc = model.encode(x)
+        rd = model.decode(rc)
+    for lv, cd in enumerate(rc):
+        f16[f"compressor_code{lv}"] = cd.numpy()
+    for i in range(rd.shape[0]):                # (the whole tensor is 1.5 MB: one file per image keeps each under 1 MiB)
+        np.savez_compressed(os.path.join(OUT, f"f16b_compressor_decode_{i}.npz"), dec=rd[i].contiguous().numpy())
+    outs16 = {}
+    # validation handlers (mcquic/validate/handlers.py)
+    from oracle import metrics_ref as M
+    H = ref_harness.load_validate_handlers()
+    x8, y8 = M.make_u8_pair(901, 2, 211, 180)
+    msssim, psnr = H["MsSSIM"](), H["PSNR"]()
+    f16["msssim_db"] = torch.tensor(msssim.handle(images=x8, restored=y8)).numpy()
+    f16["psnr"] = torch.tensor(psnr.handle(images=x8, restored=y8), dtype=torch.float64).numpy()
+    handler = H["IdealBPP"]([2, 2, 2], list(M.CODE_BATCH_KS))
+    for codes in M.make_code_batches(seed=5, batches=3):
+        handler(codes=codes, images=torch.zeros(3, 3, 768, 512, dtype=torch.uint8))
+    f16["ideal_bpp"] = np.array([handler.Result], dtype=np.float64)
+    # Neon: state_dict layout, encode / decode / residual_backward / residual_forward
+    from oracle import neon_ref as N
+    for dense, tag in ((False, "plain"), (True, "denseNorm")):
+        ch, k, size = (32 if dense else 16), 64, [4, 2, 2]
+        sd = N.make_state_dict(ch, k, size, seed=11, denseNorm=dense)
+        model = C.Neon(ch, k, size, dense).eval()
+        for key, val in _tree(model.state_dict()).items():
+            f16[f"neon_{tag}_{key}"] = val
+        model.load_state_dict(sd, strict=True)
+        x = R.make_images(2, 64, 64, seed=12)
+        with torch.inference_mode():
+            rc = model.encode(x)
+            outs = {"dec": model.decode(rc), "rb": model.residual_backward(rc[1], 2),
+                    "rf": model.residual_forward(rc[1], model.residual_forward(rc[0], None, 0), 1)}
+        for lv, cd in enumerate(rc):
+            f16[f"neon_{tag}_code{lv}"] = cd.numpy()
+        for name, t in outs.items():
+            outs16[f"neon_{tag}_{name}"] = t.contiguous().numpy()
+    for dense, tag in ((False, "plain"), (True, "denseNorm")):
+        for key, val in _tree(C.Neon(32, 256, [8, 4, 2, 2], dense).state_dict()).items():
+            f16[f"neon_tree_{tag}_{key}"] = val
+    # the native rANS coder (oracle/_ref): quantized CDFs, byte streams and decoded symbols on seed 7
+    import glob
+    import importlib.util
+    so = glob.glob(os.path.join(ROOT, "oracle", "_ref", "rans*.so"))
+    if not so:
+        raise RuntimeError("F16 needs oracle/_ref (make -C oracle)")
+    spec = importlib.util.spec_from_file_location("rans", so[0])
+    RA = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(RA)
+    rng = np.random.default_rng(7)
+    for k in (2, 33, 2048):
+        m, n = 3, 777
+        pmfs = [(lambda p: p / p.sum())(rng.random(k).astype(np.float32) ** 2) for _ in range(m)]
+        cdfs = [RA.pmfToQuantizedCDF(p.tolist(), 16) for p in pmfs]
+        sym = rng.integers(0, k, n).astype(np.int32)
+        idx = rng.integers(0, m, n).astype(np.int32)
+        by = RA.RansEncoder().encodeWithIndexes(sym.tolist(), idx.tolist(), cdfs, [k + 2] * m, [0] * m)
+        f16[f"rans_k{k}_cdf"] = np.asarray(cdfs, dtype=np.int64)
+        f16[f"rans_k{k}_bytes"] = np.frombuffer(by, dtype=np.uint8)
+        f16[f"rans_k{k}_decoded"] = np.asarray(RA.RansDecoder().decodeWithIndexes(by, idx.tolist(), cdfs, [k + 2] * m, [0] * m),
+                                               dtype=np.int64)
+    np.savez_compressed(os.path.join(OUT, "f16c_neon_outputs.npz"), **outs16)
+    np.savez_compressed(os.path.join(OUT, "f16_reference_direct.npz"), **f16)
+
+
 def main():
     C = ref_harness.load()
     import mcquic.nn as RN                      # the reference's layers
@@ -612,6 +695,9 @@ def main():
         capture_neon(C, RQ, False, "f13_neon_k4096.npz", NEON_K4096, hw=256, stride=8, logit_stride=128)
     if want("f14"):
         capture_neon(C, RQ, True, "f14_neon_k4096_dense_norm.npz", NEON_K4096, hw=256, stride=8, logit_stride=128)
+    # ---- F16: the reference side of the direct comparisons (module trees, outputs, metric handlers, native coder) --------------
+    if want("f16"):
+        capture_f16(C)
 
     # ---- F12: the reference's second listed model, No. 12 = Compressor(192, 12, [8192, 2048, 512]) (README.md:306):
     #           channel 192, twelve codebooks of 16-dimensional codewords.  1 x 768x512 and 2 x 200x136 (sizes that are no multiple of 128):

@@ -20,7 +20,7 @@ def _run(*extra):
 
 
 def test_bench_line_has_the_contract_fields(dev):
-    d = _run()
+    d = _run("--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -57,11 +57,11 @@ def test_bench_line_has_the_contract_fields(dev):
 def test_opt_in_modes_report_honest_roofline_fields(dev):
     """--winograd: `frac` is the issued MFMA work over the peak (<= 1; the direct-form-equivalent rate sits beside it);
     --graphs: nothing to bracket, so the per-kernel fields are null, not 0.0."""
-    w = _run("--no-cpu-baseline", "--winograd", "2")              # (opt-in modes never carry `secondary`)
+    w = _run("--full", "--no-cpu-baseline", "--winograd", "2")              # (opt-in modes never carry `secondary`)
     assert "secondary" not in w
     r = w["roofline"]
     assert 0 < r["frac"] <= 1.0 and r["equivalent_direct"] > r["achieved"] and r["mfma_gflop_per_step"] < r["algorithmic_gflop_per_step"]
-    g = _run("--no-cpu-baseline", "--graphs")
+    g = _run("--full", "--no-cpu-baseline", "--graphs")
     r = g["roofline"]
     assert r["achieved"] is None and r["frac"] is None and r["launches_per_step"] is None and r["avg_launch_ms"] is None
     assert 0 < r["whole_step_frac"] <= 1.0 and g["value"] > 0
@@ -80,8 +80,52 @@ def test_bench_under_a_process_group(dev):
     assert len(d["rank_ms_per_step"]) == 1 and 0 < d["rank_ms_per_step"][0] <= d["ms_per_step"] * 1.001
 
 
+def test_plain_run_prints_the_headline_only_and_dumps_outputs(dev, tmp_path):
+    """Without --full the run is the headline alone (no roofline, CPU baseline or `secondary`); --dump-outputs writes the last
+    timed step's codes and reconstructions as float32 .npy files, the same values from run to run."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = _run("--dump-outputs", str(tmp_path / str(i)))
+        for key in ("metric", "value", "unit", "ms_per_step", "higher_is_better", "dtype", "steps", "warmup", "config"):
+            assert key in d, key
+        assert d["steps"] == 2 and d["warmup"] == 1 and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) < 1e-2 * d["value"]
+        for key in ("roofline", "cpu_baseline", "parity", "secondary", "encode_ms"):
+            assert key not in d, key
+        files = sorted(p.name for p in (tmp_path / str(i)).iterdir())
+        assert files == ["codes0.npy", "codes1.npy", "codes2.npy", "pixels.npy"]
+        dumps.append({f: np.load(tmp_path / str(i) / f) for f in files})
+    a, b = dumps
+    assert all(v.dtype == np.float32 for v in a.values()) and sum(v.nbytes for v in a.values()) <= 64 << 20
+    assert a["pixels.npy"].size == 2 * 3 * 768 * 512 and a["codes0.npy"].shape[:2] == (2, 2)
+    for f in a:
+        assert np.array_equal(a[f], b[f]), f
+
+
+def test_bench_steps_sets_the_number_of_timed_steps(dev):
+    """A plain run makes exactly --warmup + --steps encode / decode calls, and nothing else."""
+    code = ("import sys\n"
+            "sys.argv = ['bench.py', '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '1']\n"
+            "import bench\n"
+            "from mcquic_amd.modules.compressor import Compressor\n"
+            "calls = {'encode': 0, 'decode': 0}\n"
+            "enc, dec = Compressor.encode, Compressor.decode\n"
+            "def e(self, x):\n    calls['encode'] += 1\n    return enc(self, x)\n"
+            "def d(self, c):\n    calls['decode'] += 1\n    return dec(self, c)\n"
+            "Compressor.encode, Compressor.decode = e, d\n"
+            "bench.main()\n"
+            "print('CALLS', calls['encode'], calls['decode'])\n")
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
+    assert lines[-1] == "CALLS 4 4", lines[-1]
+    d = json.loads(lines[-2])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["value"] > 0
+
+
 def test_bench_without_a_launcher_takes_no_process_group(dev):
-    d = _run("--no-cpu-baseline", "--no-secondary")
+    d = _run("--full", "--no-cpu-baseline", "--no-secondary")
     assert d["n_gpus"] == 1 and d["rccl_world"] is None and d["rank_ms_per_step"] is None and "secondary" not in d
 
 

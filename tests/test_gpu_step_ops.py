@@ -196,19 +196,32 @@ def test_training_step_issues_no_aten_kernels(dev, kind):
     assert not launching, f"ATen operators with kernels of their own inside the training step: {launching}"
 
 
-def test_training_step_replay_trace_holds_only_our_kernels(dev):
-    """The same statement from a profiler trace of one replay of the captured step, taken in a fresh process
-    (tests/_replay_names_worker.py); skipped when the tracer records (almost) nothing -- it does that now and then on this stack."""
-    import json
+def test_training_step_replay_trace_holds_only_our_kernels(dev, tmp_path):
+    """The same statement from a kernel trace of one replay of the captured step, taken in a fresh process
+    (tests/_replay_names_worker.py) under rocprofv3: every kernel dispatched from the start of the process's last hipGraphLaunch
+    (the replay; nothing runs after it).  torch.profiler is not the tracer here: it drops most kernels of a graph replay."""
+    import csv
+    import glob
     import os
+    import shutil
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
-    run = subprocess.run([sys.executable, os.path.join(here, "_replay_names_worker.py")], capture_output=True, text=True, timeout=600)
+    prof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+    run = subprocess.run([prof, "--kernel-trace", "--hip-runtime-trace", "-f", "csv", "-d", str(tmp_path), "-o", "replay", "--",
+                          sys.executable, os.path.join(here, "_replay_names_worker.py")],
+                         capture_output=True, text=True, timeout=600)
     assert run.returncode == 0, run.stderr[-2000:]
-    names = json.loads(run.stdout.strip().splitlines()[-1])
-    if len(names) < 100:
-        pytest.skip(f"the tracer delivered {len(names)} device activities for a replay of ~600 kernels")
+
+    def rows(kind):
+        files = glob.glob(os.path.join(str(tmp_path), "**", f"*{kind}.csv"), recursive=True)
+        assert len(files) == 1, (kind, files)
+        with open(files[0]) as f:
+            return list(csv.DictReader(f))
+    launches = [int(r["Start_Timestamp"]) for r in rows("hip_api_trace") if "GraphLaunch" in r["Function"]]
+    assert launches, "no hipGraphLaunch in the trace"
+    names = [r["Kernel_Name"] for r in rows("kernel_trace") if int(r["Start_Timestamp"]) >= max(launches)]
+    assert len(names) > 400, len(names)                              # (~600 kernels per replay)
     foreign = [n for n in names if "at::native" in n or "emset" in n or "fillBuffer" in n or "elementwise_kernel" in n or "copyBuffer" in n]
     assert not foreign, (len(foreign), sorted(set(foreign))[:8])
     ours = [n for n in names if "conv_mfma" in n or "conv_t16" in n or "vq_" in n]

@@ -14,7 +14,7 @@
 #   tests    the GPU test suite with durations
 #   vqpmc    counter passes over tools/bench_vq.py (vq_assign launches: fabric reads / writes, MFMA-busy, VALU / MFMA instruction counts)
 #   abtrain VAR A B [runs]   the same on the captured training step (tools/bench_train.py --graph)
-#   ab VAR A B [runs]   alternating `VAR=A` / `VAR=B` headline runs on this box (bench.py --steps 8 --no-secondary): in-step A/B of a switch
+#   ab VAR A B [runs]   alternating `VAR=A` / `VAR=B` headline runs on one GPU (bench.py --full --steps 8 --no-secondary): in-step A/B of a switch
 # Outputs: gpurun_out/<round>_<what>/ (merged back by gpurun; what the script copies into profiles/ on the BOX only serves the same call --
 # bench.py reads profiles/rNN_pmc.json -- and is copied from gpurun_out/ into profiles/ again by hand after the call)
 # (kernel traces and counter databases are deleted: too large to travel).  Earlier rounds' one-off scripts: git history (tools/collect_r0*.sh).
@@ -35,7 +35,7 @@ kt() {          # kt <out.txt> <env...> -- <command...>: rocprofv3 --kernel-trac
 pmc_passes() {  # FETCH_SIZE / WRITE_SIZE / MFMA-busy, one pass each (gpurun refuses --pmc together with other trace domains)
   for c in FETCH_SIZE WRITE_SIZE "SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"; do
     d=$O/pmc_$(echo $c | cut -d' ' -f1)
-    MCQUIC_AMD_BRANCH_STREAMS=0 rocprofv3 --pmc $c --kernel-trace -d $d -o pmc -- python bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1
+    MCQUIC_AMD_BRANCH_STREAMS=0 rocprofv3 --pmc $c --kernel-trace -d $d -o pmc -- python bench.py --full --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > /dev/null 2>&1
   done
   python profiles/pmc_stats.py $O/pmc_FETCH_SIZE/pmc_results.db $O/pmc_WRITE_SIZE/pmc_results.db $O/pmc_SQ_VALU_MFMA_BUSY_CYCLES/pmc_results.db > $O/pmc_by_kernel.txt 2>&1
   cp /tmp/pmc_rows.json $O/pmc_rows.json 2>/dev/null
@@ -45,8 +45,8 @@ pmc_passes() {  # FETCH_SIZE / WRITE_SIZE / MFMA-busy, one pass each (gpurun ref
 }
 
 bench_lines() {
-  python bench.py > $O/bench.json 2> $O/bench.err
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $O/bench_torchrun.json 2> $O/bench_torchrun.err
+  python bench.py --full > $O/bench.json 2> $O/bench.err
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29511 bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline --no-secondary > $O/bench_torchrun.json 2> $O/bench_torchrun.err
   [ -s $O/bench.json ] && tail -1 $O/bench.json > profiles/${R}_bench.json
   [ -s $O/bench_torchrun.json ] && tail -1 $O/bench_torchrun.json > profiles/${R}_bench_torchrun.json
 }
@@ -80,7 +80,7 @@ case "$WHAT" in
   final)
     pmc_passes                      # (first: the bench line below then finds THIS collection's rNN_pmc.json)
     bench_lines
-    CMD=(python bench.py --steps 4 --warmup 2 --no-cpu-baseline --no-secondary)
+    CMD=(python bench.py --full --steps 4 --warmup 2 --no-cpu-baseline --no-secondary)
     kt $O/kernel_stats_bench.txt MCQUIC_AMD_BRANCH_STREAMS=1; rm -rf $O/kt_$$
     kt $O/kernel_stats_bench_single_stream.txt MCQUIC_AMD_BRANCH_STREAMS=0; rm -rf $O/kt_$$
     python tools/train_conv_census.py --eval --batch 32 --height 768 --width 512 --top 200 > $O/infer_conv_census.txt 2>/dev/null
@@ -91,8 +91,8 @@ case "$WHAT" in
     python tools/bench_vq.py > $O/bench_vq.json 2>/dev/null
     python tools/bench_post.py > $O/bench_post.txt 2>/dev/null; python tools/bench_post.py --batch1 >> $O/bench_post.txt 2>/dev/null
     python tools/bench_neon.py --train-batches 4,8 > $O/bench_neon.txt 2>&1
-    python bench.py --batch 1 --graphs --steps 50 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 > $O/bench_batch1_graphs.json
-    CMD=(python bench.py --batch 1 --graphs --steps 20 --warmup 5 --no-cpu-baseline --no-secondary); kt $O/kernel_stats_batch1.txt MCQUIC_AMD_BRANCH_STREAMS=1; rm -rf $O/kt_$$
+    python bench.py --full --batch 1 --graphs --steps 50 --warmup 5 --no-cpu-baseline --no-secondary 2>/dev/null | tail -1 > $O/bench_batch1_graphs.json
+    CMD=(python bench.py --full --batch 1 --graphs --steps 20 --warmup 5 --no-cpu-baseline --no-secondary); kt $O/kernel_stats_batch1.txt MCQUIC_AMD_BRANCH_STREAMS=1; rm -rf $O/kt_$$
     for f in kernel_stats_bench.txt kernel_stats_bench_single_stream.txt infer_conv_census.txt speed_protocol.txt bench_metrics.txt bench_vq.json bench_post.txt bench_neon.txt bench_batch1_graphs.json kernel_stats_batch1.txt; do
       [ -s $O/$f ] && cp $O/$f profiles/${R}_$f
     done
@@ -105,7 +105,7 @@ case "$WHAT" in
   ab)
     VAR=$1; A=$2; B=$3; RUNS=${4:-2}; O=gpurun_out/ab_$VAR; mkdir -p $O
     for r in $(seq $RUNS); do for v in "$A" "$B"; do
-      env $VAR=$v python bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$VAR=$v', d['value'], d['ms_per_step'], d['roofline']['frac'])" | tee -a $O/ab.txt
+      env $VAR=$v python bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-secondary 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$VAR=$v', d['value'], d['ms_per_step'], d['roofline']['frac'])" | tee -a $O/ab.txt
     done; done ;;
   vqpmc)        # counter passes over tools/bench_vq.py: fabric reads / writes / MFMA-busy / instruction counts per vq_assign launch
     R=${1:-r06}; O=gpurun_out/${R}_vqpmc; rm -rf $O; mkdir -p $O
