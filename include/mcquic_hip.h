@@ -495,6 +495,28 @@ int mcq_ms_ssim_u8(const uint8_t* x, const uint8_t* y, float* out, void* workspa
 /* Host helper: the 11 float32 window taps the kernels use (metrics.py:22-37 for size 11, sigma 1.5). */
 void mcq_ms_ssim_window(float* out11);
 
+/* MS-SSIM as a float32 TRAINING LOSS (the distortion of the reference's training configs, `target: MsSSIM`:
+ * mcquic/loss/__init__.py:47-55 -> metrics.py:69-104, 142-193 with MsSSIM(data_range=2.0, sizeAverage=True) on restored + 1,
+ * image + 1).  a, b [N, C, H, W] float32; X = a + offset, Y = b + offset; C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2;
+ * the window, weights, pooling and relu of the metric above.  H and W must exceed 160, else MCQ_EINVAL; N * C <= 65535.
+ *   mcq_ms_ssim_loss_f32      loss_out[0] = 1 - mean over (image, channel) of prod_l relu(v_l)^w_l; values_out[5][N][C] = v, the
+ *                             per-level means of the cs map (levels 0..3) and of the SSIM map (level 4); `saved` receives the
+ *                             pooled X / Y of levels 1..4 (mcq_ms_ssim_loss_saved_bytes bytes), which the backward reads.
+ *   mcq_ms_ssim_loss_bwd_f32  da = dloss[0] * d loss / d a from the forward's `values` and `saved` (same a, b, offset, data range);
+ *                             db the same for b when non-NULL.  dL/dv_l = -(1 / (N C)) w_l v_l^(w_l - 1) prod_{k != l} relu(v_k)^w_k
+ *                             where v_l > 0, else 0 (torch's relu backward); then per level, coarse to fine, the maps' pointwise
+ *                             gradients through the transposed blur plus the adjoint of the 2x2 pooling.
+ * `workspace`: mcq_ms_ssim_loss_workspace_bytes(N, C, H, W, backward) bytes (backward = 0 for the forward, 1 for the backward;
+ * 0 for an invalid shape), 8-byte aligned, contents undefined after.  Caller-owned memory only, no host synchronisation, no
+ * memset, no atomics: safe inside a captured hipGraph and bitwise deterministic. */
+size_t mcq_ms_ssim_loss_saved_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
+size_t mcq_ms_ssim_loss_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W, int32_t backward);
+int mcq_ms_ssim_loss_f32(const float* a, const float* b, float offset, float data_range, float* loss_out, float* values_out,
+                         void* saved, void* workspace, int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
+int mcq_ms_ssim_loss_bwd_f32(const float* a, const float* b, float offset, float data_range, const float* values,
+                             const void* saved, const float* dloss, float* da, float* db /* or NULL */, void* workspace,
+                             int32_t N, int32_t C, int32_t H, int32_t W, void* stream);
+
 /* out[n] = sum over the per_image bytes of image n of (x - y)^2, exact (int64).  The reference's PSNR
  * (metrics.py:264-274) is 10 log10(255^2 / (out[n] / per_image + 1e-4)) in float64. */
 int mcq_sqdiff_sum_u8(const uint8_t* x, const uint8_t* y, int64_t* out, int64_t per_image, int32_t N, void* stream);

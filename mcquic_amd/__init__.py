@@ -17,6 +17,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
 _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 
 from .modules.compressor import BaseCompressor, Compressor, Neon  # noqa: E402
+from . import loss  # noqa: E402,F401  (training losses: MsSSIM, PSNR, step_loss)
 
-__all__ = ["BaseCompressor", "Compressor", "Neon"]
+__all__ = ["BaseCompressor", "Compressor", "Neon", "loss"]
 __version__ = "0.1.0"

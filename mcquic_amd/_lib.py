@@ -143,6 +143,12 @@ SYMBOLS = {
     "mcq_ms_ssim_workspace_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "mcq_ms_ssim_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "mcq_ms_ssim_window": (None, [c_void_p]),
+    "mcq_ms_ssim_loss_saved_bytes": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
+    "mcq_ms_ssim_loss_workspace_bytes": (c_size_t, [c_int32] * 5),
+    "mcq_ms_ssim_loss_f32": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "mcq_ms_ssim_loss_bwd_f32": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "mcq_sqdiff_sum_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "mcq_group_norm_workspace_floats": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "mcq_group_norm_f32": (c_int32, [c_void_p] * 8 + [c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),

@@ -198,6 +198,28 @@ class MseFn(torch.autograd.Function):
         return (da if ctx.needs_input_grad[0] else None), db
 
 
+class MsSsimFn(torch.autograd.Function):
+    """1 - MS-SSIM(a + offset, b + offset) over the batch (mcquic/loss/__init__.py:47-55 with offset 1, data range 2) from this
+    library's kernels (mcq_ms_ssim_loss_f32 / _bwd_f32): db only when it is asked for."""
+
+    @staticmethod
+    def forward(ctx, a, b, offset=1.0, data_range=2.0):
+        a, b = a.contiguous(), b.contiguous()
+        loss, values, saved = ops.ms_ssim_loss(a, b, offset, data_range)
+        ctx.save_for_backward(a, b, values, saved)
+        ctx.offset, ctx.data_range = float(offset), float(data_range)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        a, b, values, saved = ctx.saved_tensors
+        if not (ctx.needs_input_grad[0] or ctx.needs_input_grad[1]):
+            return None, None, None, None
+        da, db = ops.ms_ssim_loss_bwd(a, b, values, saved, dloss.contiguous().float(), ctx.offset, ctx.data_range,
+                                      want_db=ctx.needs_input_grad[1])
+        return (da if ctx.needs_input_grad[0] else None), db, None, None
+
+
 _ONES = {}
 
 

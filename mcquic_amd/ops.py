@@ -1090,6 +1090,50 @@ def ms_ssim(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _f32_pair(a: torch.Tensor, b: torch.Tensor):
+    a, b = _dev(a, "a"), _dev(b, "b")
+    if a.shape != b.shape or a.dim() != 4:
+        raise ValueError(f"expected two float32 [N, C, H, W] batches of one shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if min(a.shape[-2:]) <= 160:
+        raise ValueError(f"MS-SSIM needs image sides larger than 160 pixels, got {a.shape[-2]}x{a.shape[-1]}")
+    return a, b
+
+
+def ms_ssim_loss(a: torch.Tensor, b: torch.Tensor, offset: float = 1.0, data_range: float = 2.0):
+    """1 - MS-SSIM(a + offset, b + offset) over the batch (mcquic/loss/__init__.py:47-55: data range 2, batch mean) as a
+    0-dim float32 tensor, with what the backward needs: (loss, values [5, N, C] per-level map means, saved pooled pyramids).
+    mcq_ms_ssim_loss_f32: fixed-order float64 means, no memset -- safe inside a captured step."""
+    a, b = _f32_pair(a, b)
+    n, c, h, w = a.shape
+    lib = _lib.load()
+    ws = torch.empty((lib.mcq_ms_ssim_loss_workspace_bytes(n, c, h, w, 0) + 7) // 8, dtype=torch.float64, device=a.device)
+    saved = torch.empty(lib.mcq_ms_ssim_loss_saved_bytes(n, c, h, w) // 4, dtype=torch.float32, device=a.device)
+    loss = torch.empty((), dtype=torch.float32, device=a.device)
+    values = torch.empty((5, n, c), dtype=torch.float32, device=a.device)
+    with _guard(a.device):
+        check(lib.mcq_ms_ssim_loss_f32(_ptr(a), _ptr(b), float(offset), float(data_range), _ptr(loss), _ptr(values), _ptr(saved),
+                                       _ptr(ws), n, c, h, w, _stream()), "mcq_ms_ssim_loss_f32")
+    return loss, values, saved
+
+
+def ms_ssim_loss_bwd(a: torch.Tensor, b: torch.Tensor, values: torch.Tensor, saved: torch.Tensor, dloss: torch.Tensor,
+                     offset: float = 1.0, data_range: float = 2.0, want_db: bool = False):
+    """(da, db or None) of `ms_ssim_loss` from its `values` and `saved` (mcq_ms_ssim_loss_bwd_f32); `dloss` stays on the device."""
+    a, b = _f32_pair(a, b)
+    values, saved, dloss = _dev(values, "values"), _dev(saved, "saved"), _dev(dloss, "dloss")
+    n, c, h, w = a.shape
+    lib = _lib.load()
+    if values.shape != (5, n, c) or saved.numel() * 4 != lib.mcq_ms_ssim_loss_saved_bytes(n, c, h, w) or dloss.numel() != 1:
+        raise ValueError("ms_ssim_loss_bwd: `values` / `saved` / `dloss` do not belong to this shape")
+    ws = torch.empty((lib.mcq_ms_ssim_loss_workspace_bytes(n, c, h, w, 1) + 7) // 8, dtype=torch.float64, device=a.device)
+    da = torch.empty_like(a)
+    db = torch.empty_like(b) if want_db else None
+    with _guard(a.device):
+        check(lib.mcq_ms_ssim_loss_bwd_f32(_ptr(a), _ptr(b), float(offset), float(data_range), _ptr(values), _ptr(saved), _ptr(dloss),
+                                           _ptr(da), _ptr(db), _ptr(ws), n, c, h, w, _stream()), "mcq_ms_ssim_loss_bwd_f32")
+    return da, db
+
+
 def sqdiff_sum(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     """Exact per-image sum of squared differences of two uint8 batches, int64 [N]."""
     x, y = _u8_pair(x, y)

@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--graph-streams", action="store_true", help="with --graph: keep the branch streams on during capture (experiment)")
     ap.add_argument("--split", action="store_true", help="probe (tools/probes/split_capture.py): the step as several single-stream hipGraphs, the weight "
                     "gradients' batches on a side stream beside the input gradients' chain")
+    ap.add_argument("--loss", choices=("mse", "msssim"), default="mse",
+                    help="msssim: mcquic_amd.loss.step_loss(), the reference trainer's 0.5 MS-SSIM + 0.5 MSE (without LPIPS)")
     ap.add_argument("--graphed", action="store_true",
                     help="parallel.GraphedTrainStep: main hipGraph (forward + backward, flat gradient buffer) + one gradient all-reduce "
                          "over the ranks + post hipGraph (SGD update, frequency EMA) -- the data-parallel step without DDP's hooks")
@@ -82,6 +84,12 @@ def main():
     x = (torch.rand((args.batch, 3, args.crop, args.crop), generator=torch.Generator().manual_seed(rank)) * 2 - 1).to(dev)
 
     opt = torch.optim.SGD(model.parameters(), lr=1e-6) if args.optimizer_step else None
+    if args.loss == "msssim":
+        from mcquic_amd.loss import step_loss
+        _msssim = step_loss()
+
+        def mse_loss(xHat, x):                             # noqa: F811  (the objective the steps below take)
+            return _msssim((xHat,), x)
 
     def step():
         for p in model.parameters():
@@ -96,7 +104,8 @@ def main():
     if args.graphed:
         from mcquic_amd import parallel
         args.optimizer_step = True
-        gstep = parallel.GraphedTrainStep(model, torch.optim.SGD(model.parameters(), lr=1e-6), x)
+        gstep = parallel.GraphedTrainStep(model, torch.optim.SGD(model.parameters(), lr=1e-6), x,
+                                          loss_fn=(lambda out, xx: mse_loss(out[0], xx)) if args.loss != "mse" else None)
 
         def step():                                        # noqa: F811
             return gstep(x)
@@ -155,12 +164,14 @@ def main():
     dt = time.perf_counter() - t0
     if rank == 0:
         gn = float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in model.parameters() if p.grad is not None)))
+        extra = {"loss_fn": args.loss} if args.loss != "mse" else {}
         print(json.dumps({"metric": "training step (forward + backward), 256x256 crops, qp=2 model", "n_gpus": world,
                           "images_per_gpu": args.batch, "ms_per_step": round(dt / args.steps * 1e3, 2),
                           "images_per_s": round(world * args.batch * args.steps / dt, 2), "loss": float(loss), "grad_norm": gn,
                           "dtype": "f32", "graph": bool(((args.graph or args.split) and not use_dist) or args.graphed), "split": bool(args.split), "ddp": bool(use_dist and not args.graphed),
                           "graphed_data_parallel": bool(args.graphed),
-                          "optimizer_step": "SGD inside the timed region (weights re-packed every step)" if args.optimizer_step else "not included"}))
+                          "optimizer_step": "SGD inside the timed region (weights re-packed every step)" if args.optimizer_step else "not included",
+                          **extra}))
     if use_dist:
         dist.destroy_process_group()
 
