@@ -97,7 +97,7 @@ typedef struct mcq_conv_desc {
     float   res_scale;     /* +1 or -1                                                             */
     int32_t tile;          /* 0 = auto; else (log2 split-K << 8) | (MB << 4) | NB forces the wave tile (testing / tuning);
                             * bit 0x400: the 128 x 64 tile of a 3x3 stride-1 layer over pixel PAIRS (same bits, wide epilogue accesses;
-                            * even output width, flags within SiLU / twin / residual / silu' / PixelShuffle), bit 0x800: never */
+                            * even output width, flags within SiLU / twin / residual / silu' / PixelShuffle) */
     const float* post_w;    /* MCQ_CONV_POST_*: the following 1x1 layer's [128, 128] weight from mcq_pack_post1x1_weight_f32 (else NULL; ABI 9) */
     const float* post_bias; /* MCQ_CONV_POST_*: its bias [128] (GDN / IGDN: the folded beta) or NULL                                         */
 } mcq_conv_desc;

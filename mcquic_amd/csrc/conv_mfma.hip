@@ -55,7 +55,7 @@
 #endif
 // (round 6, built and dropped: conv_c32_kernel, a persistent kernel for Neon's 32 -> 32 layers with the whole filter bank in registers
 //  and the input patch double-buffered in LDS by DMA -- bit-identical to the 32 x 32 tile below, and no faster: 185 / 192 / 260 us on
-//  4 x 32 x 512x512 plain / SiLU / residual + twin against 181 / 189 / 230 here.  Source, test and counters: tools/probes/conv_c32.h,
+//  4 x 32 x 512x512 plain / SiLU / residual + twin against 181 / 189 / 230 here.  Source and test last in tree at bca81ee; counters:
 //  docs/experiments.md section 11.3)
 
 namespace {
@@ -84,50 +84,11 @@ struct ConvK {
     int tiles_log2;    // (1 << tiles_log2) output tiles per workgroup
     int total_wgs;     // (persistent Winograd instance) workgroups' worth of tiles along x; the grid may be smaller
     unsigned flags; float res_scale;
-    int xlds;          // GDN / IGDN 1x1 launches whose multiplier IS the input: the k-loop parks the loaded x in LDS for the epilogue
     const float* post_w; const float* post_b;   // MCQ_CONV_POST_*: the following 1x1 layer (accumulator-order operand stream, bias)
     int post_sub;      // MCQ_CONV_POST_IGDN through the PixelShuffle store: the four waves of a workgroup are the four sub-pixel row tiles of ONE pixel tile
 };
 
 constexpr int PRO_NONE = 0, PRO_SILU = 1, PRO_SQUARE = 2;
-#ifndef MCQ_GDN_XLDS
-#define MCQ_GDN_XLDS 0          // build switch: 1 = GDN / IGDN launches keep the streamed x in LDS for the epilogue instead of re-reading it (no gain, see the k-loop)
-#endif
-#ifndef MCQ_TAPS_LR
-#define MCQ_TAPS_LR 1           // build switch: 0 = MCQ_CONV_TAPS_LR launches walk all nine taps (rounds 1-4: 5 / 9 of their MFMAs multiply zeros)
-#endif
-#ifndef MCQ_PAIR
-#define MCQ_PAIR 0              // build switch: 1 = 3x3 stride-1 layers on the 128 x 64 tile run over pixel PAIRS (conv_mfma_kernel<..., PAIR = true>)
-#endif
-#ifndef MCQ_FAST_RSQRT
-#define MCQ_FAST_RSQRT 0        // build switch: 1 = the GDN / IGDN epilogue forms 1/sqrt(s) and sqrt(s) from v_rsq_f32 + one Newton step
-                                // (-10 % on the isolated launch, nothing inside the 32-image step, other bits: left off, docs/experiments.md 10.6)
-#endif
-// s = beta + sum gamma x^2 >= beta > 0 and far from the denormal range (the reparametrised beta is bounded below by 2^-18^2 ... ~1e-6),
-// so none of sqrtf's / the division's range handling is needed: v_rsq_f32 (1 ulp) corrected once is within 1 ulp of the exact value
-__device__ __forceinline__ float mcq_rsqrt_pos(float s) {
-    if (!MCQ_FAST_RSQRT) return 1.0f / sqrtf(s);
-    const float y = __builtin_amdgcn_rsqf(s);
-    const float e = fmaf(-s * y, y, 1.0f);
-    return fmaf(0.5f * y, e, y);
-}
-__device__ __forceinline__ float mcq_sqrt_pos(float s) {
-    if (!MCQ_FAST_RSQRT) return sqrtf(s);
-    const float y = __builtin_amdgcn_rsqf(s);
-    const float r = s * y;
-    const float e = fmaf(-r, r, s);
-    return fmaf(0.5f * y, e, r);
-}
-#ifndef MCQ_XLDS_STEPS
-#define MCQ_XLDS_STEPS 64       // k-steps (channel pairs) parked; below 64 the later channels are re-read from memory (step MCQ_XLDS_STEPS is a dump slot)
-#endif
-constexpr int XLDS_WAVE_FLOATS = (MCQ_XLDS_STEPS < 64 ? MCQ_XLDS_STEPS + 1 : 64) * 64;
-#ifndef MCQ_XLDS_TILES_LOG2
-#define MCQ_XLDS_TILES_LOG2 2   // waves per workgroup of such a launch (log2): 16 KB of LDS per wave bounds the waves resident on a CU
-#endif
-#ifndef MCQ_SHUFFLE_SIDE
-#define MCQ_SHUFFLE_SIDE 1      // build switch (A/B of the dominant instance's register allocation): 0 = the PixelShuffle store takes no side tensors
-#endif
 // 128-row Winograd instance: the epilogue flag set instance `id` (the kernel's PRO slot) is compiled for; 0 = any (run-time flags)
 constexpr unsigned wino_epilogue_flags(int id) {
     return id == 1 ? 0u : id == 2 ? MCQ_CONV_SILU_OUT : id == 3 ? MCQ_CONV_RESIDUAL : id == 4 ? (MCQ_CONV_RESIDUAL | MCQ_CONV_DUAL_SILU)
@@ -479,8 +440,6 @@ next_tile:
 #pragma unroll
     for (int i = 0; i < PGV; ++i) Vn[i] = 0.0f;
     if (WINO && active) wino_transform(0, Vn);
-    // (this wave's 64 x 64 floats of the parking area, at its own lane)
-    float* const xpark = mcq_lds + (size_t)wave * XLDS_WAVE_FLOATS + lane;
     auto kbody = [&](const int sp) __attribute__((always_inline)) {
         // Every VALU instruction between two MFMAs costs the matrix pipe ~10 cycles (tools/probes/mfma_issue.hip), so
         // the k-loop has none: the channel-pair offset of an activation load lives in its buffer descriptor -- one per
@@ -541,14 +500,7 @@ next_tile:
 #pragma unroll
                 for (int nb = 0; nb < NBG; ++nb) {
                     float v = B[sb][nb];
-                    // (round 5, -DMCQ_GDN_XLDS=1, measured and left OFF) y = x f(beta + gamma x^2): the closing multiply needs the very x
-                    // values this loop streams through -- lane (hi, j) loads channel 2 s + hi of pixel j at k-step s -- so they can be
-                    // parked in LDS ([k-step][lane], 16 KB per wave at 128 channels, read back by the same wave) instead of being read a
-                    // second time.  It buys nothing: that second read is served by L2 (PMC counts it, HBM does not see it), and 64 KB of
-                    // LDS per workgroup costs the third resident workgroup -- 1198-1211 -> 1229-1237 us at 32 x 128 x 384x256; with 48 of
-                    // the 64 steps parked (three workgroups stay) 1191-1200, headline unchanged (docs/experiments.md 10.6)
-                    if (MCQ_GDN_XLDS && TAPS == 1 && PRO == PRO_SQUARE && NB == 1 && p.xlds)
-                        xpark[(size_t)(MCQ_XLDS_STEPS < 64 ? min(sp + u, MCQ_XLDS_STEPS) : sp + u) * 64] = v;
+                    // (round 5, built and dropped: GDN / IGDN parking these x values in LDS for the epilogue, docs/experiments.md section 10.6)
                     if (PRO == PRO_SILU) v = mcq_silu(v);
                     if (PRO == PRO_SQUARE) v = v * v;
                     bv[nb] = v;
@@ -669,10 +621,10 @@ next_tile:
                 for (int q = 0; q < 4; ++q) {
                     if (fl & MCQ_CONV_POST_IGDN) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) sacc[q][r] = acc[q][nb][r] * mcq_sqrt_pos(sacc[q][r]);
+                        for (int r = 0; r < 16; ++r) sacc[q][r] = acc[q][nb][r] * sqrtf(sacc[q][r]);
                     } else {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) sacc[q][r] = acc[q][nb][r] * mcq_rsqrt_pos(sacc[q][r]);
+                        for (int r = 0; r < 16; ++r) sacc[q][r] = acc[q][nb][r] * (1.0f / sqrtf(sacc[q][r]));
                     }
 #pragma unroll
                     for (int r = 0; r < 16; ++r) mcq_buffer_store_s(sacc[q][r], yr, pvo, band_so(q, r));
@@ -854,12 +806,12 @@ next_tile:
                         const unsigned so = ((co_row0 >> 2) + 2u * (unsigned)rq) * HoWo * 16u;
                         f32x4v top = f32x4v{v0[rq * 4 + 0], v0[rq * 4 + 1], v1[rq * 4 + 0], v1[rq * 4 + 1]};
                         f32x4v bot = f32x4v{v0[rq * 4 + 2], v0[rq * 4 + 3], v1[rq * 4 + 2], v1[rq * 4 + 3]};
-                        if (MCQ_SHUFFLE_SIDE && (f & MCQ_CONV_DSILU_MUL)) {
+                        if (f & MCQ_CONV_DSILU_MUL) {
                             const f32x4v mt = mcq_buffer_load4_s(mr[0], pvo[0], so), mb2 = mcq_buffer_load4_s(mr[0], pvo[0], so + W2b);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) { top[e] = top[e] * mcq_dsilu(mt[e]); bot[e] = bot[e] * mcq_dsilu(mb2[e]); }
                         }
-                        if (MCQ_SHUFFLE_SIDE && (f & MCQ_CONV_RESIDUAL)) {
+                        if (f & MCQ_CONV_RESIDUAL) {
                             const f32x4v rt = mcq_buffer_load4_s(rr_[0], pvo[0], so), rb = mcq_buffer_load4_s(rr_[0], pvo[0], so + W2b);
 #pragma unroll
                             for (int e = 0; e < 4; ++e) { top[e] = top[e] + p.res_scale * rt[e]; bot[e] = bot[e] + p.res_scale * rb[e]; }
@@ -914,12 +866,12 @@ next_tile:
                         // (round 5) the input-gradient launch of a stride-2 convolution stores through the shuffle; when that convolution
                         // sits behind a SiLU and beside a skip path (ResidualBlockWithStride) the two side operations of the plain
                         // input-gradient launches apply here too, at the shuffled addresses: * silu'(mul), + res
-                        if (MCQ_SHUFFLE_SIDE && (f & MCQ_CONV_DSILU_MUL)) {
+                        if (f & MCQ_CONV_DSILU_MUL) {
                             const f32x2v mt = mcq_buffer_load2_s(mr[nb], pvo[nb], so), mb2 = mcq_buffer_load2_s(mr[nb], pvo[nb], so + W2b);
                             top = f32x2v{top[0] * mcq_dsilu(mt[0]), top[1] * mcq_dsilu(mt[1])};
                             bot = f32x2v{bot[0] * mcq_dsilu(mb2[0]), bot[1] * mcq_dsilu(mb2[1])};
                         }
-                        if (MCQ_SHUFFLE_SIDE && (f & MCQ_CONV_RESIDUAL)) {
+                        if (f & MCQ_CONV_RESIDUAL) {
                             const f32x2v rt = mcq_buffer_load2_s(rr_[nb], pvo[nb], so), rb = mcq_buffer_load2_s(rr_[nb], pvo[nb], so + W2b);
                             top = f32x2v{top[0] + p.res_scale * rt[0], top[1] + p.res_scale * rt[1]};
                             bot = f32x2v{bot[0] + p.res_scale * rb[0], bot[1] + p.res_scale * rb[1]};
@@ -968,22 +920,15 @@ next_tile:
                 }
                 if (f & (MCQ_CONV_GDN | MCQ_CONV_IGDN | MCQ_CONV_GATE | MCQ_CONV_MUL | MCQ_CONV_DSILU_MUL)) {
                     float m[16];
-                    if (MCQ_GDN_XLDS && TAPS == 1 && PRO == PRO_SQUARE && NB == 1 && p.xlds && (MCQ_XLDS_STEPS >= 64 || co_row0 < 2u * MCQ_XLDS_STEPS)) {
-                        // row c = co_row0 + (r & 3) + 8 (r >> 2) + 4 hi of pixel j went through the k-loop at step c >> 1, in the half-wave
-                        // c & 1: each half-wave reads 32 consecutive floats
-                        const float* xw = mcq_lds + (size_t)wave * XLDS_WAVE_FLOATS + (co_row0 >> 1) * 64u + (unsigned)hi * 128u + (unsigned)j;
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) m[r] = xw[(mcq_drow(r, 0) >> 1) * 64 + (mcq_drow(r, 0) & 1) * 32];
-                    } else {
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) m[r] = mcq_buffer_load_s(mr[nb], pvo[nb], so[r]);
-                    }
+                    for (int r = 0; r < 16; ++r) m[r] = mcq_buffer_load_s(mr[nb], pvo[nb], so[r]);
+                    // (round 5, built and dropped: 1/sqrt(s) and sqrt(s) from v_rsq_f32 + one Newton step, docs/experiments.md section 10.6)
                     if (f & MCQ_CONV_GDN) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) v[r] = m[r] * mcq_rsqrt_pos(v[r]);
+                        for (int r = 0; r < 16; ++r) v[r] = m[r] * (1.0f / sqrtf(v[r]));
                     } else if (f & MCQ_CONV_IGDN) {
 #pragma unroll
-                        for (int r = 0; r < 16; ++r) v[r] = m[r] * mcq_sqrt_pos(v[r]);
+                        for (int r = 0; r < 16; ++r) v[r] = m[r] * sqrtf(v[r]);
                     } else if (f & MCQ_CONV_MUL) {
 #pragma unroll
                         for (int r = 0; r < 16; ++r) v[r] = m[r] * v[r];
@@ -1514,10 +1459,8 @@ int launch_tile(ConvK k, int pro, long long tiles, int co_tiles, int ksplit_log2
     k.ks_log2 = ksplit_log2;
     k.slice_pairs = k.S >> ksplit_log2;
     k.tiles_log2 = ksplit_log2 >= 2 ? 0 : 2 - ksplit_log2;           // 4 waves per workgroup, 8 for 8-way split
-    if (!(MCQ_GDN_XLDS && NB == 1 && ksplit_log2 == 0 && k.ks == 1 && pro == PRO_SQUARE)) k.xlds = 0;
-    if (k.xlds) k.tiles_log2 = MCQ_XLDS_TILES_LOG2;
     const int waves = 1 << (k.ks_log2 + k.tiles_log2);
-    const size_t lds = ksplit_log2 ? (size_t)waves * NB * 1024 * sizeof(float) : k.xlds ? (size_t)waves * XLDS_WAVE_FLOATS * sizeof(float) : 0;
+    const size_t lds = ksplit_log2 ? (size_t)waves * NB * 1024 * sizeof(float) : 0;
     const dim3 grid((unsigned)((tiles + (1 << k.tiles_log2) - 1) >> k.tiles_log2), (unsigned)co_tiles, (unsigned)k.nprob);
     const dim3 block(64 * waves);
     // (round 4, measured and removed: `s_setprio 2` for the first-dispatched workgroup of every CU in single-round launches, so that
@@ -1866,7 +1809,7 @@ int conv_validate(const mcq_conv_desc* d) {
     if (fl & MCQ_CONV_SHUFFLE2) {
         if ((d->Cout & 3) || (fl & ~(unsigned)(MCQ_CONV_SHUFFLE2 | MCQ_CONV_SILU_IN | MCQ_CONV_SQUARE_IN | MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D | MCQ_CONV_WINOGRAD2D16 |
                                                MCQ_CONV_DSILU_MUL | MCQ_CONV_RESIDUAL | MCQ_CONV_POST_IGDN))) return MCQ_EINVAL;
-        if ((fl & (MCQ_CONV_DSILU_MUL | MCQ_CONV_RESIDUAL)) && (!MCQ_SHUFFLE_SIDE || (fl & (MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D | MCQ_CONV_WINOGRAD2D16))))
+        if ((fl & (MCQ_CONV_DSILU_MUL | MCQ_CONV_RESIDUAL)) && (fl & (MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D | MCQ_CONV_WINOGRAD2D16)))
             return MCQ_EINVAL;
     }
     // one image's input slab plus the prefetch rings' over-read (up to 8 channels) must stay below 2 GiB: byte offsets and
@@ -1884,7 +1827,7 @@ bool t16_takes(int N, int Cin, int H, int W, int Cout, int ksize, int stride, un
 int conv_launch(const mcq_conv_desc* descs, int nprob, void* stream) {
     const mcq_conv_desc* d = descs;
     const unsigned fl = d->flags & ~(unsigned)MCQ_CONV_TAPS_LR;
-    const bool lr4 = MCQ_TAPS_LR && (d->flags & MCQ_CONV_TAPS_LR);      // only the filter's lower-right 2 x 2 taps are non-zero
+    const bool lr4 = d->flags & MCQ_CONV_TAPS_LR;      // only the filter's lower-right 2 x 2 taps are non-zero
     ConvK k;
     k.x = d->x; k.wp = d->w_packed;
     k.wp64 = k.wp + section_floats(d->Cout, d->Cin, d->ksize, 4);
@@ -1900,10 +1843,6 @@ int conv_launch(const mcq_conv_desc* descs, int nprob, void* stream) {
     k.flags = fl; k.res_scale = d->res_scale;
     k.nprob = nprob;
     k.post_w = d->post_w; k.post_b = d->post_bias; k.post_sub = 0;
-    // GDN / IGDN whose multiplier is the launch's own input, all channels of it inside one k-loop of <= 64 steps (launch_tile
-    // clears this again for the tiles without the LDS parking area)
-    k.xlds = (fl & (MCQ_CONV_GDN | MCQ_CONV_IGDN)) && d->ksize == 1 && d->stride == 1 && d->Cin == d->Cout && d->Cin <= 128;
-    for (int c = 0; c < nprob; ++c) if (descs[c].mul != descs[c].x) k.xlds = 0;
     for (int c = 1; c < MCQ_CONV_MAX_MULTI; ++c) {
         const mcq_conv_desc* e = descs + (c < nprob ? c : 0);
         ConvPtrs& a = k.alt[c - 1];
@@ -2139,16 +2078,13 @@ int conv_launch(const mcq_conv_desc* descs, int nprob, void* stream) {
     }
     const int pro = (fl & MCQ_CONV_SILU_IN) ? PRO_SILU : (fl & MCQ_CONV_SQUARE_IN) ? PRO_SQUARE : PRO_NONE;
     long long ptiles = (tb + NB - 1) / NB;
-    // (round 5) the 128 x 64 tile of a 3x3 stride-1 layer over 32 PAIRS of horizontally adjacent pixels (tile bit 0x400 forces it,
-    // 0x800 forbids it): pair blocks shaped (32 >> b) rows x (1 << b) pairs, b by the fewest wasted lanes
+    // (round 5) the 128 x 64 tile of a 3x3 stride-1 layer over 32 PAIRS of horizontally adjacent pixels, when tile bit 0x400 asks
+    // for it: pair blocks shaped (32 >> b) rows x (1 << b) pairs, b by the fewest wasted lanes
     const bool pair_ok = !post && !lr4 && MB == 4 && (NB == 2 || dsilu41) && ksl == 0 && d->ksize == 3 && d->stride == 1 && pro == PRO_NONE && (k.Wo & 1) == 0 &&
                          !(fl & ~(unsigned)(MCQ_CONV_SILU_OUT | MCQ_CONV_RESIDUAL | MCQ_CONV_DUAL_SILU | MCQ_CONV_DSILU_MUL | MCQ_CONV_SHUFFLE2));
-    // on its own it takes the launches whose pair tiles are ONE round of the chip (1536 < waves <= 2048, two per SIMD: 8 x 128 x 128 x 128,
-    // 8 x 128 -> 512 x 64 x 64): with nothing behind a wave to hide its prologue and epilogue the shorter instruction streams pay
-    // (isolated 280-299 us against 301-332 for the best other tile); in multi-round launches they do not (B32: -0.7 % without a twin,
-    // +1 % with residual + twin)
-    bool pair = false;
-    if (pair_ok) {
+    // (round 5, built and dropped: the launcher choosing it on its own for one-round launches, docs/experiments.md section 10.8)
+    const bool pair = pair_ok && (d->tile & 0x400);
+    if (pair) {
         const int Wp = k.Wo / 2;
         int bl = 5; double bu = -1.0;
         for (int lg = 5; lg >= 2; --lg) {
@@ -2158,9 +2094,8 @@ int conv_launch(const mcq_conv_desc* descs, int nprob, void* stream) {
             if (util > bu + 1e-9) { bu = util; bl = lg; }
         }
         const int pnbx = (Wp + (1 << bl) - 1) >> bl, pnby = (k.Ho + (32 >> bl) - 1) / (32 >> bl);
-        const long long pt = (long long)k.N * pnbx * pnby, pair_waves = pt * ((co32 + 3) / 4) * nprob;
-        pair = (d->tile & 0x400) || (MCQ_PAIR && !(d->tile & 0x800) && pair_waves > 1536 && pair_waves <= 2048);
-        if (pair) { NB = 2; k.bw_log2 = bl; k.nbx = pnbx; k.nby = pnby; ptiles = pt; k.total_blocks = (int)pt; }
+        const long long pt = (long long)k.N * pnbx * pnby;
+        NB = 2; k.bw_log2 = bl; k.nbx = pnbx; k.nby = pnby; ptiles = pt; k.total_blocks = (int)pt;
     }
     const int co_tiles = post ? 1 : (co32 + MB - 1) / MB;      // (POST through the shuffle: the four row tiles are the waves of a workgroup)
     // the epilogue addresses one image of the output (and of every side input) through a 32-bit buffer offset,

@@ -335,42 +335,6 @@ def test_group_norm_large_runs(dev, shape, groups):
     assert torch.equal(y, y2)
 
 
-def test_group_norm_one_launch_equals_two_launches(dev):
-    """Round 6: statistics and normalisation of the chunked GroupNorm in ONE launch per direction (workgroups of a run meet on a
-    device-scope counter and finish from registers) -- bit for bit the two-launch form's outputs (MCQUIC_AMD_GN_FUSED=0, read once
-    per process: the other form runs in a child), forward with statistics and SiLU twin, backward with parameter gradients.  The
-    last shape's runs are longer than the one-launch form takes (320 workgroups): both processes run the same kernels there."""
-    import hashlib
-    import os
-    import subprocess
-    import sys
-    code = """
-import hashlib, sys, torch
-from mcquic_amd import ops
-dev = torch.device('cuda:0')
-for shape, groups in (((8, 32, 512, 512), 32), ((2, 32, 192, 192), 32), ((1, 8, 128, 128), 1), ((2, 16, 300, 211), 4), ((1, 8, 512, 640), 1)):
-    g = torch.Generator().manual_seed(7)
-    x = (torch.randn(shape, generator=g) * 1.5 + 0.3).to(dev)
-    c = shape[1]
-    gamma, beta, dy = torch.randn(c, generator=g).to(dev), torch.randn(c, generator=g).to(dev), torch.randn(shape, generator=g).to(dev)
-    h = hashlib.sha256()
-    for _ in range(3):                                             # (several launches in a row: the counters start from zero every time)
-        y, mean, rstd = ops.group_norm(x, gamma, beta, groups, 1e-5, dual_silu=True, want_stats=True)
-        dx, dw, db = ops.group_norm_bwd(x, dy, gamma, mean, rstd, groups)
-        for t in (y, ops.silu_twin(y), mean, rstd, dx, dw, db):
-            h.update(t.cpu().numpy().tobytes())
-    print('GN', shape, h.hexdigest())
-"""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    outs = {}
-    for fused in ("1", "0"):
-        env = dict(os.environ, MCQUIC_AMD_GN_FUSED=fused, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-        run = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=env, cwd=root)
-        assert run.returncode == 0, run.stderr[-2000:]
-        outs[fused] = [ln for ln in run.stdout.splitlines() if ln.startswith("GN ")]
-    assert len(outs["1"]) == 5 and outs["1"] == outs["0"]
-
-
 def test_grouped_gdn_operand_refresh_equals_layer_by_layer(dev):
     """autograd.refresh_gdn_operands (one re-parametrisation launch + two grouped packs for all stale GDN layers) leaves the same
     folded parameters and operand streams as the per-layer path, in place (addresses kept) when the parameters change again."""
@@ -403,12 +367,9 @@ def test_grouped_gdn_operand_refresh_equals_layer_by_layer(dev):
 
 
 @pytest.mark.parametrize("kind", ["compressor", "neon_dense_norm"])
-def test_deferred_reduce_passes_give_the_same_gradients(dev, kind, monkeypatch):
+def test_deferred_reduce_passes_match_plain_backward(dev, kind):
     """autograd.backward (weight-gradient reduce passes recorded and run batched at the end of the pass) against a plain
-    loss.backward() (every launch reduces right away): every parameter gradient bit for bit -- same partial tiles, same order.
-    Third mode: the opt-in queue of round 6 (MCQUIC_AMD_WGRAD_SIDE=1: the weight-gradient launches themselves issued in batches
-    on a side stream, docs/experiments.md 11.8) -- the same bits again (a gradient the engine cloned because it saw a second
-    reference to a queued output would hold whatever the buffer held before the launch ran)."""
+    loss.backward() (every launch reduces right away): every parameter gradient bit for bit -- same partial tiles, same order."""
     from mcquic_amd import Compressor, Neon, ops
     from mcquic_amd.autograd import backward, mse_loss
     torch.manual_seed(3407)
@@ -423,8 +384,7 @@ def test_deferred_reduce_passes_give_the_same_gradients(dev, kind, monkeypatch):
         us = [(torch.rand((4, 1, s, s, 256), generator=g).to(dev), torch.rand((4, 1, s, s, 256), generator=g).to(dev)) for s in (2, 2, 4, 8)]
     grads = {}
     ema0 = [f.detach().clone() for f in model._quantizer._entropyCoder._freqEMA]
-    for mode in ("plain", "deferred", "queued"):
-        monkeypatch.setattr(ops, "_WGRAD_SIDE", mode == "queued")
+    for mode in ("plain", "deferred"):
         for p in model.parameters():
             p.grad = None
         with torch.no_grad():                                       # (the forward moves the frequency EMA, which the random drop reads)
@@ -436,13 +396,12 @@ def test_deferred_reduce_passes_give_the_same_gradients(dev, kind, monkeypatch):
         else:
             backward(loss)
         assert ops._lib.load().mcq_wgrad_pending() == 0
-        assert not ops._defer["queue"] and not ops._defer["keep"] and ops._defer["side"] is None
+        assert not ops._defer["keep"]
         torch.cuda.synchronize()
         grads[mode] = {n: p.grad.clone() for n, p in model.named_parameters() if p.grad is not None}
-    assert set(grads["plain"]) == set(grads["deferred"]) == set(grads["queued"]) and len(grads["plain"]) > 50
+    assert set(grads["plain"]) == set(grads["deferred"]) and len(grads["plain"]) > 50
     for n in grads["plain"]:
         assert torch.equal(grads["plain"][n], grads["deferred"][n]), n
-        assert torch.equal(grads["plain"][n], grads["queued"][n]), n
 
 
 def test_deferral_steps_aside_for_accumulation_hooks_and_frozen_weights(dev):
