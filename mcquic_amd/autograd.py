@@ -55,6 +55,7 @@ class ConvFn(torch.autograd.Function):
         sy = ops.silu_twin(y)                       # silu(y) from the same launch, for a consumer that starts with an activation
         ctx.save_for_backward(x, weight)
         ctx.conv, ctx.shuffle2, ctx.has_bias, ctx.has_res = conv, shuffle2, bias is not None, res is not None
+        ctx.wgrad_slots = (1, 2)                    # (weight, bias: their gradients may be deferred, _leaves_take_by_stealing)
         if sy is not None:
             ctx.mark_non_differentiable(sy)
         ctx.set_materialize_grads(False)
@@ -227,10 +228,17 @@ def _leaves_take_by_stealing(roots) -> bool:
     """Deferring the weight gradients' reduce passes hands the autograd engine dW / db tensors whose values only exist after the
     flush.  That is sound only if nothing LOOKS at them before: every parameter the pass reaches must take its gradient by stealing
     the tensor -- `.grad is None` (a second backward() without zero_grad would run `p.grad += dW` on unreduced memory) and no tensor
-    hook / post-accumulate hook on it (they would be called with it).  Walks the graph under `roots` once (a few hundred nodes).
+    hook / post-accumulate hook on it (they would be called with it) -- and every deferred dW / db must arrive at such a leaf ALONE:
+      * a parameter read by two nodes (tied convolution weights) has its gradients summed by the engine's input buffer before
+        AccumulateGrad runs: no AccumulateGrad node may have a second edge beside one that carries a deferred gradient;
+      * a weight that is itself the output of an op (w * mask, a re-parametrisation) hands its dW to that op's backward node during
+        the pass: every edge that carries a deferred gradient (`ctx.wgrad_slots` of the nodes whose backward defers: the forward
+        inputs that are convolution weights / biases) must end in an AccumulateGrad node.
+    Walks the graph under `roots` once, every edge once (a few hundred nodes).
     (Hooks put on the AccumulateGrad nodes themselves from C++ -- torch DDP's reducer -- are invisible from here: with DDP use
     `loss.backward()`, see `backward`.)"""
     seen, stack = set(), [t.grad_fn for t in roots if t is not None and t.grad_fn is not None]
+    edges = {}                                                  # AccumulateGrad node -> [edges into it, any of them deferred]
     while stack:
         fn = stack.pop()
         if fn in seen:
@@ -241,7 +249,20 @@ def _leaves_take_by_stealing(roots) -> bool:
             if v.grad is not None or getattr(v, "_backward_hooks", None) or getattr(v, "_post_accumulate_grad_hooks", None):
                 return False
             continue
-        stack.extend(nf for nf, _ in fn.next_functions if nf is not None)
+        slots = getattr(fn, "wgrad_slots", ())
+        for i, (nf, _) in enumerate(fn.next_functions):
+            if nf is None:
+                continue
+            deferred = i in slots
+            if hasattr(nf, "variable"):
+                e = edges.setdefault(nf, [0, False])
+                e[0] += 1
+                e[1] = e[1] or deferred
+                if e[0] > 1 and e[1]:
+                    return False
+            elif deferred:
+                return False
+            stack.append(nf)
     return True
 
 
@@ -384,6 +405,7 @@ class ResidualBlockFn(torch.autograd.Function):
         y, sy, saved = _rb_forward(block, x, sx)
         ctx.save_for_backward(*saved)
         ctx.block = block
+        ctx.wgrad_slots = range(2, 1 + len(rest))
         ctx.mark_non_differentiable(sy)
         ctx.set_materialize_grads(False)        # (or autograd fills a zero tensor of sy's size for `_dsy` on every backward)
         return y, sy
@@ -419,6 +441,7 @@ class AttentionBlockFn(torch.autograd.Function):
         sout = ops.silu_twin(out)
         ctx.save_for_backward(a, b, *saved)
         ctx.block = block
+        ctx.wgrad_slots = range(2, 1 + len(rest))
         ctx.mark_non_differentiable(sout)
         ctx.set_materialize_grads(False)
         return out, sout
@@ -593,6 +616,7 @@ class LockstepFn(torch.autograd.Function):
         ctx.layers = [layer for _, layer, _ in tape]
         ctx.save_for_backward(*tensors)
         ctx.stacks, ctx.k = stacks, k
+        ctx.wgrad_slots = range(1 if shared else k, len(args) - 1)
         return tuple(ys)
 
     @staticmethod
@@ -807,6 +831,7 @@ class ScaleBlockFn(torch.autograd.Function):
         sy = ops.silu_twin(y)
         ctx.save_for_backward(x, sx, t, u, beta_p, gamma_p, w1, w2, ws)
         ctx.block, ctx.up, ctx.packed, ctx.back, ctx.bounds = block, up, packed, back, bounds
+        ctx.wgrad_slots = (2, 3, 6, 7, 8, 9)        # (the three convolutions; beta / gamma are reduced right away, _gdn_backward)
         ctx.mark_non_differentiable(sy)
         ctx.set_materialize_grads(False)
         return y, sy

@@ -38,11 +38,16 @@ __device__ __forceinline__ float block_sum(float v, float* slots) {
 
 // (mean, rstd) of one contiguous run; every thread returns the same values
 __device__ __forceinline__ void run_moments(const float* __restrict__ x, int count, float eps, float* slots, float& mean, float& rstd) {
-    const bool vec = (((uintptr_t)x & 15) == 0) && (count % 4 == 0);
+    // (a run of whole quads is summed quad by quad whatever its address: a tensor that starts 4 bytes into an allocation gets the
+    //  bits of its 16-byte-aligned copy, from 4-byte loads -- tests/test_gpu_leaf_ops.py::test_views_group_norm)
+    const bool quads = count % 4 == 0;
+    const bool vec = (((uintptr_t)x & 15) == 0) && quads;
     float s = 0.0f;
     if (vec) {
         const f32x4v* x4 = (const f32x4v*)x;
         for (int i = threadIdx.x; i < count / 4; i += kThreads) { const f32x4v v = x4[i]; s += (v[0] + v[1]) + (v[2] + v[3]); }
+    } else if (quads) {
+        for (int i = threadIdx.x; i < count / 4; i += kThreads) s += (x[4 * i] + x[4 * i + 1]) + (x[4 * i + 2] + x[4 * i + 3]);
     } else {
         for (int i = threadIdx.x; i < count; i += kThreads) s += x[i];
     }
@@ -53,6 +58,11 @@ __device__ __forceinline__ void run_moments(const float* __restrict__ x, int cou
         for (int i = threadIdx.x; i < count / 4; i += kThreads) {
             const f32x4v v = x4[i];
             const float a = v[0] - mean, b = v[1] - mean, c = v[2] - mean, d = v[3] - mean;
+            q += (a * a + b * b) + (c * c + d * d);
+        }
+    } else if (quads) {
+        for (int i = threadIdx.x; i < count / 4; i += kThreads) {
+            const float a = x[4 * i] - mean, b = x[4 * i + 1] - mean, c = x[4 * i + 2] - mean, d = x[4 * i + 3] - mean;
             q += (a * a + b * b) + (c * c + d * d);
         }
     } else {

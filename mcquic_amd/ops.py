@@ -131,6 +131,15 @@ def _dev(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
     return t if t.is_contiguous() else t.contiguous()
 
 
+def _dev16(t: torch.Tensor, name: str) -> torch.Tensor:
+    """`_dev` for the operands of kernels written for 16-byte-aligned tensors (the 128-bit loads of add_kernel / add3_kernel, the
+    64- / 128-bit side-tensor accesses of the convolution's pixel-pair and PixelShuffle epilogues, none of which look at the
+    address): a contiguous view that starts elsewhere in its allocation (t.flatten()[1:], a slice of a flat gradient buffer) is
+    copied to a fresh one.  torch's allocator hands out 512-byte-aligned blocks, so tensors that own their storage pass as they are."""
+    t = _dev(t, name)
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
 def _ptr(t: Optional[torch.Tensor]):
     """Device address for a `void*` parameter / struct field (ctypes converts the int; None = NULL)."""
     return None if t is None else t.data_ptr()
@@ -366,7 +375,7 @@ def _conv_desc(x: torch.Tensor, w: PackedConv, stride: int = 1, *, silu_in: bool
         twin = silu_twin(x)
         if twin is not None:
             x, silu_in = twin, False
-    x = _dev(x, "x")
+    x = _dev16(x, "x")
     n, cin, h, wd = x.shape
     if cin != w.cin:
         raise ValueError(f"channel mismatch: x has {cin}, weight expects {w.cin}")
@@ -393,18 +402,18 @@ def _conv_desc(x: torch.Tensor, w: PackedConv, stride: int = 1, *, silu_in: bool
     mul = None
     if res is not None:
         flags |= CONV_RESIDUAL
-        res = _dev(res, "res")
+        res = _dev16(res, "res")
         if res.shape != y.shape:
             raise ValueError(f"residual shape {tuple(res.shape)} != output shape {tuple(y.shape)}")
     for flag, t in ((CONV_GDN, gdn_mul), (CONV_IGDN, igdn_mul), (CONV_GATE, gate_mul), (CONV_MUL, mul_in), (CONV_DSILU_MUL, dsilu_mul)):
         if t is not None:
             if not (flag == CONV_GATE and post_gate is not None):     # (post_gate: the gate closes the FUSED 1x1 layer, MCQ_CONV_POST_GATE)
                 flags |= flag
-            mul = _dev(t, "mul")
+            mul = _dev16(t, "mul")
             if mul.shape != y.shape:
                 raise ValueError(f"mul shape {tuple(mul.shape)} != output shape {tuple(y.shape)}")
     if gate_id is not None:
-        gate_id = _dev(gate_id, "gate_id")
+        gate_id = _dev16(gate_id, "gate_id")
         if gate_id.shape != y.shape:
             raise ValueError("gate identity shape mismatch")
     post = None
@@ -943,7 +952,7 @@ def vq_dequant_soft(index: torch.Tensor, hot: torch.Tensor, cb: PackedCodebook, 
 
 
 def add(a: torch.Tensor, b: torch.Tensor, dual_silu: bool = False) -> torch.Tensor:
-    a, b = _dev(a, "a"), _dev(b, "b")
+    a, b = _dev16(a, "a"), _dev16(b, "b")
     if a.shape != b.shape:
         raise ValueError("add: shape mismatch")
     out = torch.empty_like(a)
@@ -957,7 +966,7 @@ def add(a: torch.Tensor, b: torch.Tensor, dual_silu: bool = False) -> torch.Tens
 
 def add3(a: torch.Tensor, b: torch.Tensor, c: torch.Tensor) -> torch.Tensor:
     """(a + b) + c in one launch (mcq_add3_f32)."""
-    a, b, c = _dev(a, "a"), _dev(b, "b"), _dev(c, "c")
+    a, b, c = _dev16(a, "a"), _dev16(b, "b"), _dev16(c, "c")
     if a.shape != b.shape or a.shape != c.shape:
         raise ValueError("add3: shape mismatch")
     out = torch.empty_like(a)

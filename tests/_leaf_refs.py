@@ -1,0 +1,270 @@
+"""Inputs and references for the leaf kernels of the training step (tests/test_gpu_leaf_ops.py holds the HIP kernels to them,
+tests/test_leaf_ops_reference.py holds the float32 restatements to float64 autograd on the CPU).  Nothing here imports
+mcquic_amd: every reference is the mathematics, written with torch on the CPU.
+
+Two kinds of reference per op:
+  *64       the operation in float64 (torch.autograd where it is a derivative)
+  *_f32     the kernel's own operation order, one float32 rounding per operation (the library is built with -ffp-contract=off;
+            float divide and square root are correctly rounded on both sides): what a correct kernel returns bit for bit where
+            no transcendental is involved, and the yardstick for the ulp bars where one is (4x its own worst error)."""
+import torch
+
+F32 = torch.float32
+FLAT_SIZES = (1, 3, 255, 256, 257, 1023, 4097, 2 ** 20 + 3)          # every n % 4, both sides of a 256-thread workgroup and of a 4096 chunk
+NET_SHAPE = (8, 128, 64, 64)                                         # one network-sized activation (4 M elements)
+SHAPES = ((1, 1, 1, 1), (2, 3, 5, 7), (3, 33, 1, 1), (2, 40, 9, 13), (1, 64, 32, 32), (35, 5, 3, 3))
+SILU_DZERO = -1.2784645427610738                                     # the zero of silu'
+ULP_FLOOR = 2.0 ** -80                                               # below this magnitude (8e-25) errors count absolutely (see ulp_err)
+
+
+def f32(v) -> torch.Tensor:
+    """A Python float as the float32 scalar a `float` kernel argument receives."""
+    return torch.tensor(float(v), dtype=F32)
+
+
+def sqrt_f32(t):
+    """The correctly rounded float32 square root.  Not torch.sqrt: ATen's vectorised float32 kernel is up to an ulp off on AVX-512
+    hosts (its scalar path is exact, so one- and three-element tensors agreed and 255-element ones did not -- found by the first
+    GPU run of test_gdn_bwd_prep, where the device's sqrtf WAS the correctly rounded one).  The float64 root rounded to float32 is:
+    53 >= 2 * 24 + 2 bits make the double rounding innocuous."""
+    return torch.sqrt(t.double()).to(F32)
+
+
+def div_f32(a, b):
+    """The correctly rounded float32 quotient, through float64 for the same reason."""
+    return (torch.as_tensor(a, dtype=torch.float64) / b.double()).to(F32)
+
+
+def rand(shape, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return ((torch.rand(shape, generator=g) * 2 - 1) * scale).to(F32)
+
+
+def randn(shape, seed, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return (torch.randn(shape, generator=g) * scale).to(F32)
+
+
+def special_x(n, seed):
+    """n arguments of a sigmoid: [-30, 30] evenly (shuffled), then -- room permitting -- the points where kernels go wrong written over
+    the head: +-87 and +-100 (expf(-x) overflows to inf at x < -88.7), +-0, and a cluster around the zero of silu'."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.linspace(-30.0, 30.0, n)[torch.randperm(n, generator=g)].to(F32) if n > 1 else torch.tensor([0.75], dtype=F32)
+    sp = torch.tensor([87.0, -87.0, 100.0, -100.0, 0.0, -0.0, SILU_DZERO, SILU_DZERO + 1e-3, SILU_DZERO - 1e-3, -88.5, -89.0, 16.7, -16.7, 1e-30, -1e-30],
+                      dtype=F32)
+    k = min(n // 2, sp.numel())
+    x[:k] = sp[:k]
+    return x
+
+
+def ulp_err(got, want64, scale64=None):
+    """|got - want| in units of the float32 spacing at max(|want|, |scale|, 2^-80).  `scale`: the magnitude the result is
+    accurate RELATIVE TO where that is not its own (a sum that cancels: its larger operand; silu' near its zero: |dy|).  The floor
+    keeps values no training step can tell from zero (float32 denormals included) from being measured relative to themselves."""
+    ref = want64.abs()
+    if scale64 is not None:
+        ref = torch.maximum(ref, scale64.abs())
+    ref = ref.clamp_min(ULP_FLOOR).float()
+    spacing = (torch.nextafter(ref, torch.full_like(ref, float("inf"))) - ref).double()
+    return (got.double() - want64).abs() / spacing
+
+
+# ---- SiLU backward ----------------------------------------------------------------------------------------------------------------
+def silu_bwd64(x, dy, other=None):
+    """dy * silu'(x) (+ other) from float64 autograd through x * sigmoid(x)."""
+    xd = x.double().requires_grad_()
+    (xd * torch.sigmoid(xd)).backward(dy.double())
+    return xd.grad if other is None else xd.grad + other.double()
+
+
+def silu_bwd_scale64(x, dy, other=None):
+    """What silu_bwd is accurate relative to: |dy| within 1/4 of the zero of silu' (s (1 + x (1 - s)) cancels there), the larger
+    operand of the closing addition with `other`."""
+    near = (x.double() - SILU_DZERO).abs() <= 0.25
+    sc = torch.where(near, dy.double().abs(), torch.zeros((), dtype=torch.float64))
+    if other is not None:
+        xd = x.double()
+        s = torch.sigmoid(xd)
+        sc = torch.maximum(sc, torch.maximum((dy.double() * s * (1 + xd * (1 - s))).abs(), other.double().abs()))
+    return sc
+
+
+def silu_bwd_f32(x, dy, other=None):
+    s = 1.0 / (1.0 + torch.exp(-x))
+    v = dy * (s * (1.0 + x * (1.0 - s)))
+    return v if other is None else v + other
+
+
+# ---- attention gate ------------------------------------------------------------------------------------------------------------------
+def gate64(a, b, x):
+    return a.double() * torch.sigmoid(b.double()) + x.double()
+
+
+def gate_scale64(a, b, x):
+    return torch.maximum((a.double() * torch.sigmoid(b.double())).abs(), x.double().abs())
+
+
+def gate_f32(a, b, x):
+    return a * (1.0 / (1.0 + torch.exp(-b))) + x
+
+
+def silu64(v):
+    return v.double() * torch.sigmoid(v.double())
+
+
+def silu_f32(v):
+    return v / (1.0 + torch.exp(-v))
+
+
+def gate_bwd64(a, b, dout):
+    """(da, db) from float64 autograd through a * sigmoid(b) + x."""
+    ad, bd = a.double().requires_grad_(), b.double().requires_grad_()
+    xd = torch.zeros_like(ad, requires_grad=True)
+    (ad * torch.sigmoid(bd) + xd).backward(dout.double())
+    assert torch.equal(xd.grad, dout.double())
+    return ad.grad, bd.grad
+
+
+def gate_bwd_db_scale64(a, b, dout):
+    """db = dout a s (1 - s): for b > 0 the factor 1 - s cancels (s is within half an ulp of 1 from b = 17 on), so the product is
+    accurate relative to the factor's largest value, |dout a| / 4, not to itself; for b <= 0 nothing cancels (scale 0)."""
+    return torch.where(b.double() > 0, (dout.double() * a.double()).abs() * 0.25, torch.zeros((), dtype=torch.float64))
+
+
+def gate_bwd_f32(a, b, dout):
+    s = 1.0 / (1.0 + torch.exp(-b))
+    return dout * s, dout * a * s * (1.0 - s)
+
+
+# ---- GDN / IGDN backward, element-wise part ------------------------------------------------------------------------------------------
+def gdn_inputs(n, seed):
+    """(x, s, dy): s log-uniform over [1e-6, 1e3] with both ends present."""
+    x, dy = randn((n,), seed, 2.0), randn((n,), seed + 1)
+    g = torch.Generator().manual_seed(seed + 2)
+    s = (10.0 ** (torch.rand(n, generator=g, dtype=torch.float64) * 9.0 - 6.0)).to(F32)
+    if n >= 2:
+        s[0], s[1] = 1e-6, 1e3
+    return x, s, dy
+
+
+def gdn_bwd_prep64(x, s, dy, inverse):
+    """(d y / d x at fixed s, d y / d s) times dy, from float64 autograd through y = x * s^(+-1/2)."""
+    xd, sd = x.double().requires_grad_(), s.double().requires_grad_()
+    (xd * sd ** (0.5 if inverse else -0.5)).backward(dy.double())
+    return xd.grad, sd.grad
+
+
+def gdn_bwd_prep_f32(x, s, dy, inverse):
+    root = sqrt_f32(s)
+    rs = div_f32(1.0, root)
+    if inverse:
+        return dy * root, dy * x * (0.5 * rs)
+    return dy * rs, dy * x * (-0.5 * rs * rs * rs)
+
+
+# ---- non-negative re-parametrisation ------------------------------------------------------------------------------------------------
+class _LowerBound(torch.autograd.Function):
+    """max(p, bound) whose gradient passes where p >= bound or where it is negative (it pushes p up): the rule the reference puts
+    in front of its squared parameters."""
+
+    @staticmethod
+    def forward(ctx, p, bound):
+        ctx.save_for_backward(p, bound)
+        return torch.max(p, bound)
+
+    @staticmethod
+    def backward(ctx, g):
+        p, bound = ctx.saved_tensors
+        return torch.where((p >= bound) | (g < 0), g, torch.zeros_like(g)), None
+
+
+def reparam_inputs(n, seed, bound):
+    """(p, dfolded) around `bound`: p == float32(bound) exactly, p just below / above it, p < bound with a gradient of each sign,
+    gradients of exactly +-0."""
+    p, d = randn((n,), seed, 0.5) + 0.3, randn((n,), seed + 1)
+    b = float(f32(bound))
+    head = [(b, 1.0), (b, -1.0), (b, 0.0), (b - 0.25, 1.0), (b - 0.25, -1.0), (b - 0.25, 0.0), (b - 0.25, -0.0), (b + 0.25, 0.0),
+            (float(torch.nextafter(f32(b), f32(-1e9))), 2.0), (float(torch.nextafter(f32(b), f32(1e9))), 2.0), (-3.0, 1.0), (-3.0, -1.0)]
+    k = min(n, len(head))
+    for i in range(k):
+        p[i], d[i] = head[i]
+    return p, d
+
+
+def reparam64(p, bound, pedestal):
+    return torch.maximum(p.double(), f32(bound).double()) ** 2 - f32(pedestal).double()
+
+
+def reparam_f32(p, bound, pedestal):
+    v = torch.maximum(p, f32(bound))
+    return v * v - f32(pedestal)
+
+
+def reparam_bwd64(p, dfolded, bound, pedestal=0.0):
+    pd = p.double().requires_grad_()
+    (_LowerBound.apply(pd, f32(bound).double()) ** 2 - pedestal).backward(dfolded.double())
+    return pd.grad
+
+
+def reparam_bwd_f32(p, dfolded, bound):
+    g = (2.0 * torch.maximum(p, f32(bound))) * dfolded
+    return torch.where((p >= f32(bound)) | (g < 0), g, torch.zeros_like(g))
+
+
+# ---- linear forms ------------------------------------------------------------------------------------------------------------------------
+def axpby_f32(a, b, alpha, beta):
+    return f32(alpha) * a + f32(beta) * b
+
+
+def add3_f32(a, b, c):
+    return (a + b) + c
+
+
+def mse_bwd64(a, b, dloss):
+    ad, bd = a.double().requires_grad_(), b.double().requires_grad_()
+    ((ad - bd) ** 2).mean().backward(dloss.double().reshape(()))
+    return ad.grad, bd.grad
+
+
+def mse_bwd_f32(a, b, dloss):
+    scale = torch.tensor(2.0 / float(a.numel()), dtype=torch.float64).to(F32)        # (float)(2.0 / (double)n)
+    g = (a - b) * (scale * dloss.reshape(()))
+    return g, -g
+
+
+def clip_f32(x, norm, max_norm, eps):
+    """x scaled by max_norm / (norm + eps) where that is < 1 (a NaN compares false: untouched)."""
+    coef = div_f32(f32(max_norm), norm.reshape(()) + f32(eps))
+    return x * coef if bool(coef < 1.0) else x.clone()
+
+
+# ---- reductions: the error bounds ----------------------------------------------------------------------------------------------------------
+def channel_sum_chain(n, hw):
+    """Longest chain of float32 additions behind one output of channel_sum: the launcher cuts the batch into min(n, 16) chunks (one
+    for n == 1), a thread adds ceil(n / chunks) * ceil(hw / 256) terms, an 8-level tree follows, then the chunks in order."""
+    chunks = min(n, 16) if n > 1 else 1
+    per = -(-n // chunks)
+    return per * -(-hw // 256) + 8 + (chunks if chunks > 1 else 0), chunks
+
+
+# ---- views with the values of a fresh tensor ----------------------------------------------------------------------------------------------
+def views_of(t):
+    """[(name, tensor)]: the same values as `t` behind (1) a channel slice of a wider tensor, (2) a transposed map -- both
+    non-contiguous -- and (3) a contiguous view that starts one ELEMENT into its allocation (float32: only 4-byte aligned)."""
+    out = []
+    if t.dim() == 4:
+        wide = torch.zeros((t.shape[0], t.shape[1] + 2) + tuple(t.shape[2:]), dtype=t.dtype, device=t.device)
+        wide[:, 1:-1] = t
+        out.append(("channel slice", wide[:, 1:-1]))
+        out.append(("transposed map", t.transpose(-1, -2).contiguous().transpose(-1, -2)))
+    elif t.dim() == 1:
+        wide = torch.zeros(2 * t.numel(), dtype=t.dtype, device=t.device)
+        wide[::2] = t
+        out.append(("stride 2", wide[::2]))
+    buf = torch.zeros(t.numel() + 1, dtype=t.dtype, device=t.device)
+    buf[1:] = t.reshape(-1)
+    out.append(("offset 1", buf[1:].view(t.shape)))
+    for name, v in out:
+        assert torch.equal(v, t), name
+    assert out[-1][1].storage_offset() == 1
+    return out

@@ -468,6 +468,87 @@ def test_deferral_steps_aside_for_accumulation_hooks_and_frozen_weights(dev):
         assert torch.equal(v, once[n]), n
 
 
+def test_deferral_steps_aside_for_shared_and_derived_weights(dev):
+    """The deferred reduce passes hand the engine dW / db tensors that only the flush writes: sound while each reaches an
+    AccumulateGrad node alone.  (a) two Conv2d layers sharing one weight Parameter: the engine SUMS the two dW tensors in its input
+    buffer during the pass; (b) a weight that reaches ConvFn as the output of a torch op (w * mask, mask of ones): the dW goes to
+    MulBackward during the pass.  Both read unreduced memory unless autograd.backward steps aside (`_leaves_take_by_stealing`
+    False), in which case every gradient is bit-equal to a plain loss.backward() of the same graph -- and within test_conv_backward's
+    bars (test_gpu_backward.py: 3e-6 of the largest entry) of CPU autograd through F.conv2d.  The unmodified Compressor step still
+    defers."""
+    import torch.nn.functional as F
+    from mcquic_amd import Compressor, ops
+    from mcquic_amd.nn import Conv2d
+    from mcquic_amd.autograd import ConvFn, backward, mse_loss, _leaves_take_by_stealing
+    g = torch.Generator().manual_seed(5)
+    n, c, h, w = 2, 32, 16, 24                                      # (the row-walk weight-gradient kernel's domain: its reduce pass is deferrable)
+    x = (torch.rand((n, c, h, w), generator=g) * 2 - 1)
+    target = (torch.rand((n, c, h, w), generator=g) * 2 - 1)
+    assert ops._lib.load().mcq_conv2d_wgrad_nchw_workspace_floats(n, c, h, w, c) > 0 and ops._WGRAD_DEFER
+
+    def close(got, want, what):
+        err, ref = float((got.detach().cpu() - want).abs().max()), max(float(want.abs().max()), 1e-3)
+        assert torch.isfinite(got).all() and err <= 3e-6 * ref, f"{what}: max abs err {err:.3e} (ref max {ref:.3e})"
+
+    def run(build_loss, params, how):
+        for p in params:
+            p.grad = None
+        loss = build_loss()
+        steals = _leaves_take_by_stealing([loss])
+        if how == "plain":
+            loss.backward()
+        else:
+            backward(loss)
+        assert ops._lib.load().mcq_wgrad_pending() == 0 and not ops._defer["keep"]
+        torch.cuda.synchronize()
+        return steals, [p.grad.clone() for p in params]
+
+    # (a) tied weights
+    torch.manual_seed(11)
+    c1, c2 = Conv2d(c, c, 3).to(dev).train(), Conv2d(c, c, 3).to(dev).train()
+    c2.weight = c1.weight
+    params = [c1.weight, c1.bias, c2.bias]
+    xd, td = x.to(dev), target.to(dev)
+    loss_a = lambda: mse_loss(c2(c1(xd)), td)                                                                  # noqa: E731
+    steals, plain = run(loss_a, params, "plain")
+    assert steals is False
+    _, ours = run(loss_a, params, "ours")
+    for name, a, b in zip(("weight", "bias 1", "bias 2"), ours, plain):
+        assert torch.equal(a, b), f"(a) {name}: autograd.backward differs from loss.backward()"
+    wr, b1r, b2r = (p.detach().cpu().double().requires_grad_() for p in params)
+    F.mse_loss(F.conv2d(F.conv2d(x.double(), wr, b1r, padding=1), wr, b2r, padding=1), target.double()).backward()
+    for name, a, r in zip(("weight", "bias 1", "bias 2"), ours, (wr, b1r, b2r)):
+        close(a, r.grad.float(), f"(a) {name}")
+
+    # (b) a derived weight: ConvFn.apply directly (Conv2d.forward packs the module's own parameter: with a mask of ones the
+    #     forward value is the module's, and d w = dW * mask)
+    torch.manual_seed(12)
+    cv = Conv2d(c, c, 3).to(dev).train()
+    mask = torch.ones_like(cv.weight)
+    params = [cv.weight, cv.bias]
+    loss_b = lambda: mse_loss(ConvFn.apply(xd, cv.weight * mask, cv.bias, None, cv, False, False)[0], td)     # noqa: E731
+    steals, plain = run(loss_b, params, "plain")
+    assert steals is False
+    _, ours = run(loss_b, params, "ours")
+    for name, a, b in zip(("weight", "bias"), ours, plain):
+        assert torch.equal(a, b), f"(b) {name}: autograd.backward differs from loss.backward()"
+    wr, br = (p.detach().cpu().double().requires_grad_() for p in params)
+    F.mse_loss(F.conv2d(x.double(), wr * mask.cpu().double(), br, padding=1), target.double()).backward()
+    for name, a, r in zip(("weight", "bias"), ours, (wr, br)):
+        close(a, r.grad.float(), f"(b) {name}")
+    # the same layer with nothing in front of its weight defers, and gives the same gradients
+    steals, direct = run(lambda: mse_loss(cv(xd), td), params, "ours")
+    assert steals is True
+    for a, b in zip(direct, plain):
+        assert torch.equal(a, b)
+
+    # the unmodified Compressor step still defers
+    torch.manual_seed(3407)
+    model = Compressor(32, 2, [64, 32, 16]).to(dev).train()
+    xs = (torch.rand((4, 3, 128, 128), generator=torch.Generator().manual_seed(0)) * 2 - 1).to(dev)
+    assert _leaves_take_by_stealing([mse_loss(model(xs)[0], xs)])
+
+
 def test_generator_state_round_trip(dev):
     """ops.get_rng_state / set_rng_state: a run resumed from the saved state draws what the uninterrupted run drew."""
     from mcquic_amd import ops
