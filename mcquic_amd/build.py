@@ -1,10 +1,11 @@
 """Build recipe for libmcquic_hip.so (gfx950 only, hipcc; no cmake, no JIT cache -- the .so lives in-tree).
 
-Every source is compiled to its own object (in parallel, only when it or a header changed) and the objects are linked
+Every source is compiled to its own object (in parallel, only when it or a file it includes changed: hipcc's depfiles) and the objects are linked
 into mcquic_amd/libmcquic_hip.so.  Objects live in mcquic_amd/_obj/ (git-ignored)."""
 from __future__ import annotations
 
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -14,8 +15,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "libmcquic_hip.so")
-SOURCES = ["conv_mfma.hip", "conv_wino16.hip", "vq.hip", "vq_train.hip", "vq_bwd_mfma.hip", "train_ops.hip", "step_ops.hip", "wgrad_rows.hip", "metrics.hip", "msssim_loss.hip", "norm.hip", "rans.cpp"]
-HEADERS = ["mcq_common.h", "vq_common.h", "conv_head16.h", "conv_t16.h", "conv_wino16.h", "vq_bwd_mfma.h", "wgrad_t16.h", os.path.join("..", "..", "include", "mcquic_hip.h")]
+# conv_mfma_kernel's instances are spread over conv_tiles_*.hip / conv_wino32.hip (build section, has their compile
+# times); conv_launch.hip and conv_pack.hip hold none, so an edit to the launcher or the pack layout rebuilds in seconds.
+SOURCES = ["conv_tiles_128.hip", "conv_wino32.hip", "conv_tiles_41.hip", "conv_tiles_32.hip", "conv_tiles_64.hip", "conv_launch.hip",
+           "conv_pack.hip", "conv_wino16.hip", "vq.hip", "vq_train.hip", "vq_bwd_mfma.hip", "train_ops.hip", "step_ops.hip",
+           "wgrad_rows.hip", "metrics.hip", "msssim_loss.hip", "norm.hip", "rans.cpp"]
 # -ffp-contract=off: element-wise epilogues keep the reference's one-rounding-per-op sequence
 #   (e.g. a * sigmoid(b) then + x are two torch kernels in mcquic/nn/blocks.py:286-287).
 # -pragma-unroll-threshold: the 128-register epilogue must be fully unrolled or the accumulators spill to scratch.
@@ -24,42 +28,63 @@ CFLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-f
 LDFLAGS = ["--offload-arch=gfx950", "-shared", "-fPIC", "-pthread"]
 
 
+def _includes(path: str):
+    """The files `path` includes with quotes (its own headers), resolved against its directory."""
+    here = os.path.dirname(path)
+    found = re.findall(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', open(path).read(), re.M)
+    return [os.path.normpath(os.path.join(here, f)) for f in found]
+
+
+def conv_files():
+    """Every file that holds convolution device code: the conv_* sources and, transitively, the headers they include."""
+    todo = [os.path.join(CSRC, s) for s in SOURCES if s.startswith("conv_")]
+    seen = set()
+    while todo:
+        f = todo.pop()
+        if f not in seen:
+            seen.add(f)
+            todo += _includes(f)
+    return sorted(seen)
+
+
 def csrc_sha() -> str:
-    """SHA-256 over the sources of the dominant kernel (csrc/conv_mfma.hip and the headers it includes, names + contents): what
-    measurement artefacts about that kernel are stamped with (profiles/rNN_pmc.json) so that a number collected on an older
-    kernel can be recognised as stale."""
+    """SHA-256 over conv_files() (names + contents): what measurement artefacts about the convolution kernels are stamped with
+    (profiles/rNN_pmc.json) so that a number collected on an older kernel can be recognised as stale."""
     import hashlib
     h = hashlib.sha256()
-    for f in ("conv_mfma.hip", "conv_head16.h", "conv_t16.h", "mcq_common.h", "conv_wino16.hip", "conv_wino16.h"):
-        h.update(f.encode() + b"\0")
-        h.update(open(os.path.join(CSRC, f), "rb").read())
+    for f in conv_files():
+        h.update(os.path.relpath(f, CSRC).replace(os.sep, "/").encode() + b"\0")
+        h.update(open(f, "rb").read())
     return h.hexdigest()
 
 
-def _headers():
-    hs = [os.path.join(CSRC, h) for h in HEADERS]
-    hs += [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h") and os.path.join(CSRC, f) not in hs]
-    return hs + [os.path.abspath(__file__)]
+def _obj_of(src: str, objdir: str = OBJ) -> str:
+    return os.path.join(objdir, os.path.splitext(src)[0] + ".o")
 
 
-def _obj_of(src: str) -> str:
-    return os.path.join(OBJ, os.path.splitext(src)[0] + ".o")
+def _deps(src: str):
+    """What the object of `src` was compiled from, as hipcc's depfile of that compilation recorded it (paths relative to csrc/).
+    Without that record (a tree that came with the library but without its objects): the source and every header."""
+    try:
+        text = open(_obj_of(src) + ".d").read()
+    except OSError:
+        return [os.path.join(CSRC, src), os.path.join(HERE, "..", "include", "mcquic_hip.h")] + \
+               [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")]
+    names = re.split(r"(?<!\\)\s+", text.replace("\\\n", " ").split(":", 1)[1].strip())       # (make syntax: a space inside a name is "\ ")
+    return [os.path.join(CSRC, d.replace("\\ ", " ")) for d in names]
+
+
+def _newer(deps, t: float) -> bool:
+    return any(not os.path.exists(d) or os.path.getmtime(d) > t for d in set(deps) | {os.path.abspath(__file__)})
 
 
 def _obj_stale(src: str) -> bool:
     o = _obj_of(src)
-    if not os.path.exists(o):
-        return True
-    t = os.path.getmtime(o)
-    return any(os.path.getmtime(d) > t for d in [os.path.join(CSRC, src)] + _headers())
+    return not (os.path.exists(o) and os.path.exists(o + ".d")) or _newer(_deps(src), os.path.getmtime(o))
 
 
 def _stale() -> bool:
-    if not os.path.exists(LIB):
-        return True
-    t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES] + _headers()
-    return any(os.path.getmtime(d) > t for d in deps)
+    return not os.path.exists(LIB) or _newer([d for s in SOURCES for d in _deps(s)], os.path.getmtime(LIB))
 
 
 def build(force: bool = False, verbose: bool = False, extra_flags=(), lib: str = LIB) -> str:
@@ -75,15 +100,15 @@ def build(force: bool = False, verbose: bool = False, extra_flags=(), lib: str =
     os.makedirs(objdir, exist_ok=True)
 
     def compile_one(src: str) -> str:
-        o = os.path.join(objdir, os.path.splitext(src)[0] + ".o")
+        o = _obj_of(src, objdir)
         if force or variant or _obj_stale(src):
-            cmd = [hipcc] + CFLAGS + list(extra_flags) + ["-c", os.path.join(CSRC, src), "-o", o]
+            cmd = [hipcc] + CFLAGS + list(extra_flags) + ["-MD", "-MF", o + ".d", "-c", src, "-o", o]      # (run in csrc/: the depfile names the project's files relative to it)
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.run(cmd, check=True, cwd=CSRC)
         return o
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1)) as pool:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 1, 16)) as pool:
         objs = list(pool.map(compile_one, SOURCES))
     cmd = [hipcc] + LDFLAGS + ["-o", lib + ".tmp"] + objs
     if verbose:

@@ -18,13 +18,11 @@
 // the k-steps of a tile over 2 / 4 / 8 waves of a workgroup (LDS reduction); the epilogue (bias, GDN / IGDN, gate,
 // residual, SiLU, SiLU twin, PixelShuffle store) runs on buffer instructions without predication.
 // Build switches below (all measured on MI355X): ring depths, XCD-aware tile order, tile rules.
-#include <mutex>
+#pragma once
 #include <type_traits>
-#include <unordered_map>
 
 #include "mcq_common.h"
 #include "../../include/mcquic_hip.h"
-#include "conv_wino16.h"
 
 // (The ablation / stamp / packed-SiLU / peel build switches of rounds 1-2 are gone from this file: what they measured is in
 //  DESIGN.md section 4, the code in the history up to commit 0aa82a9.)
@@ -58,7 +56,8 @@
 //  4 x 32 x 512x512 plain / SiLU / residual + twin against 181 / 189 / 230 here.  Source and test last in tree at bca81ee; counters:
 //  docs/experiments.md section 11.3)
 
-namespace {
+// (ConvPtrs / ConvK are the argument of the launch functions of conv_instances.h, which are defined in one file and called
+//  from another: they are the only names of this header outside the anonymous namespace)
 
 // tensors of one convolution; a launch can carry up to MCQ_CONV_MAX_MULTI independent convolutions of ONE geometry and flag
 // set (blockIdx.z picks the problem): the two stacks of an AttentionBlock run the same layer shapes side by side, and on the
@@ -88,6 +87,8 @@ struct ConvK {
     int post_sub;      // MCQ_CONV_POST_IGDN through the PixelShuffle store: the four waves of a workgroup are the four sub-pixel row tiles of ONE pixel tile
 };
 
+namespace {
+
 constexpr int PRO_NONE = 0, PRO_SILU = 1, PRO_SQUARE = 2;
 // 128-row Winograd instance: the epilogue flag set instance `id` (the kernel's PRO slot) is compiled for; 0 = any (run-time flags)
 constexpr unsigned wino_epilogue_flags(int id) {
@@ -95,13 +96,6 @@ constexpr unsigned wino_epilogue_flags(int id) {
          : id == 5 ? MCQ_CONV_DUAL_SILU : id == 6 ? (MCQ_CONV_RESIDUAL | MCQ_CONV_SILU_OUT) : 0xffffffffu;
 }
 constexpr unsigned RUNTIME_FLAGS = 0xffffffffu;    // epilogue instance that tests the flags at run time
-
-}  // namespace
-
-#include "conv_head16.h"
-#include "conv_t16.h"
-
-namespace {
 
 template <int MB> struct AVec;
 template <> struct AVec<4> { typedef f32x4v T; };
@@ -1238,934 +1232,4 @@ next_tile:
     }, kslice, std::integral_constant<int, 1>{});
 }
 
-// OIHW -> [Cout/(32 bands)][TP][64 lanes][bands]: lane l, slot q holds W[co = 32 bands T + 32 q + (l & 31)][ci = 2 s + (l >> 5)][tap]
-// for k-step = s * taps + tap (channel-major, tap-inner); zero beyond Cout / Cin and in the tail (MCQ_TAIL_STEPS).
-// up to MCQ_PACK_MAX_MULTI weights of one shape per launch (blockIdx.y picks the pair): after an optimizer step every conv of
-// the network re-packs its forward and its input-gradient operand stream -- 660 launches of ~4 us each, one by one
-// Which copy of its operand stream a launch reads, recorded per packed buffer while tracing is on (mcq_conv_section_trace): a
-// training step captured as a hipGraph replays the same launches forever, so its in-graph re-pack after the optimizer's update
-// only needs to refresh the copies those launches read (mcq_pack_conv_weight_multi_masked_f32) -- a quarter of the bytes.
-std::mutex g_sec_mu;
-bool g_sec_trace = false;
-std::unordered_map<const float*, unsigned> g_sec_used;
-inline void sec_note(const mcq_conv_desc* descs, int nprob, unsigned bit) {
-    if (!g_sec_trace) return;
-    std::lock_guard<std::mutex> lock(g_sec_mu);
-    for (int c = 0; c < nprob; ++c) g_sec_used[descs[c].w_packed] |= bit;
-}
-
-constexpr int PACK_MAX_MULTI = 64;       // (round 5: 16 -> 64; the qp=2 model's ~150 convolutions of one shape re-pack in 3 launches instead of 10)
-constexpr int MCQ_TAIL_STEPS = 32;       // (16 until ABI 8: the four-tap walk's weight ring runs 8 LIVE steps = up to 26 dense steps ahead)
-struct PackTable { const float* w[PACK_MAX_MULTI]; float* out[PACK_MAX_MULTI]; unsigned char mask[PACK_MAX_MULTI]; };
-// (mask: sections to write -- bit 0 the 128-row copy, 1 the 64-row, 2 the 32-row, 3 the 16x16-tile order; mcq_pack_conv_weight_multi_masked_f32)
-
-__device__ __forceinline__ void pack_conv_weight_body(const float* __restrict__ w, int Cout, int Cin, int ks, int S, int TP,
-                                                      float* __restrict__ out, size_t sec4, size_t sec2, size_t total, int mode, int Co, int Ci,
-                                                      float scale) {
-    // three copies back to back, `bands` = 32-row bands per tile (4 / 2 / 1 for the 128- / 64- / 32-row copies), each
-    // laid out [tile][step][lane][band] and followed by its zero tail
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const size_t at = i;
-    int bands = 4;
-    if (i >= sec4) { i -= sec4; bands = 2; if (i >= sec2) { i -= sec2; bands = 1; } }
-    const size_t sec1 = ((size_t)((Cout + 31) / 32) * TP + MCQ_TAIL_STEPS) * 64;
-    if (bands == 1 && i >= sec1) {
-        // fourth section (conv_t16.h): [Cout / 16][(Cin / 4) * 9 / 4][lane][4], k-step 4 g + u = 9 (channel quad) + tap
-        i -= sec1;
-        const int u = (int)(i & 3), lane = (int)((i >> 2) & 63);
-        const size_t gg = i >> 8;
-        const int G = (Cin / 4) * 9 / 4;
-        const int tile = (int)(gg / G), step = 4 * (int)(gg - (size_t)tile * G) + u;
-        const int co = 16 * tile + (lane & 15), ci = 4 * (step / 9) + (lane >> 4);
-        out[at] = pack_source(w, mode, Co, Ci, ks, co, ci, step % 9) * scale;
-        return;
-    }
-    const int ntile = (Cout + 32 * bands - 1) / (32 * bands);
-    const int q = (int)(i % bands);
-    const int lane = (int)((i / bands) & 63);
-    const size_t stepg = i / ((size_t)bands * 64);
-    const int tile = (int)(stepg / TP);
-    const int step = (int)(stepg - (size_t)tile * TP);
-    float v = 0.0f;
-    const int taps = mode == 5 ? 16 : mode >= 3 ? 12 : ks * ks;
-    if (tile < ntile && step < TP) {
-        const int s = step / taps, tap = step - s * taps;
-        const int co = tile * 32 * bands + 32 * q + (lane & 31);
-        const int ci = 2 * s + (lane >> 5);
-        if (co < Cout && ci < Cin) {
-            if (mode == 5) {
-                // F(2x2, 3x3): tap = 4 i + j, U = G g G^T in float64, rounded once
-                const double G[4][3] = {{1.0, 0.0, 0.0}, {0.5, 0.5, 0.5}, {0.5, -0.5, 0.5}, {0.0, 0.0, 1.0}};
-                const int pi = tap >> 2, pj = tap & 3;
-                double u = 0.0;
-                for (int a = 0; a < 3; ++a)
-                    for (int b = 0; b < 3; ++b) u += G[pi][a] * (double)pack_source(w, 0, Co, Ci, 3, co, ci, 3 * a + b) * G[pj][b];
-                v = (float)u;
-            } else if (mode >= 3) {
-                // Winograd F(2, 3) along x: tap = 4 dy + position; G = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]];
-                // mode 3 from the layer's own filter rows, mode 4 from those of its stride-1 input-gradient convolution
-                const int row = 3 * (tap >> 2), src = mode == 3 ? 0 : 1;
-                const double g0 = pack_source(w, src, Co, Ci, 3, co, ci, row), g1 = pack_source(w, src, Co, Ci, 3, co, ci, row + 1),
-                             g2 = pack_source(w, src, Co, Ci, 3, co, ci, row + 2);
-                const int pos = tap & 3;
-                v = (float)(pos == 0 ? g0 : pos == 1 ? 0.5 * (g0 + g1 + g2) : pos == 2 ? 0.5 * (g0 - g1 + g2) : g2);
-            } else
-                v = pack_source(w, mode, Co, Ci, ks, co, ci, tap) * scale;
-        }
-    }
-    out[at] = v;
-}
-
-__global__ void pack_conv_weight_kernel(const float* __restrict__ w, int Cout, int Cin, int ks, int S, int TP,
-                                        float* __restrict__ out, size_t sec4, size_t sec2, size_t total, int mode, int Co, int Ci,
-                                        float scale) {
-    pack_conv_weight_body(w, Cout, Cin, ks, S, TP, out, sec4, sec2, total, mode, Co, Ci, scale);
-}
-
-__global__ void pack_conv_weight_multi_kernel(PackTable t, int Cout, int Cin, int ks, int S, int TP, size_t sec4, size_t sec2, size_t total,
-                                              int mode, int Co, int Ci, float scale) {
-    // (a uniform dynamic index into the by-value table: scalar loads from the kernel-argument segment -- a compare chain over 64
-    //  entries cost every thread ~190 vector instructions)
-    const int c = (int)blockIdx.y;
-    const float* w = t.w[c];
-    float* out = t.out[c];
-    pack_conv_weight_body(w, Cout, Cin, ks, S, TP, out, sec4, sec2, total, mode, Co, Ci, scale);
-}
-
-// The same four sections for a 3x3 weight with one thread per (output channel, input channel) run: the nine taps of a pair are
-// 36 consecutive bytes of the OIHW tensor in every mode (forward, flipped / transposed, sub-pixel), so a thread reads its run
-// once and leaves nine values 64 x bands floats apart -- a wave's store is still 256 consecutive bytes.  The element-per-thread
-// kernel above fetched a 128-byte line for every float it wrote (a wave's 64 lanes = 64 different rows of the weight): with an
-// optimizer step inside the training step every conv re-packs both its operand streams, and those ~45 grouped launches were
-// 1.6 ms of a 24 ms step; this form does the same in a quarter of the time.  Same bits in the same places.
-__device__ __forceinline__ void pack_conv_weight_runs_body(const float* __restrict__ w, int Cout, int Cin, int S, int TP,
-                                                           float* __restrict__ out, int mode, int Co, int Ci, float scale, unsigned n16,
-                                                           unsigned mask) {
-    // (32-bit index arithmetic throughout: a packed weight is far below 2^31 floats -- the element-per-thread kernel's 64-bit
-    //  divisions were a good part of its time)
-    unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    unsigned base = 0;
-#pragma unroll
-    for (int b = 4; b >= 1; b >>= 1) {
-        const unsigned ntile = (unsigned)(Cout + 32 * b - 1) / (32u * b);
-        const unsigned main = ntile * (unsigned)S * 64u * b, tail = (unsigned)MCQ_TAIL_STEPS * 64u * b;
-        const bool wanted = (mask >> (b == 4 ? 0 : b == 2 ? 1 : 2)) & 1u;
-        if (i < main) {
-            if (!wanted) return;
-            const unsigned q = i % b, lane = (i / b) & 63u;
-            const unsigned sg = i / (64u * b);
-            const unsigned tile = sg / (unsigned)S, s = sg - tile * (unsigned)S;
-            const int co = (int)(tile * 32u * b + 32u * q + (lane & 31u)), ci = (int)(2u * s + (lane >> 5));
-            float v[9];
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) v[tap] = 0.0f;
-            if (co < Cout && ci < Cin) {
-#pragma unroll
-                for (int tap = 0; tap < 9; ++tap) v[tap] = pack_source(w, mode, Co, Ci, 3, co, ci, tap) * scale;
-            }
-            float* o = out + base + ((tile * (unsigned)TP + s * 9u) * 64u + lane) * b + q;
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) o[(unsigned)tap * 64u * b] = v[tap];
-            return;
-        }
-        i -= main;
-        if (i < tail) { if (wanted) out[base + ntile * (unsigned)TP * 64u * b + i] = 0.0f; return; }
-        i -= tail;
-        base += (ntile * (unsigned)TP + MCQ_TAIL_STEPS) * 64u * b;
-    }
-    if (i < n16 && (mask & 8u)) {             // fourth section (conv_t16.h): one 16-byte store = four consecutive k-steps of a lane
-        const unsigned lane = i & 63u, gg = i >> 6;
-        const unsigned G = (unsigned)(Cin / 4) * 9u / 4u;
-        const unsigned tile = gg / G, g = gg - tile * G;
-        const int co = (int)(16u * tile + (lane & 15u));
-        f32x4v v;
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const unsigned step = 4u * g + (unsigned)u;
-            v[u] = pack_source(w, mode, Co, Ci, 3, co, (int)(4u * (step / 9u) + (lane >> 4)), (int)(step % 9u)) * scale;
-        }
-        *reinterpret_cast<f32x4v*>(out + base + i * 4u) = v;
-    }
-}
-
-__global__ void pack_conv_weight_runs_kernel(const float* __restrict__ w, int Cout, int Cin, int S, int TP, float* __restrict__ out,
-                                             int mode, int Co, int Ci, float scale, unsigned n16) {
-    pack_conv_weight_runs_body(w, Cout, Cin, S, TP, out, mode, Co, Ci, scale, n16, 15u);
-}
-
-__global__ void pack_conv_weight_runs_multi_kernel(PackTable t, int Cout, int Cin, int S, int TP, int mode, int Co, int Ci, float scale, unsigned n16) {
-    const int c = (int)blockIdx.y;
-    const float* w = t.w[c];
-    float* out = t.out[c];
-    const unsigned mask = t.mask[c];
-    pack_conv_weight_runs_body(w, Cout, Cin, S, TP, out, mode, Co, Ci, scale, n16, mask);
-}
-
-__global__ void nonneg_reparam_kernel(const float* __restrict__ p, float bound, float pedestal, float* __restrict__ out,
-                                      int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) {
-        const float v = fmaxf(p[i], bound);
-        out[i] = v * v - pedestal;
-    }
-}
-
-// several parameters in one launch (the beta [C] and gamma [C, C] of every GDN layer after an optimizer step: 20 launches -> 1)
-constexpr int REPARAM_MAX_MULTI = 64;
-struct ReparamTable { const float* p[REPARAM_MAX_MULTI]; float* out[REPARAM_MAX_MULTI]; long long n[REPARAM_MAX_MULTI]; float bound[REPARAM_MAX_MULTI];
-                      float pedestal[REPARAM_MAX_MULTI]; };
-__global__ void nonneg_reparam_multi_kernel(ReparamTable t) {
-    const int c = (int)blockIdx.y;                              // (uniform index into the kernel-argument table)
-    const float* p = t.p[c]; float* out = t.out[c]; const long long n = t.n[c]; const float bound = t.bound[c], pedestal = t.pedestal[c];
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-        const float v = fmaxf(p[i], bound);
-        out[i] = v * v - pedestal;
-    }
-}
-
-inline int pairs_padded(int Cin, int ks) {        // 1x1 loops advance a whole prefetch ring (<= 16 pairs) at a time
-    const int S = (Cin + 1) / 2;
-    return ks == 1 ? (S + 15) & ~15 : S;
-}
-inline int steps_padded(int Cin, int ks) { return pairs_padded(Cin, ks) * ks * ks; }
-// The operand stream of conv_mfma_kernel exists once per tile height: 128-, 64- and 32-row copies, each with its own
-// zero steps for the prefetch tail (MCQ_TAIL_STEPS: the deepest weight ring of any instance); layers conv_t16.h can take carry a
-// fourth section in its order.
-inline size_t section_floats(int Cout, int Cin, int ks, int bands) {
-    const size_t ntile = (size_t)(Cout + 32 * bands - 1) / (32 * bands);
-    return (ntile * (size_t)steps_padded(Cin, ks) + MCQ_TAIL_STEPS) * 64 * bands;
-}
-// threads of pack_conv_weight_runs_kernel: one per (channel pair run, lane, band), per zero of a tail, per 16 bytes of the fourth section
-inline size_t pack_runs_threads(int Cout, int Cin) {
-    size_t t = 0;
-    for (int b = 4; b >= 1; b >>= 1) t += ((size_t)(Cout + 32 * b - 1) / (32 * b) * (size_t)pairs_padded(Cin, 3) + MCQ_TAIL_STEPS) * 64 * b;
-    return t + t16_floats(Cout, Cin, 3) / 4;
-}
-
-inline size_t general_floats(int Cout, int Cin, int ks) {
-    return section_floats(Cout, Cin, ks, 4) + section_floats(Cout, Cin, ks, 2) + section_floats(Cout, Cin, ks, 1) + t16_floats(Cout, Cin, ks);
-}
-
-template <int MB, int NB, int PF3A, int PF3B, int PF1>
-int launch_tile(ConvK k, int pro, long long tiles, int co_tiles, int ksplit_log2, hipStream_t s, bool pair = false, bool lr4 = false, int post = 0) {
-    // split-K: one 32-row band per owner wave (KS >= MB), whole channel pairs per slice, slices of >= 8 pairs of a
-    // 3x3 conv (1x1 convs, 64 steps in all, are never split)
-    if (ksplit_log2 > 0 && (1 << ksplit_log2) < MB) ksplit_log2 = MB == 4 ? 2 : 1;
-    if (k.ks == 1) ksplit_log2 = 0;
-    while (ksplit_log2 > 0 && (k.S % (1 << ksplit_log2) != 0 || (k.S >> ksplit_log2) < 8)) --ksplit_log2;
-    if ((1 << ksplit_log2) < MB) ksplit_log2 = 0;
-    constexpr int OCC = (MB == 2 && NB == 2) ? 3 : 2;      // waves per SIMD the register budget is sized for
-    k.ks_log2 = ksplit_log2;
-    k.slice_pairs = k.S >> ksplit_log2;
-    k.tiles_log2 = ksplit_log2 >= 2 ? 0 : 2 - ksplit_log2;           // 4 waves per workgroup, 8 for 8-way split
-    const int waves = 1 << (k.ks_log2 + k.tiles_log2);
-    const size_t lds = ksplit_log2 ? (size_t)waves * NB * 1024 * sizeof(float) : 0;
-    const dim3 grid((unsigned)((tiles + (1 << k.tiles_log2) - 1) >> k.tiles_log2), (unsigned)co_tiles, (unsigned)k.nprob);
-    const dim3 block(64 * waves);
-    // (round 4, measured and removed: `s_setprio 2` for the first-dispatched workgroup of every CU in single-round launches, so that
-    //  one of the two waves of a SIMD finishes its k-loop early and its epilogue runs under the other's MFMAs -- the captured
-    //  training step 22.32 vs 22.34 ms, the 32-image step 123.3 vs 123.4 ms: two epilogues side by side cost what one does)
-    if (post) {             // the following 1x1 layer inside the launch (MCQ_CONV_POST_*): unsplit 128-row tiles only
-        if constexpr (MB == 4 && NB == 1) {
-            if (ksplit_log2 != 0 || k.ks != 3 || pair || lr4 || k.nprob != 1 || (pro != PRO_NONE && pro != PRO_SILU)) return MCQ_EINVAL;
-            dim3 pgrid = grid, pblock = block;
-            if (k.post_sub) { k.tiles_log2 = 0; pgrid = dim3((unsigned)tiles, 1u, 1u); pblock = dim3(256); }   // one pixel tile per workgroup, its four waves = the four row tiles
-            if (post == 1 && pro == PRO_NONE) hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_NONE, PF3A, PF3B, 9, OCC, false, 1>), pgrid, pblock, 0, s, k);
-            else if (post == 1) hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_SILU, PF3A, PF3B, 9, OCC, false, 1>), pgrid, pblock, 0, s, k);
-            else if (pro == PRO_NONE) hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_NONE, PF3A, PF3B, 9, OCC, false, 2>), pgrid, pblock, 0, s, k);
-            else hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_SILU, PF3A, PF3B, 9, OCC, false, 2>), pgrid, pblock, 0, s, k);
-            return mcq_check_launch();
-        }
-        return MCQ_EINVAL;
-    }
-    if (pair) {
-        if constexpr (MB == 4 && NB == 2) {
-            if (ksplit_log2 != 0 || pro != PRO_NONE || k.ks != 3) return MCQ_EINVAL;
-            hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_NONE, PF3A, PF3B, 9, OCC, true>), grid, block, lds, s, k);
-            return mcq_check_launch();
-        }
-        return MCQ_EINVAL;
-    }
-    if (lr4) {              // (the rings in live steps: weights 8 ahead, activations 16 = four channel pairs)
-        if (pro != PRO_NONE || k.ks != 3) return MCQ_EINVAL;
-        hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_NONE, 8, 16, 4, OCC>), grid, block, lds, s, k);
-        return mcq_check_launch();
-    }
-    if (k.ks == 3) {
-        if (pro == PRO_SILU) hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_SILU, PF3A, PF3B, 9, OCC>), grid, block, lds, s, k);
-        else if (pro == PRO_NONE) hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_NONE, PF3A, PF3B, 9, OCC>), grid, block, lds, s, k);
-        else return MCQ_EINVAL;
-    } else {
-        if (pro == PRO_SQUARE) hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_SQUARE, PF1, PF1, 1, OCC>), grid, block, lds, s, k);
-        else if (pro == PRO_NONE) hipLaunchKernelGGL((conv_mfma_kernel<MB, NB, PRO_NONE, PF1, PF1, 1, OCC>), grid, block, lds, s, k);
-        else return MCQ_EINVAL;
-    }
-    return mcq_check_launch();
-}
-
-inline size_t wino_section_floats(int Cout, int Cin, int bands) {
-    const size_t ntile = (size_t)(Cout + 32 * bands - 1) / (32 * bands);
-    return (ntile * (size_t)((Cin + 1) / 2) * 12 + 16) * 64 * bands;
-}
-
-// Winograd F(2, 3) launches: one pair block (32 pairs of pixels) per wave, four waves per workgroup, no split-K
-template <int MB>
-int launch_wino(ConvK k, long long tiles, int co_tiles, hipStream_t s) {
-    constexpr int OCC = MB == 4 ? 1 : 2;                   // 4 x MB accumulator tiles: 256 registers at MB = 4
-    k.ks_log2 = 0;
-    k.slice_pairs = k.S;
-    k.tiles_log2 = 2;
-    k.total_wgs = (int)((tiles + 3) >> 2);
-    // MB = 4: one workgroup per CU is all that fits, so 256 * MCQ_WINO_PERSIST of them walk the tiles (a multiple of 8 keeps a
-    // workgroup on one XCD's eighth of the image); MB = 2 launches a workgroup per four tiles as usual
-    const unsigned gx = MB == 4 && MCQ_WINO_PERSIST > 0 && k.total_wgs > 256 * MCQ_WINO_PERSIST ? 256u * MCQ_WINO_PERSIST : (unsigned)k.total_wgs;
-    const dim3 grid(gx, (unsigned)co_tiles, (unsigned)k.nprob);
-    // activations run ~2.6 us ahead of their MFMAs (a step is MB MFMAs of 64 cycles): 24 steps at MB = 4, 48 at MB = 2
-    if constexpr (MB == 4) {
-        const unsigned ef = k.flags & ~(unsigned)(MCQ_CONV_SILU_IN | MCQ_CONV_SQUARE_IN);
-        int id = 0;
-        for (int c = 1; c <= 6; ++c) if (ef == wino_epilogue_flags(c)) id = c;
-        switch (id) {
-            case 1: hipLaunchKernelGGL((conv_mfma_kernel<4, 2, 1, 12, 24, 12, OCC>), grid, dim3(256), 0, s, k); break;
-            case 2: hipLaunchKernelGGL((conv_mfma_kernel<4, 2, 2, 12, 24, 12, OCC>), grid, dim3(256), 0, s, k); break;
-            case 3: hipLaunchKernelGGL((conv_mfma_kernel<4, 2, 3, 12, 24, 12, OCC>), grid, dim3(256), 0, s, k); break;
-            case 4: hipLaunchKernelGGL((conv_mfma_kernel<4, 2, 4, 12, 24, 12, OCC>), grid, dim3(256), 0, s, k); break;
-            case 5: hipLaunchKernelGGL((conv_mfma_kernel<4, 2, 5, 12, 24, 12, OCC>), grid, dim3(256), 0, s, k); break;
-            case 6: hipLaunchKernelGGL((conv_mfma_kernel<4, 2, 6, 12, 24, 12, OCC>), grid, dim3(256), 0, s, k); break;
-            default: hipLaunchKernelGGL((conv_mfma_kernel<4, 2, 0, 12, 24, 12, OCC>), grid, dim3(256), 0, s, k); break;
-        }
-    } else
-        hipLaunchKernelGGL((conv_mfma_kernel<MB, 2, PRO_NONE, 12, MCQ_WINO_PFB2, 12, OCC>), grid, dim3(256), 0, s, k);
-    return mcq_check_launch();
-}
-
-// F(2x2, 3x3) launches: one block of 32 tiles (2 x 2 pixels each) per workgroup, its four waves = four 32-row bands
-int launch_wino2d(ConvK k, long long tiles, int co_groups, hipStream_t s) {
-    k.ks_log2 = 0;
-    k.slice_pairs = k.S;
-    k.tiles_log2 = 0;
-    k.total_wgs = (int)tiles;
-    const unsigned gx = MCQ_WINO_PERSIST > 0 && k.total_wgs > 256 * MCQ_WINO_PERSIST ? 256u * MCQ_WINO_PERSIST : (unsigned)k.total_wgs;
-    const dim3 grid(gx, (unsigned)co_groups, (unsigned)k.nprob);
-    const unsigned ef = k.flags & ~(unsigned)(MCQ_CONV_SILU_IN | MCQ_CONV_SQUARE_IN);
-    int id = 0;
-    for (int c = 1; c <= 6; ++c) if (ef == wino_epilogue_flags(c)) id = c;
-    switch (id) {
-        case 1: hipLaunchKernelGGL((conv_mfma_kernel<1, 4, 1, 16, 32, 16, 1>), grid, dim3(256), 8192, s, k); break;
-        case 2: hipLaunchKernelGGL((conv_mfma_kernel<1, 4, 2, 16, 32, 16, 1>), grid, dim3(256), 8192, s, k); break;
-        case 3: hipLaunchKernelGGL((conv_mfma_kernel<1, 4, 3, 16, 32, 16, 1>), grid, dim3(256), 8192, s, k); break;
-        case 4: hipLaunchKernelGGL((conv_mfma_kernel<1, 4, 4, 16, 32, 16, 1>), grid, dim3(256), 8192, s, k); break;
-        case 5: hipLaunchKernelGGL((conv_mfma_kernel<1, 4, 5, 16, 32, 16, 1>), grid, dim3(256), 8192, s, k); break;
-        case 6: hipLaunchKernelGGL((conv_mfma_kernel<1, 4, 6, 16, 32, 16, 1>), grid, dim3(256), 8192, s, k); break;
-        default: hipLaunchKernelGGL((conv_mfma_kernel<1, 4, 0, 16, 32, 16, 1>), grid, dim3(256), 8192, s, k); break;
-    }
-    return mcq_check_launch();
-}
-
-inline size_t wino2d_floats(int Cout, int Cin) {           // [Cout/32][Cin/2 x 16 (+ 16 tail)][64 lanes]
-    return (((size_t)(Cout + 31) / 32) * (size_t)((Cin + 1) / 2) * 16 + 16) * 64;
-}
-
-bool wino_shape(int Cout, int ksize, int stride, unsigned fl) {
-    return ksize == 3 && stride == 1 && Cout % 64 == 0 && !(fl & (MCQ_CONV_SILU_IN | MCQ_CONV_SQUARE_IN));
-}
-
 }  // namespace
-
-extern "C" size_t mcq_packed_conv_winograd_floats(int32_t Cout, int32_t Cin) {
-    if (Cout <= 0 || Cin <= 0) return 0;
-    return wino_section_floats(Cout, Cin, 4) + wino_section_floats(Cout, Cin, 2);
-}
-
-extern "C" int mcq_pack_conv_weight_winograd_f32(const float* w, int32_t Cout, int32_t Cin, float* out, void* stream) {
-    if (!w || !out || Cout <= 0 || Cin <= 0) return MCQ_EINVAL;
-    const size_t sec4 = wino_section_floats(Cout, Cin, 4), sec2 = wino_section_floats(Cout, Cin, 2), total = sec4 + sec2;
-    const int S = (Cin + 1) / 2, TP = S * 12;
-    hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin,
-                       3, S, TP, out, sec4, sec2, total, 3, Cout, Cin, 1.0f);
-    return mcq_check_launch();
-}
-
-// the same for the layer's stride-1 INPUT-GRADIENT convolution (a [Cin, Cout, 3, 3] conv on flipped / transposed taps): `out`
-// holds mcq_packed_conv_winograd_floats(Cin, Cout) floats
-extern "C" int mcq_pack_conv_dgrad_weight_winograd_f32(const float* w, int32_t Cout, int32_t Cin, float* out, void* stream) {
-    if (!w || !out || Cout <= 0 || Cin <= 0) return MCQ_EINVAL;
-    const int co_d = Cin, ci_d = Cout;
-    const size_t sec4 = wino_section_floats(co_d, ci_d, 4), sec2 = wino_section_floats(co_d, ci_d, 2), total = sec4 + sec2;
-    const int S = (ci_d + 1) / 2, TP = S * 12;
-    hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, co_d, ci_d,
-                       3, S, TP, out, sec4, sec2, total, 4, Cout, Cin, 1.0f);
-    return mcq_check_launch();
-}
-
-extern "C" size_t mcq_packed_conv_winograd2d_floats(int32_t Cout, int32_t Cin) {
-    return Cout <= 0 || Cin <= 0 ? 0 : wino2d_floats(Cout, Cin);
-}
-
-extern "C" int mcq_pack_conv_weight_winograd2d_f32(const float* w, int32_t Cout, int32_t Cin, float* out, void* stream) {
-    if (!w || !out || Cout <= 0 || Cin <= 0) return MCQ_EINVAL;
-    const size_t total = wino2d_floats(Cout, Cin);
-    const int S = (Cin + 1) / 2, TP = S * 16;
-    hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin,
-                       3, S, TP, out, (size_t)0, (size_t)0, total, 5, Cout, Cin, 1.0f);
-    return mcq_check_launch();
-}
-
-extern "C" int32_t mcq_conv2d_winograd_ok(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t ksize, int32_t stride,
-                                          uint32_t flags) {
-    return (N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && wino_shape(Cout, ksize, stride, flags)) ? 1 : 0;
-}
-
-extern "C" size_t mcq_packed_conv_weight_floats(int32_t Cout, int32_t Cin, int32_t ksize) {
-    if (Cout <= 0 || Cin <= 0 || (ksize != 1 && ksize != 3)) return 0;
-    return general_floats(Cout, Cin, ksize) + (head16_shape(Cout, ksize) ? head16_floats(Cin) : 0);
-}
-
-extern "C" int mcq_pack_conv_weight_f32(const float* w, int32_t Cout, int32_t Cin, int32_t ksize, float* out,
-                                        void* stream) {
-    if (!w || !out || Cout <= 0 || Cin <= 0 || (ksize != 1 && ksize != 3)) return MCQ_EINVAL;
-    const size_t total = general_floats(Cout, Cin, ksize);
-    const int S = pairs_padded(Cin, ksize), TP = steps_padded(Cin, ksize);
-    if (ksize == 3 && total < (1ull << 31))
-        hipLaunchKernelGGL(pack_conv_weight_runs_kernel, dim3((unsigned)((pack_runs_threads(Cout, Cin) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           w, Cout, Cin, S, TP, out, 0, Cout, Cin, 1.0f, (unsigned)(t16_floats(Cout, Cin, 3) / 4));
-    else
-        hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin,
-                           ksize, S, TP, out, section_floats(Cout, Cin, ksize, 4), section_floats(Cout, Cin, ksize, 2), total, 0, Cout, Cin, 1.0f);
-    if (head16_shape(Cout, ksize)) {      // second copy in the 16-row operand order of conv_head16_kernel
-        const size_t t16 = head16_floats(Cin);
-        hipLaunchKernelGGL(pack_head16_kernel, dim3((unsigned)((t16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, Cout, Cin,
-                           (Cin + 3) / 4, out + total, t16, 0, Cout, Cin, 1.0f);
-    }
-    return mcq_check_launch();
-}
-
-extern "C" int mcq_dgrad_weight_shape(int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, int32_t* Cout_d, int32_t* Cin_d) {
-    if (Cout <= 0 || Cin <= 0 || !Cout_d || !Cin_d) return MCQ_EINVAL;
-    if (stride == 1 && (ksize == 1 || ksize == 3)) { *Cout_d = Cin; *Cin_d = Cout; return MCQ_OK; }
-    if (stride == 2 && ksize == 3) { *Cout_d = 4 * Cin; *Cin_d = Cout; return MCQ_OK; }
-    return MCQ_EINVAL;
-}
-
-extern "C" int mcq_pack_conv_dgrad_weight_f32(const float* w, int32_t Cout, int32_t Cin, int32_t ksize, int32_t stride, float scale,
-                                              float* out, void* stream) {
-    int32_t co_d = 0, ci_d = 0;
-    if (!w || !out || mcq_dgrad_weight_shape(Cout, Cin, ksize, stride, &co_d, &ci_d) != MCQ_OK) return MCQ_EINVAL;
-    // same layout and size as a forward pack of a [co_d, ci_d, ks, ks] weight: mcq_packed_conv_weight_floats(co_d, ci_d, ks)
-    const size_t total = general_floats(co_d, ci_d, ksize);
-    const int S = pairs_padded(ci_d, ksize), TP = steps_padded(ci_d, ksize);
-    if (ksize == 3 && total < (1ull << 31))
-        hipLaunchKernelGGL(pack_conv_weight_runs_kernel, dim3((unsigned)((pack_runs_threads(co_d, ci_d) + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                           w, co_d, ci_d, S, TP, out, stride == 1 ? 1 : 2, Cout, Cin, scale, (unsigned)(t16_floats(co_d, ci_d, 3) / 4));
-    else
-        hipLaunchKernelGGL(pack_conv_weight_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, co_d, ci_d,
-                           ksize, S, TP, out, section_floats(co_d, ci_d, ksize, 4), section_floats(co_d, ci_d, ksize, 2), total,
-                           stride == 1 ? 1 : 2, Cout, Cin, scale);
-    if (head16_shape(co_d, ksize)) {      // narrow input gradients (the 8-channel fixture models) take the 16-row kernel
-        const size_t t16 = head16_floats(ci_d);
-        hipLaunchKernelGGL(pack_head16_kernel, dim3((unsigned)((t16 + 255) / 256)), dim3(256), 0, (hipStream_t)stream, w, co_d, ci_d,
-                           (ci_d + 3) / 4, out + total, t16, stride == 1 ? 1 : 2, Cout, Cin, scale);
-    }
-    return mcq_check_launch();
-}
-
-extern "C" int32_t mcq_pack_conv_weight_max_multi(void) { return PACK_MAX_MULTI; }
-
-extern "C" void mcq_conv_section_trace(int32_t on) {
-    std::lock_guard<std::mutex> lock(g_sec_mu);
-    if (on) g_sec_used.clear();
-    g_sec_trace = on != 0;
-}
-
-extern "C" uint32_t mcq_conv_sections_used(const float* packed) {
-    std::lock_guard<std::mutex> lock(g_sec_mu);
-    const auto it = g_sec_used.find(packed);
-    return it == g_sec_used.end() ? 0u : it->second;
-}
-
-namespace {
-int pack_multi(const float* const* w, float* const* out, const uint8_t* masks, int32_t n, int32_t Cout, int32_t Cin, int32_t ksize,
-               int32_t dgrad, int32_t stride, float scale, void* stream);
-}
-
-extern "C" int mcq_pack_conv_weight_multi_f32(const float* const* w, float* const* out, int32_t n, int32_t Cout, int32_t Cin, int32_t ksize,
-                                              int32_t dgrad, int32_t stride, float scale, void* stream) {
-    return pack_multi(w, out, nullptr, n, Cout, Cin, ksize, dgrad, stride, scale, stream);
-}
-
-extern "C" int mcq_pack_conv_weight_multi_masked_f32(const float* const* w, float* const* out, const uint8_t* masks, int32_t n, int32_t Cout,
-                                                     int32_t Cin, int32_t ksize, int32_t dgrad, int32_t stride, float scale, void* stream) {
-    return pack_multi(w, out, masks, n, Cout, Cin, ksize, dgrad, stride, scale, stream);
-}
-
-namespace {
-int pack_multi(const float* const* w, float* const* out, const uint8_t* masks, int32_t n, int32_t Cout, int32_t Cin, int32_t ksize,
-               int32_t dgrad, int32_t stride, float scale, void* stream) {
-    if (!w || !out || n < 1 || n > PACK_MAX_MULTI || Cout <= 0 || Cin <= 0 || (ksize != 1 && ksize != 3)) return MCQ_EINVAL;
-    int32_t co = Cout, ci = Cin;
-    int mode = 0;
-    if (dgrad) {
-        if (mcq_dgrad_weight_shape(Cout, Cin, ksize, stride, &co, &ci) != MCQ_OK) return MCQ_EINVAL;
-        mode = stride == 1 ? 1 : 2;
-    }
-    if (head16_shape(co, ksize)) return MCQ_EINVAL;          // (narrow layers carry a second copy: one by one)
-    PackTable t;
-    for (int c = 0; c < PACK_MAX_MULTI; ++c) {
-        const int k = c < n ? c : 0;
-        if (!w[k] || !out[k]) return MCQ_EINVAL;
-        t.w[c] = w[k]; t.out[c] = out[k];
-        t.mask[c] = (masks && (masks[k] & 15u)) ? (unsigned char)(masks[k] & 15u) : (unsigned char)15u;      // (0 = unknown = everything)
-    }
-    const size_t total = general_floats(co, ci, ksize);
-    const int S = pairs_padded(ci, ksize), TP = steps_padded(ci, ksize);
-    if (ksize == 3 && total < (1ull << 31))
-        hipLaunchKernelGGL(pack_conv_weight_runs_multi_kernel, dim3((unsigned)((pack_runs_threads(co, ci) + 255) / 256), (unsigned)n), dim3(256), 0,
-                           (hipStream_t)stream, t, co, ci, S, TP, mode, Cout, Cin, dgrad ? scale : 1.0f, (unsigned)(t16_floats(co, ci, 3) / 4));
-    else
-        hipLaunchKernelGGL(pack_conv_weight_multi_kernel, dim3((unsigned)((total + 255) / 256), (unsigned)n), dim3(256), 0, (hipStream_t)stream, t, co,
-                           ci, ksize, S, TP, section_floats(co, ci, ksize, 4), section_floats(co, ci, ksize, 2), total, mode, Cout, Cin,
-                           dgrad ? scale : 1.0f);
-    return mcq_check_launch();
-}
-}  // namespace
-
-extern "C" int32_t mcq_nonneg_reparam_max_multi(void) { return REPARAM_MAX_MULTI; }
-
-extern "C" int mcq_nonneg_reparam_multi_f32(const float* const* p, float* const* out, const int64_t* n, const float* bound, const float* pedestal,
-                                            int32_t count, void* stream) {
-    if (!p || !out || !n || !bound || !pedestal || count < 1 || count > REPARAM_MAX_MULTI) return MCQ_EINVAL;
-    ReparamTable t;
-    long long most = 0;
-    for (int c = 0; c < REPARAM_MAX_MULTI; ++c) {
-        const int k = c < count ? c : 0;
-        if (!p[k] || !out[k] || n[k] <= 0) return MCQ_EINVAL;
-        t.p[c] = p[k]; t.out[c] = out[k]; t.n[c] = n[k]; t.bound[c] = bound[k]; t.pedestal[c] = pedestal[k];
-        if (n[k] > most) most = n[k];
-    }
-    long long blocks = (most + 255) / 256;
-    if (blocks > 256) blocks = 256;                          // (grid-stride loop inside)
-    hipLaunchKernelGGL(nonneg_reparam_multi_kernel, dim3((unsigned)blocks, (unsigned)count), dim3(256), 0, (hipStream_t)stream, t);
-    return mcq_check_launch();
-}
-
-extern "C" int mcq_nonneg_reparam_f32(const float* p, float bound, float pedestal, float* out, int64_t n, void* stream) {
-    if (!p || !out || n <= 0) return MCQ_EINVAL;
-    hipLaunchKernelGGL(nonneg_reparam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p,
-                       bound, pedestal, out, n);
-    return mcq_check_launch();
-}
-
-namespace {
-
-// does mcq_conv2d_f32 take a MCQ_CONV_POST_* launch on its own (`row_tiles` 128-row tiles per pixel block)?  From two 128 x 32 wave tiles
-// per SIMD; below that the map's 3x3 layer is normally split over waves and the 1x1 layer stays a launch (unless the caller forces tile 0x41)
-inline bool post_fills_chip(long long tb, int row_tiles) { return tb * row_tiles >= 2048; }
-
-// [128, 128] 1x1 weight -> [POST_STEPS + POST_TAIL][64 lanes][4]: k-step t = 16 mb + r holds the channels 32 mb + drow(r) (+ 4 for the
-// upper half-wave) -- the order in which a wave's own accumulator registers supply them
-__global__ void pack_post1x1_kernel(const float* __restrict__ w, float* __restrict__ out) {
-    const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (unsigned)((POST_STEPS + POST_TAIL) * 256)) return;
-    const unsigned q = i & 3u, lane = (i >> 2) & 63u, t = i >> 8;
-    float v = 0.0f;
-    if (t < (unsigned)POST_STEPS) {
-        const unsigned r = t & 15u;
-        const unsigned ci = 32u * (t >> 4) + (r & 3u) + 8u * (r >> 2) + 4u * (lane >> 5);
-        v = w[(32u * q + (lane & 31u)) * 128u + ci];
-    }
-    out[i] = v;
-}
-
-int conv_validate(const mcq_conv_desc* d) {
-    if (!d || !d->x || !d->w_packed || !d->y) return MCQ_EINVAL;
-    if (d->N <= 0 || d->Cin <= 0 || d->H <= 0 || d->W <= 0 || d->Cout <= 0) return MCQ_EINVAL;
-    if ((d->ksize != 1 && d->ksize != 3) || (d->stride != 1 && d->stride != 2)) return MCQ_EINVAL;
-    if ((d->flags & MCQ_CONV_TAPS_LR) && (d->ksize != 3 || d->stride != 1 || (d->flags & (MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D | MCQ_CONV_WINOGRAD2D16 |
-                                                                                    MCQ_CONV_SILU_IN | MCQ_CONV_SQUARE_IN)))) return MCQ_EINVAL;
-    const unsigned fl = d->flags & ~(unsigned)MCQ_CONV_TAPS_LR;      // (a promise about the weights, not an operation)
-    if (fl & MCQ_CONV_POST_MASK) {                           // the following 1x1 layer inside this launch
-        const unsigned post = fl & MCQ_CONV_POST_MASK;
-        if ((post & (post - 1)) || !d->post_w || d->ksize != 3 || (d->flags & MCQ_CONV_TAPS_LR)) return MCQ_EINVAL;
-        unsigned allowed = MCQ_CONV_POST_MASK | MCQ_CONV_SILU_IN;
-        if (post == MCQ_CONV_POST_IGDN) allowed |= MCQ_CONV_SHUFFLE2;
-        if (post == MCQ_CONV_POST_GATE) allowed |= MCQ_CONV_RESIDUAL | MCQ_CONV_DUAL_SILU;
-        if (fl & ~allowed) return MCQ_EINVAL;
-        if (d->Cout != ((fl & MCQ_CONV_SHUFFLE2) ? 512 : 128)) return MCQ_EINVAL;
-        if (post == MCQ_CONV_POST_GATE && (!d->mul || !d->gate_id || d->stride != 1)) return MCQ_EINVAL;
-    }
-    if ((fl & MCQ_CONV_RESIDUAL) && !d->res) return MCQ_EINVAL;
-    if ((fl & (MCQ_CONV_GDN | MCQ_CONV_IGDN | MCQ_CONV_GATE | MCQ_CONV_MUL | MCQ_CONV_DSILU_MUL)) && !d->mul) return MCQ_EINVAL;
-    if ((fl & MCQ_CONV_GATE) && !d->gate_id) return MCQ_EINVAL;
-    if ((fl & MCQ_CONV_DUAL_SILU) && (!d->y_silu || (fl & MCQ_CONV_SILU_OUT))) return MCQ_EINVAL;
-    if (fl & (MCQ_CONV_GDN_BWD | MCQ_CONV_IGDN_BWD)) {      // s-launch with the GDN backward's element-wise part as its epilogue
-        if (!d->res || !d->mul || !d->y_silu || (fl & ~(unsigned)(MCQ_CONV_SQUARE_IN | MCQ_CONV_GDN_BWD | MCQ_CONV_IGDN_BWD)) ||
-            (fl & MCQ_CONV_GDN_BWD && fl & MCQ_CONV_IGDN_BWD) || d->ksize != 1) return MCQ_EINVAL;
-    }
-    if (fl & MCQ_CONV_GATE_BWD) {                            // s-launch with the gate's backward as its epilogue
-        if (!d->res || !d->mul || !d->y_silu || (fl & ~(unsigned)MCQ_CONV_GATE_BWD) || d->ksize != 1 || d->stride != 1) return MCQ_EINVAL;
-    }
-    if ((fl & MCQ_CONV_SILU_IN) && (fl & MCQ_CONV_SQUARE_IN)) return MCQ_EINVAL;
-    if (fl & MCQ_CONV_SHUFFLE2) {
-        if ((d->Cout & 3) || (fl & ~(unsigned)(MCQ_CONV_SHUFFLE2 | MCQ_CONV_SILU_IN | MCQ_CONV_SQUARE_IN | MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D | MCQ_CONV_WINOGRAD2D16 |
-                                               MCQ_CONV_DSILU_MUL | MCQ_CONV_RESIDUAL | MCQ_CONV_POST_IGDN))) return MCQ_EINVAL;
-        if ((fl & (MCQ_CONV_DSILU_MUL | MCQ_CONV_RESIDUAL)) && (fl & (MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D | MCQ_CONV_WINOGRAD2D16)))
-            return MCQ_EINVAL;
-    }
-    // one image's input slab plus the prefetch rings' over-read (up to 8 channels) must stay below 2 GiB: byte offsets and
-    // the descriptors' shrinking num_records are 32-bit (signed in the scalar arithmetic of the k-loop)
-    if ((uint64_t)(d->Cin + 8) * d->H * d->W * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
-    return MCQ_OK;
-}
-
-bool t16_takes(int N, int Cin, int H, int W, int Cout, int ksize, int stride, unsigned fl, int nprob) {
-    return N > 0 && H > 0 && W > 0 && nprob >= 1 && t16_shape(Cout, Cin, ksize) && stride == 1 && (fl & ~T16_FLAGS) == 0 &&
-           t16_tiles((long long)N * H * W, Cout, nprob) <= T16_MAX_TILES &&
-           (uint64_t)N * (Cin > Cout ? Cin : Cout) * H * W * 4ull < 0x80000000ull;
-}
-
-int conv_launch(const mcq_conv_desc* descs, int nprob, void* stream) {
-    const mcq_conv_desc* d = descs;
-    const unsigned fl = d->flags & ~(unsigned)MCQ_CONV_TAPS_LR;
-    const bool lr4 = d->flags & MCQ_CONV_TAPS_LR;      // only the filter's lower-right 2 x 2 taps are non-zero
-    ConvK k;
-    k.x = d->x; k.wp = d->w_packed;
-    k.wp64 = k.wp + section_floats(d->Cout, d->Cin, d->ksize, 4);
-    k.wp32 = k.wp64 + section_floats(d->Cout, d->Cin, d->ksize, 2);
-    k.bias = d->bias; k.y = d->y; k.y2 = d->y_silu; k.res = d->res; k.mul = d->mul; k.gid = d->gate_id;
-    k.N = d->N; k.Cin = d->Cin; k.H = d->H; k.W = d->W; k.Cout = d->Cout;
-    k.ks = d->ksize; k.stride = d->stride;
-    const int pad = d->ksize / 2;
-    k.Ho = (d->H + 2 * pad - d->ksize) / d->stride + 1;
-    k.Wo = (d->W + 2 * pad - d->ksize) / d->stride + 1;
-    k.S = pairs_padded(d->Cin, d->ksize);
-    k.TP = steps_padded(d->Cin, d->ksize);
-    k.flags = fl; k.res_scale = d->res_scale;
-    k.nprob = nprob;
-    k.post_w = d->post_w; k.post_b = d->post_bias; k.post_sub = 0;
-    for (int c = 1; c < MCQ_CONV_MAX_MULTI; ++c) {
-        const mcq_conv_desc* e = descs + (c < nprob ? c : 0);
-        ConvPtrs& a = k.alt[c - 1];
-        a.x = e->x; a.wp = e->w_packed;
-        a.wp64 = a.wp + section_floats(d->Cout, d->Cin, d->ksize, 4);
-        a.wp32 = a.wp64 + section_floats(d->Cout, d->Cin, d->ksize, 2);
-        a.bias = e->bias; a.y = e->y; a.y2 = e->y_silu; a.res = e->res; a.mul = e->mul; a.gid = e->gate_id;
-    }
-
-    if (fl & MCQ_CONV_WINOGRAD2D16) {
-        // F(2x2, 3x3) on the 16 x 16 x 4 instruction, two waves per SIMD (conv_wino16.hip)
-        if ((fl & (MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D)) || !wino_shape(d->Cout, d->ksize, d->stride, fl)) return MCQ_EINVAL;
-        W16K w;
-        w.x = d->x; w.wp = d->w_packed; w.bias = d->bias; w.y = d->y; w.y2 = d->y_silu; w.res = d->res;
-        for (int c = 1; c < W16_MAX_MULTI; ++c) {
-            const mcq_conv_desc* e = descs + (c < nprob ? c : 0);
-            W16Ptrs& a = w.alt[c - 1];
-            a.x = e->x; a.wp = e->w_packed; a.bias = e->bias; a.y = e->y; a.y2 = e->y_silu; a.res = e->res;
-        }
-        w.nprob = nprob; w.N = d->N; w.Cin = d->Cin; w.H = d->H; w.W = d->W; w.Cout = d->Cout; w.Ho = k.Ho; w.Wo = k.Wo;
-        w.flags = fl & ~(unsigned)MCQ_CONV_WINOGRAD2D16; w.res_scale = d->res_scale;
-        return mcq_wino16_launch(w, stream);
-    }
-    if (fl & MCQ_CONV_WINOGRAD2D) {
-        if ((fl & MCQ_CONV_WINOGRAD) || !wino_shape(d->Cout, d->ksize, d->stride, fl) || d->Cout % 128 != 0 || d->Cin % 8 != 0) return MCQ_EINVAL;
-        if ((uint64_t)(d->Cin + 16) * d->H * d->W * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
-        k.TP = k.S * 16;
-        k.wp32 = k.wp; k.wp64 = k.wp;
-        for (int c = 1; c < MCQ_CONV_MAX_MULTI; ++c) { k.alt[c - 1].wp32 = k.alt[c - 1].wp; k.alt[c - 1].wp64 = k.alt[c - 1].wp; }
-        // tile blocks: 32 tiles of 2 x 2 pixels shaped (32 >> b) rows x (1 << b) tiles, b by the fewest wasted lanes
-        const int Wt = (k.Wo + 1) / 2, Ht = (k.Ho + 1) / 2;
-        int best_log2 = 5; double best_util = -1.0;
-        for (int lg = 5; lg >= 0; --lg) {
-            const int bw = 1 << lg, bh = 32 >> lg;
-            const double cover = (double)((Ht + bh - 1) / bh * bh) * (double)((Wt + bw - 1) / bw * bw);
-            const double util = (double)Ht * Wt / cover;
-            if (util > best_util + 1e-9) { best_util = util; best_log2 = lg; }
-        }
-        k.bw_log2 = best_log2;
-        k.nbx = (Wt + (1 << best_log2) - 1) >> best_log2;
-        k.nby = (Ht + (32 >> best_log2) - 1) / (32 >> best_log2);
-        const long long tbw = (long long)k.N * k.nbx * k.nby;
-        if (tbw > 0x7fffffffLL) return MCQ_ETOOLARGE;
-        k.total_blocks = (int)tbw;
-        if ((uint64_t)d->Cout * (uint64_t)k.Ho * k.Wo * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
-        k.flags = fl & ~(unsigned)MCQ_CONV_WINOGRAD2D;
-        return launch_wino2d(k, tbw, d->Cout / 128, (hipStream_t)stream);
-    }
-    if (fl & MCQ_CONV_WINOGRAD) {
-        if (!wino_shape(d->Cout, d->ksize, d->stride, fl)) return MCQ_EINVAL;
-        if ((uint64_t)(d->Cin + 16) * d->H * d->W * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;     // (rings up to 8 channel pairs ahead)
-        const int forced_mb = (d->tile & 0xff) >> 4;
-        const int MBw = forced_mb == 2 || d->Cout % 128 != 0 ? 2 : 4;
-        k.TP = k.S * 12;
-        k.wp64 = k.wp + wino_section_floats(d->Cout, d->Cin, 4);
-        k.wp32 = k.wp64;
-        for (int c = 1; c < MCQ_CONV_MAX_MULTI; ++c) {
-            k.alt[c - 1].wp64 = k.alt[c - 1].wp + wino_section_floats(d->Cout, d->Cin, 4);
-            k.alt[c - 1].wp32 = k.alt[c - 1].wp64;
-        }
-        // pair blocks: 32 pairs shaped (32 >> b) rows x (1 << b) pairs, b by the fewest wasted lanes
-        const int Wp = (k.Wo + 1) / 2;
-        int best_log2 = 5; double best_util = -1.0;
-        for (int lg = 5; lg >= 2; --lg) {
-            const int bw = 1 << lg, bh = 32 >> lg;
-            const double cover = (double)((k.Ho + bh - 1) / bh * bh) * (double)((Wp + bw - 1) / bw * bw);
-            const double util = (double)k.Ho * Wp / cover;
-            if (util > best_util + 1e-9) { best_util = util; best_log2 = lg; }
-        }
-        k.bw_log2 = best_log2;
-        k.nbx = (Wp + (1 << best_log2) - 1) >> best_log2;
-        k.nby = (k.Ho + (32 >> best_log2) - 1) / (32 >> best_log2);
-        const long long tbw = (long long)k.N * k.nbx * k.nby;
-        if (tbw > 0x7fffffffLL) return MCQ_ETOOLARGE;
-        k.total_blocks = (int)tbw;
-        const int co_tiles = (d->Cout + 32 * MBw - 1) / (32 * MBw);
-        if ((uint64_t)co_tiles * 32u * (unsigned)MBw * (uint64_t)k.Ho * k.Wo * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
-        k.flags = fl & ~(unsigned)MCQ_CONV_WINOGRAD;
-        return MBw == 4 ? launch_wino<4>(k, tbw, co_tiles, (hipStream_t)stream) : launch_wino<2>(k, tbw, co_tiles, (hipStream_t)stream);
-    }
-
-    // launches too small to fill the chip with 32 x 32 tiles: 16 x 16 tiles, one per workgroup (conv_t16.h)
-    if (d->tile == 0 && t16_takes(d->N, d->Cin, d->H, d->W, d->Cout, d->ksize, d->stride, fl, nprob)) {
-        sec_note(descs, nprob, 8u);
-        T16K t;
-        const size_t sec = section_floats(d->Cout, d->Cin, 3, 4) + section_floats(d->Cout, d->Cin, 3, 2) + section_floats(d->Cout, d->Cin, 3, 1);
-        for (int c = 0; c < MCQ_CONV_MAX_MULTI; ++c) {
-            const mcq_conv_desc* e = descs + (c < nprob ? c : 0);
-            T16Ptrs& a = t.p[c];
-            a.x = e->x; a.wp = e->w_packed + sec; a.bias = e->bias; a.y = e->y; a.y2 = e->y_silu; a.res = e->res; a.mul = e->mul;
-        }
-        t.N = d->N; t.Cin = d->Cin; t.H = d->H; t.W = d->W; t.Cout = d->Cout; t.flags = fl; t.res_scale = d->res_scale;
-        const dim3 grid((unsigned)(((long long)d->N * d->H * d->W + 15) / 16), (unsigned)(d->Cout / 16), (unsigned)nprob);
-        if (d->Cin == 128) hipLaunchKernelGGL(conv_t16_kernel<8>, grid, dim3(256), 0, (hipStream_t)stream, t);
-        else hipLaunchKernelGGL(conv_t16_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, t);
-        return mcq_check_launch();
-    }
-
-    // <= 16 output channels, 3x3, stride 1, nothing but bias / PixelShuffle in the epilogue: the 16-row MFMA kernel
-    if (nprob == 1 && head16_shape(d->Cout, d->ksize) && d->stride == 1 && (d->tile & 0xff) == 0 &&
-        (fl & ~(unsigned)(MCQ_CONV_SHUFFLE2 | MCQ_CONV_SILU_IN)) == 0) {
-        if ((uint64_t)d->Cout * d->H * d->W * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
-        Head16K h;
-        h.x = d->x; h.wp16 = d->w_packed + general_floats(d->Cout, d->Cin, d->ksize); h.bias = d->bias; h.y = d->y;
-        h.N = d->N; h.Cin = d->Cin; h.H = d->H; h.W = d->W; h.Cout = d->Cout;
-        h.S4 = (d->Cin + 3) / 4;
-        h.gpr = (d->W + 15) / 16;
-        h.total_groups = (long long)d->N * d->H * h.gpr;
-        h.flags = fl;
-        const long long waves = (h.total_groups + H16_NB - 1) / H16_NB;
-        if ((waves + 3) / 4 > 0x7fffffffLL) return MCQ_ETOOLARGE;
-        const dim3 grid((unsigned)((waves + 3) / 4));
-        if (fl & MCQ_CONV_SILU_IN) hipLaunchKernelGGL(conv_head16_kernel<PRO_SILU>, grid, dim3(256), 0, (hipStream_t)stream, h);
-        else hipLaunchKernelGGL(conv_head16_kernel<PRO_NONE>, grid, dim3(256), 0, (hipStream_t)stream, h);
-        return mcq_check_launch();
-    }
-
-    // pixel-block shape: the power-of-two width that wastes the fewest lanes (wider wins ties)
-    int best_log2 = 5; double best_util = -1.0;
-    for (int lg = 5; lg >= 2; --lg) {
-        const int bw = 1 << lg, bh = 32 >> lg;
-        const double cover = (double)((k.Ho + bh - 1) / bh * bh) * (double)((k.Wo + bw - 1) / bw * bw);
-        const double util = (double)k.Ho * k.Wo / cover;
-        if (util > best_util + 1e-9) { best_util = util; best_log2 = lg; }
-    }
-    k.bw_log2 = best_log2;
-    const int bw = 1 << best_log2, bh = 32 >> best_log2;
-    k.nbx = (k.Wo + bw - 1) / bw;
-    k.nby = (k.Ho + bh - 1) / bh;
-    const long long tb = (long long)k.N * k.nbx * k.nby;
-    if (tb > 0x7fffffffLL) return MCQ_ETOOLARGE;
-    k.total_blocks = (int)tb;
-
-    // Wave tile and split-K.  Weight traffic per wave is the whole filter bank whatever the tile, so the tile stays
-    // as large as the layer allows (128 co x 64 px); when that leaves too few waves for the 1024 SIMDs the k-steps of
-    // a tile are split over 2/4/8 waves of one workgroup and reduced through LDS.
-    const int co32 = (d->Cout + 31) / 32;
-    int MB, NB, ksl = 0;
-    bool dsilu41 = false;                 // the 128 x 32 tile chosen over the 128 x 64 one for an input-gradient epilogue (see below)
-    const int forced = d->tile & 0xff;
-    if (forced) {
-        MB = forced >> 4; NB = forced & 15; ksl = (d->tile >> 8) & 3;
-        if ((MB != 1 && MB != 2 && MB != 4) || (NB != 1 && NB != 2 && NB != 4)) return MCQ_EINVAL;      // (no such tile: NB = 0 would divide by zero below)
-    }
-    else if (co32 == 1) {
-        // <= 32 output channels (the 12-channel head, the tiny fixture models): one weight load feeds NB MFMAs, so the
-        // widest pixel tile that still leaves >= 2048 waves amortises it best (head conv 2.34 -> 2.05 ms with NB = 4)
-        MB = 1; NB = (tb * nprob >= 4 * 2048) ? 4 : 2;
-        // Neon's 32-wide layers (channel 32, stride-1 stem: 256 x 256 ... 16 x 16 maps; round 5, tools/microbench_conv.py --neon,
-        // profiles/r05_neon_tile_sweep.txt): with <= 32 input channels a k-loop is 144 steps and the epilogue weighs as much as the
-        // weights' amortisation -- two pixel blocks per wave only where the launch has waves to spare (4 x 512x512: 218 us against
-        // 237 / 221 for one / four), one below that (256x256 49.9 vs 53.8 us, 128x128 16.0 vs 26.9, 64x64 11.5 vs 14.8), split over
-        // two waves when even that leaves SIMDs idle (4 x 64 -> 8 at 64x64: 11.6 us against 22.4)
-        if (d->Cin <= 64) {
-            NB = (tb * nprob >= 16384) ? 2 : 1;
-            while (ksl < 3 && (((tb + NB - 1) / NB * nprob) << ksl) < 1024) ++ksl;
-        }
-    }
-    else if (co32 == 2 && ((tb + 1) / 2) * nprob < 2048 && d->ksize == 3) {
-        // 64 output channels on maps that leave the 64 x 64 tile short of waves (Neon's 64-wide layers live on 64 x 64 maps):
-        // one wave per 32 x 32 tile, unsplit, instead of the larger tile split 4 / 8 ways through LDS (4 x 64 -> 64 at 64x64:
-        // 14.7 us against 21.4; 32 -> 64: 11.6 against 17.0)
-        MB = 1; NB = 1;
-        while (ksl < 3 && ((tb * co32 * nprob) << ksl) < 1024) ++ksl;
-    }
-    else {
-        // (the 128 x 32 tile <4, 1> is instantiated and reachable through `tile`; an automatic rule preferring it on
-        //  the 24x16 / 12x8 levels gained 0.4 % at batch 32 and lost 8 % on the batch-8 training step: not used)
-        static const int cand[3][2] = {{4, 2}, {2, 2}, {1, 1}};
-        MB = 1; NB = 1;
-        // Cout that is no multiple of 128 (model No. 12 of the reference: channel 192 = six 32-row bands): the 128-row tile would
-        // run its last instance half empty -- 8 bands of MFMAs for 6 -- where 64-row tiles cover the rows exactly; the 64 x 64 tile
-        // costs ~3 % more per MFMA than the 128 x 64 one (operand loads per MFMA), far less than a quarter of the work
-        const bool rows64 = ((co32 + 3) / 4) * 4 > ((co32 + 1) / 2) * 2;
-        for (int c = 0; c < 3; ++c) {
-            const int mb = cand[c][0], nb = cand[c][1];
-            if (mb > co32 || (mb == 4 && rows64)) continue;
-            const long long tiles = ((tb + nb - 1) / nb) * ((co32 + mb - 1) / mb);      // (per problem: the tile a single launch takes)
-            MB = mb; NB = nb;
-            if (tiles * 8 >= 1024) break;          // even an 8-way split would leave SIMDs idle: try a smaller tile
-        }
-        const long long tiles1 = ((tb + NB - 1) / NB) * ((co32 + MB - 1) / MB);             // one problem
-        const long long tiles = tiles1 * nprob;                                              // all problems of the launch
-        while (ksl < 3 && (tiles << ksl) < 2048) ++ksl;
-        int ksl1 = 0;                                                                        // what a single-problem launch would split
-        while (ksl1 < 3 && (tiles1 << ksl1) < 2048) ++ksl1;
-        // an 8-way split of the 128 x 64 tile runs as a 4-way split of the 128 x 32 tile instead: the same number of
-        // waves, half the LDS reduction depth, 3 waves / SIMD resident (8 x 128 x 32 x 32 layer: 50 -> 28 us)
-        // a 4-way split 128 x 64 tile that needs 1.5 rounds at 2 waves / SIMD -- the 48x32 level -- runs as
-        // the 64 x 64 tile split 2 ways, all waves resident at 3 / SIMD (120 -> 111 us per launch, +0.4 % images/s; with
-        // the earlier k-loop, whose address arithmetic weighed twice as much on the smaller tile, it cost 0.4 %)
-        // (judged per problem: two such problems in one launch are 6144 waves = two full rounds at 3 / SIMD, 204 us per pair,
-        //  where the 128 x 64 tile split 2 ways would be 1.5 rounds at 2 / SIMD, 224 us)
-        // (round 3, forced-tile sweeps with 2 / 4 problems per launch: with the paired heads in lockstep the 48x32 level mostly
-        //  runs as such launches, and then the 64 x 64 tile needs no split at all -- 4 problems: 449 -> 414 us, 2: 217 -> 215)
-        if (MB == 4 && NB == 2 && ksl1 == 2 && tiles1 * 4 > 2048 && tiles1 * 4 <= 3072 && d->ksize == 3 &&
-            k.S % 2 == 0 && (k.S >> 1) >= 8) { MB = 2; NB = 2; ksl = nprob >= 2 ? 0 : 1; }
-        if (MB == 4 && NB == 2 && ksl == 3 && d->ksize == 3 && k.S % 4 == 0 && (k.S >> 2) >= 8) { NB = 1; ksl = 2; }
-        // the same trade one step down: a 2-way split of the 128 x 64 tile runs as the UNSPLIT 128 x 32 tile -- as many waves, no
-        // LDS reduction, every wave finishes its own half of the pixels instead of the owner waves finishing all of them
-        // (two 8 x 128 x 64 x 64 problems in one launch, the AttentionBlock stacks of a training step: 153-156 -> 140-142 us)
-        else if (MB == 4 && NB == 2 && ksl == 1 && d->ksize == 3) { NB = 1; ksl = 0; }
-        // ... and a 4-way split of it in a multi-problem launch as the 64 x 64 tile split 2 ways (32 x 24x16 maps, 4 problems:
-        // 120 -> 112 us; one 192x128 map, 2 problems: 117 -> 110 us)
-        else if (MB == 4 && NB == 2 && ksl == 2 && nprob >= 2 && d->ksize == 3 && k.S % 2 == 0 && (k.S >> 1) >= 8) { MB = 2; ksl = 1; }
-        // input-gradient launches of the training step (* silu'(.) [+ dy]): their epilogue carries one more output-shaped side
-        // read and a sigmoid per element; the 128 x 32 tile has a band-wise instance of it (the 128 x 64 tile has no registers
-        // left for one) and at three waves per SIMD hides it better (8 x 128 x 128 x 128: 300-311 -> 270-277 us)
-        else if (MB == 4 && NB == 2 && ksl == 0 && (fl & MCQ_CONV_DSILU_MUL) && d->ksize == 3) { NB = 1; dsilu41 = true; }
-        // 1x1 layers (GDN / IGDN, the AttentionBlock gate): 64 k-steps per tile against an epilogue that reads and writes an
-        // output-shaped tensor each -- HBM time, not matrix time.  One pixel block per wave (half the epilogue per wave, three
-        // waves per SIMD to hide it) wins wherever the launch still fills the chip without a split: 32 x 128 x 384x256 GDN
-        // 1276 -> 1234 us, 192x128 323 -> 306, 96x64 87 -> 73, 48x32 (64 x 32 tile) 38.7 -> 26.3 (tools/microbench_conv.py --k1 --flags gdn)
-        if (d->ksize == 1 && d->stride == 1 && co32 >= 4) {
-            const long long t41 = tb * ((co32 + 3) / 4) * nprob, t21 = tb * ((co32 + 1) / 2) * nprob;
-            if (t41 >= 2048 && !rows64) { MB = 4; NB = 1; ksl = 0; }
-            else if (t21 >= 2048) { MB = 2; NB = 1; ksl = 0; }
-        }
-    }
-    if (fl & (MCQ_CONV_GDN_BWD | MCQ_CONV_IGDN_BWD)) {      // the instances that carry this epilogue: one pixel block per wave, no split
-        if (!(fl & MCQ_CONV_SQUARE_IN)) return MCQ_EINVAL;
-        NB = 1; ksl = 0;
-    }
-    if (fl & MCQ_CONV_GATE_BWD) { NB = 1; ksl = 0; }        // (likewise)
-    int post = 0;
-    if (fl & MCQ_CONV_POST_MASK) {
-        // unsplit 128-row tiles that fill the chip, or the caller runs the 1x1 layer as its own launch (mcq_conv2d_post_ok)
-        if (nprob != 1 || lr4) return MCQ_EINVAL;
-        if (!post_fills_chip(tb, (fl & MCQ_CONV_SHUFFLE2) ? 4 : 1) && forced != 0x41) return MCQ_EINVAL;     // (tile 0x41: on any map size)
-        MB = 4; NB = 1; ksl = 0; dsilu41 = false;
-        post = (fl & MCQ_CONV_POST_GATE) ? 2 : 1;
-        k.post_sub = (fl & MCQ_CONV_SHUFFLE2) ? 1 : 0;
-    }
-    const int pro = (fl & MCQ_CONV_SILU_IN) ? PRO_SILU : (fl & MCQ_CONV_SQUARE_IN) ? PRO_SQUARE : PRO_NONE;
-    long long ptiles = (tb + NB - 1) / NB;
-    // (round 5) the 128 x 64 tile of a 3x3 stride-1 layer over 32 PAIRS of horizontally adjacent pixels, when tile bit 0x400 asks
-    // for it: pair blocks shaped (32 >> b) rows x (1 << b) pairs, b by the fewest wasted lanes
-    const bool pair_ok = !post && !lr4 && MB == 4 && (NB == 2 || dsilu41) && ksl == 0 && d->ksize == 3 && d->stride == 1 && pro == PRO_NONE && (k.Wo & 1) == 0 &&
-                         !(fl & ~(unsigned)(MCQ_CONV_SILU_OUT | MCQ_CONV_RESIDUAL | MCQ_CONV_DUAL_SILU | MCQ_CONV_DSILU_MUL | MCQ_CONV_SHUFFLE2));
-    // (round 5, built and dropped: the launcher choosing it on its own for one-round launches, docs/experiments.md section 10.8)
-    const bool pair = pair_ok && (d->tile & 0x400);
-    if (pair) {
-        const int Wp = k.Wo / 2;
-        int bl = 5; double bu = -1.0;
-        for (int lg = 5; lg >= 2; --lg) {
-            const int bw2 = 1 << lg, bh2 = 32 >> lg;
-            const double cover = (double)((k.Ho + bh2 - 1) / bh2 * bh2) * (double)((Wp + bw2 - 1) / bw2 * bw2);
-            const double util = (double)k.Ho * Wp / cover;
-            if (util > bu + 1e-9) { bu = util; bl = lg; }
-        }
-        const int pnbx = (Wp + (1 << bl) - 1) >> bl, pnby = (k.Ho + (32 >> bl) - 1) / (32 >> bl);
-        const long long pt = (long long)k.N * pnbx * pnby;
-        NB = 2; k.bw_log2 = bl; k.nbx = pnbx; k.nby = pnby; ptiles = pt; k.total_blocks = (int)pt;
-    }
-    const int co_tiles = post ? 1 : (co32 + MB - 1) / MB;      // (POST through the shuffle: the four row tiles are the waves of a workgroup)
-    // the epilogue addresses one image of the output (and of every side input) through a 32-bit buffer offset,
-    // rows of the last cout tile included
-    if ((uint64_t)(post && k.post_sub ? 4 : co_tiles) * 32u * (unsigned)MB * (uint64_t)k.Ho * k.Wo * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
-    hipStream_t s = (hipStream_t)stream;
-    sec_note(descs, nprob, MB == 4 ? 1u : MB == 2 ? 2u : 4u);
-    if (MB == 4 && NB == 2) return launch_tile<4, 2, MCQ_PF42A, MCQ_PF42B, 4>(k, pro, ptiles, co_tiles, ksl, s, pair, lr4);
-    if (MB == 4 && NB == 1) return launch_tile<4, 1, 9, MCQ_PFB, 8>(k, pro, ptiles, co_tiles, ksl, s, false, lr4, post);
-    if (MB == 2 && NB == 2) return launch_tile<2, 2, 9, MCQ_PFB, 8>(k, pro, ptiles, co_tiles, ksl, s, false, lr4);
-    if (MB == 2 && NB == 1) return launch_tile<2, 1, 9, MCQ_PFB, 16>(k, pro, ptiles, co_tiles, ksl, s, false, lr4);
-    if (MB == 1 && NB == 4) return launch_tile<1, 4, 9, MCQ_PFB, 8>(k, pro, ptiles, co_tiles, ksl, s, false, lr4);
-    if (MB == 1 && NB == 2) return launch_tile<1, 2, 9, MCQ_PFB, 8>(k, pro, ptiles, co_tiles, ksl, s, false, lr4);
-    if (MB == 1 && NB == 1) return launch_tile<1, 1, 9, MCQ_PFB, 16>(k, pro, ptiles, co_tiles, ksl, s, false, lr4);
-    return MCQ_EINVAL;
-}
-
-}  // namespace
-
-extern "C" int mcq_conv2d_f32(const mcq_conv_desc* d, void* stream) {
-    const int rc = conv_validate(d);
-    return rc != MCQ_OK ? rc : conv_launch(d, 1, stream);
-}
-
-extern "C" int32_t mcq_conv2d_max_multi(void) { return MCQ_CONV_MAX_MULTI; }
-
-extern "C" size_t mcq_packed_post1x1_floats(void) { return (size_t)(POST_STEPS + POST_TAIL) * 256; }
-
-extern "C" int mcq_pack_post1x1_weight_f32(const float* w, float* out, void* stream) {
-    if (!w || !out) return MCQ_EINVAL;
-    hipLaunchKernelGGL(pack_post1x1_kernel, dim3((unsigned)(POST_STEPS + POST_TAIL)), dim3(256), 0, (hipStream_t)stream, w, out);
-    return mcq_check_launch();
-}
-
-extern "C" int32_t mcq_conv2d_post_ok(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t ksize, int32_t stride, uint32_t flags) {
-    const unsigned post = flags & MCQ_CONV_POST_MASK;
-    if (N <= 0 || Cin <= 0 || H <= 0 || W <= 0 || ksize != 3 || (stride != 1 && stride != 2) || !post || (post & (post - 1))) return 0;
-    const bool sub = flags & MCQ_CONV_SHUFFLE2;
-    if (sub && post != MCQ_CONV_POST_IGDN) return 0;
-    if (Cout != (sub ? 512 : 128)) return 0;
-    const int Ho = (H + 2 - 3) / stride + 1, Wo = (W + 2 - 3) / stride + 1;
-    int best_log2 = 5; double best_util = -1.0;             // (the pixel-block shape conv_launch picks)
-    for (int lg = 5; lg >= 2; --lg) {
-        const int bw = 1 << lg, bh = 32 >> lg;
-        const double cover = (double)((Ho + bh - 1) / bh * bh) * (double)((Wo + bw - 1) / bw * bw);
-        const double util = (double)Ho * Wo / cover;
-        if (util > best_util + 1e-9) { best_util = util; best_log2 = lg; }
-    }
-    const long long tb = (long long)N * ((Wo + (1 << best_log2) - 1) >> best_log2) * ((Ho + (32 >> best_log2) - 1) / (32 >> best_log2));
-    // (the number of 128 x 32 wave tiles, capped: >= 2048 is what mcq_conv2d_f32 takes on its own; below that a caller may still
-    //  force the fused form with tile 0x41 where it has measured a gain -- one image's large maps)
-    const long long waves = tb * (sub ? 4 : 1);
-    return (int32_t)(waves > 0x7fffffffLL ? 0x7fffffffLL : waves);
-}
-
-extern "C" int32_t mcq_conv2d_small_launch(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t ksize, int32_t stride,
-                                           uint32_t flags, int32_t nprob) {
-    return t16_takes(N, Cin, H, W, Cout, ksize, stride, flags, nprob) ? 1 : 0;
-}
-
-extern "C" int mcq_conv2d_multi_f32(const mcq_conv_desc* descs, int32_t n, void* stream) {
-    if (!descs || n < 1 || n > MCQ_CONV_MAX_MULTI) return MCQ_EINVAL;
-    for (int c = 0; c < n; ++c) {
-        const int rc = conv_validate(descs + c);
-        if (rc != MCQ_OK) return rc;
-        const mcq_conv_desc &a = descs[0], &b = descs[c];
-        if (a.N != b.N || a.Cin != b.Cin || a.H != b.H || a.W != b.W || a.Cout != b.Cout || a.ksize != b.ksize || a.stride != b.stride ||
-            a.flags != b.flags || a.res_scale != b.res_scale || a.tile != b.tile || (a.bias == nullptr) != (b.bias == nullptr))
-            return MCQ_EINVAL;                       // one geometry, one flag set, bias on all or none
-    }
-    return conv_launch(descs, n, stream);
-}
-

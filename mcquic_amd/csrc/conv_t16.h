@@ -1,4 +1,4 @@
-// 3x3 stride-1 convolutions of launches too small to fill the chip, on v_mfma_f32_16x16x4_f32 (included by conv_mfma.hip).
+// 3x3 stride-1 convolutions of launches too small to fill the chip, on v_mfma_f32_16x16x4_f32 (included by conv_launch.hip).
 //
 // The general kernel's smallest tile is 32 output channels x 32 pixels, and when a launch has fewer than ~2048 such tiles it
 // splits their k-steps over the 8 waves of ONE workgroup.  For the smallest maps of the network -- the 4x4 / 8x8 / 16x16 levels of
@@ -15,7 +15,7 @@
 // Cin = 128 a wave's share is 72 MFMAs and 72 + 72 operand registers, so there is NO ring -- a wave requests its whole slice
 // (18 sixteen-byte weight loads, 72 activation loads) and multiplies as the data arrives; wave 0 requests bias / residual / the
 // silu' operand before anything else, so the epilogue finds them there.  The partial tiles (4 floats per lane) meet in LDS, wave 0
-// adds them in slice order.  Weights: a fourth section of the general operand stream (conv_mfma.hip: pack_conv_weight_body),
+// adds them in slice order.  Weights: a fourth section of the general operand stream (conv_pack.hip: pack_conv_weight_body; t16_shape / t16_floats: conv_sizes.h),
 // [Cout / 16][(Cin / 4) x 9 steps / 4][64 lanes][4]: a lane's four consecutive k-steps are one 16-byte load.
 // Arithmetic and epilogue order are the general kernel's (bias, * silu'(.), + scale * residual, SiLU, twin); the summation order
 // over k differs (four channels per step, slices of channels), like between any two of its tiles.
@@ -32,8 +32,6 @@ struct T16K {
 };
 
 constexpr unsigned T16_FLAGS = MCQ_CONV_SILU_OUT | MCQ_CONV_RESIDUAL | MCQ_CONV_DUAL_SILU | MCQ_CONV_DSILU_MUL;
-inline bool t16_shape(int Cout, int Cin, int ksize) { return ksize == 3 && Cout >= 32 && Cout % 16 == 0 && (Cin == 64 || Cin == 128); }
-inline size_t t16_floats(int Cout, int Cin, int ksize) { return t16_shape(Cout, Cin, ksize) ? (size_t)(Cout / 16) * (size_t)(Cin / 4) * 9 * 64 : 0; }
 
 template <int QS>           // channel quads per wave = Cin / 16
 __global__ __launch_bounds__(256) void conv_t16_kernel(T16K k) {

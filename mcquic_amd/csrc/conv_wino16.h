@@ -1,4 +1,4 @@
-// Launch interface between conv_mfma.hip (mcq_conv2d_f32 / mcq_conv2d_multi_f32 dispatch) and conv_wino16.hip
+// Launch interface between conv_launch.hip (mcq_conv2d_f32 / mcq_conv2d_multi_f32 dispatch) and conv_wino16.hip
 // (F(2x2, 3x3) on v_mfma_f32_16x16x4_f32, two waves per SIMD).  Internal to the library.
 #pragma once
 #include <stdint.h>

@@ -1,6 +1,6 @@
 // F(2x2, 3x3) on v_mfma_f32_16x16x4_f32: the TWO-WAVES-PER-SIMD form of the opt-in Winograd mode (round 3).
 //
-// The first 2-D instance (conv_mfma.hip, TAPS == 16) gives a wave one 32-row band x 32 tiles x 16 transform positions = 256
+// The first 2-D instance (conv_mfma_kernel.h, TAPS == 16) gives a wave one 32-row band x 32 tiles x 16 transform positions = 256
 // accumulator registers: the whole AGPR half of a one-wave-per-SIMD register file.  Ablations put 22 % of its
 // time OUTSIDE the k-loop -- per 28 us tile ~7.7 us of prologue (first operands from HBM) and epilogue (residual loads, 256
 // accumulator reads) that a lone wave per SIMD exposes in full and cannot prefetch around (vmcnt retires in order).  The direct
@@ -44,7 +44,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino16_kernel(W16K p) {
                 P_x = a.x; P_wp = a.wp; P_bias = a.bias; P_y = a.y; P_y2 = a.y2; P_res = a.res;
             }
     }
-    // XCD-aware block order (see conv_mfma.hip): XCD k walks the contiguous k-th eighth of the tile blocks
+    // XCD-aware block order (see conv_mfma_kernel.h): XCD k walks the contiguous k-th eighth of the tile blocks
     unsigned wg = blockIdx.x;
     {
         const unsigned nwg = gridDim.x, xcd = wg & 7u, slot = wg >> 3;

@@ -2,7 +2,7 @@
 //
 // The reference gets these from torch.autograd over nn.Conv2d / F.conv2d / SiLU / GDN / sigmoid gates
 // (mcquic/nn/convs.py, nn/gdn.py, nn/blocks.py); here:
-//   * input gradients of every convolution reuse the forward MFMA kernel (conv_mfma.hip) with transformed weights
+//   * input gradients of every convolution reuse the forward MFMA kernel (mcq_conv2d_f32, conv_launch.hip) with transformed weights
 //     (flip + transpose; stride-2 and pixel-shuffle convs through the sub-pixel identity), so only the WEIGHT
 //     gradient needs its own contraction;
 //   * mcq_conv2d_wgrad_f32: dW[co][ci][tap] = sum over output pixels of dY[co][p] * X[ci][p + tap] -- a GEMM whose
@@ -551,6 +551,29 @@ __global__ void nonneg_reparam_bwd_kernel(const float* __restrict__ p, const flo
     }
 }
 
+// NonNegativeParametrizer itself (mcquic/nn/base.py:81-84): folded = max(p, bound)^2 - pedestal
+__global__ void nonneg_reparam_kernel(const float* __restrict__ p, float bound, float pedestal, float* __restrict__ out,
+                                      int64_t n) {
+    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) {
+        const float v = fmaxf(p[i], bound);
+        out[i] = v * v - pedestal;
+    }
+}
+
+// several parameters in one launch (the beta [C] and gamma [C, C] of every GDN layer after an optimizer step: 20 launches -> 1)
+constexpr int REPARAM_MAX_MULTI = 64;
+struct ReparamTable { const float* p[REPARAM_MAX_MULTI]; float* out[REPARAM_MAX_MULTI]; long long n[REPARAM_MAX_MULTI]; float bound[REPARAM_MAX_MULTI];
+                      float pedestal[REPARAM_MAX_MULTI]; };
+__global__ void nonneg_reparam_multi_kernel(ReparamTable t) {
+    const int c = (int)blockIdx.y;                              // (uniform index into the kernel-argument table)
+    const float* p = t.p[c]; float* out = t.out[c]; const long long n = t.n[c]; const float bound = t.bound[c], pedestal = t.pedestal[c];
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        const float v = fmaxf(p[i], bound);
+        out[i] = v * v - pedestal;
+    }
+}
+
 // out[n][c*4 + i*2 + j][y][x] = in[n][c][2y + i][2x + j]   (inverse of nn.PixelShuffle(2))
 __global__ void pixel_unshuffle2_kernel(const float* __restrict__ in, float* __restrict__ out, int N, int C, int H, int W) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;     // over the INPUT [N, C, 2H, 2W]
@@ -758,6 +781,32 @@ extern "C" int mcq_gdn_bwd_prep_f32(const float* x, const float* s, const float*
     if (!x || !s || !dy || !dx_direct || !ds || n <= 0) return MCQ_EINVAL;
     hipLaunchKernelGGL(gdn_bwd_prep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, s, dy, inverse,
                        dx_direct, ds, n);
+    return mcq_check_launch();
+}
+
+extern "C" int32_t mcq_nonneg_reparam_max_multi(void) { return REPARAM_MAX_MULTI; }
+
+extern "C" int mcq_nonneg_reparam_multi_f32(const float* const* p, float* const* out, const int64_t* n, const float* bound, const float* pedestal,
+                                            int32_t count, void* stream) {
+    if (!p || !out || !n || !bound || !pedestal || count < 1 || count > REPARAM_MAX_MULTI) return MCQ_EINVAL;
+    ReparamTable t;
+    long long most = 0;
+    for (int c = 0; c < REPARAM_MAX_MULTI; ++c) {
+        const int k = c < count ? c : 0;
+        if (!p[k] || !out[k] || n[k] <= 0) return MCQ_EINVAL;
+        t.p[c] = p[k]; t.out[c] = out[k]; t.n[c] = n[k]; t.bound[c] = bound[k]; t.pedestal[c] = pedestal[k];
+        if (n[k] > most) most = n[k];
+    }
+    long long blocks = (most + 255) / 256;
+    if (blocks > 256) blocks = 256;                          // (grid-stride loop inside)
+    hipLaunchKernelGGL(nonneg_reparam_multi_kernel, dim3((unsigned)blocks, (unsigned)count), dim3(256), 0, (hipStream_t)stream, t);
+    return mcq_check_launch();
+}
+
+extern "C" int mcq_nonneg_reparam_f32(const float* p, float bound, float pedestal, float* out, int64_t n, void* stream) {
+    if (!p || !out || n <= 0) return MCQ_EINVAL;
+    hipLaunchKernelGGL(nonneg_reparam_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p,
+                       bound, pedestal, out, n);
     return mcq_check_launch();
 }
 

@@ -161,7 +161,7 @@ __global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p) {
             // compile-time number, so the LDS read takes an immediate offset and nothing is computed per lane
             const int lsn = SPC ? (t + PF) % (SPC ? SPC : 1) : ls;
             const unsigned son = SPC ? (unsigned)lsn * step_bytes : soffL;
-            // vector-block major, each activation slot refilled right after its last use (as in conv_mfma_kernel)
+            // vector-block major, each activation slot refilled right after its last use (as in the convolution kernel)
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
 #pragma unroll

@@ -27,7 +27,8 @@ _WINOGRAD_MIN_PIXELS = int(os.environ.get("MCQUIC_AMD_WINOGRAD_MIN_PIXELS", str(
 #  7.3 -> 6.0 ms per encode+decode with the maps above it; at 12 k pixels, 32 x 24x16, it loses, 41 -> 44 us)
 _WINOGRAD_MIN_PIXELS_2D = int(os.environ.get("MCQUIC_AMD_WINOGRAD_MIN_PIXELS_2D", str(20 * 1024)))
 # which instance runs the F(2x2, 3x3) layers: 16 = v_mfma_f32_16x16x4_f32, two waves per SIMD (csrc/conv_wino16.hip; layers with
-# Cin % 16 == 0 and a SiLU / residual / twin / PixelShuffle epilogue), 32 = the one-wave-per-SIMD 32x32x2 instance of conv_mfma.hip
+# Cin % 16 == 0 and a SiLU / residual / twin / PixelShuffle epilogue), 32 = the one-wave-per-SIMD 32x32x2 instance of conv_mfma_kernel
+# (csrc/conv_wino32.hip)
 _W2D_KERNEL = int(os.environ.get("MCQUIC_AMD_W2D_KERNEL", "16"))
 _W16_EPILOGUES = CONV_SILU_OUT | CONV_RESIDUAL | CONV_DUAL_SILU
 
@@ -476,7 +477,7 @@ def set_slab_limit(nbytes: Optional[int]) -> int:
 
 
 def _slab_bytes(cin: int, h: int, wd: int, cout: int, ho: int, wo: int) -> int:
-    """What conv_validate / conv_launch bound (csrc/conv_mfma.hip): the input slab plus the prefetch rings' over-read, the output
+    """What conv_validate / conv_launch bound (csrc/conv_launch.hip): the input slab plus the prefetch rings' over-read, the output
     slab with its last 128-row tile complete."""
     return max((cin + 32) * h * wd * 4, -(-cout // 128) * 128 * ho * wo * 4)
 

@@ -626,7 +626,7 @@ def test_conv_winograd2d_epilogues(dev):
 @pytest.mark.parametrize("kernel", [16, 32])
 def test_conv_winograd2d_both_instances(dev, monkeypatch, kernel):
     """The two instances of the F(2x2, 3x3) form -- csrc/conv_wino16.hip (v_mfma_f32_16x16x4_f32, two waves per SIMD; the
-    default) and the 32x32x2 one inside csrc/conv_mfma.hip (MCQUIC_AMD_W2D_KERNEL=32; also the fallback for Cin % 16 != 0
+    default) and the 32x32x2 one of csrc/conv_wino32.hip (MCQUIC_AMD_W2D_KERNEL=32; also the fallback for Cin % 16 != 0
     and for epilogues the new kernel does not carry) -- are each held to F.conv2d, single launches and multi-problem ones."""
     from mcquic_amd import ops
     monkeypatch.setattr(ops, "_W2D_KERNEL", kernel)

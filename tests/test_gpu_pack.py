@@ -1,5 +1,5 @@
 """The packed operand stream of a 3x3 weight (include/mcquic_hip.h: mcq_pack_conv_weight_f32 and its grouped / masked forms)
-against a numpy restatement of the layout the conv kernel reads (csrc/conv_mfma.hip: [tile][k-step][lane][band] per copy,
+against a numpy restatement of the layout the conv kernel reads (csrc/conv_pack.hip: [tile][k-step][lane][band] per copy,
 k-step = channel pair * 9 + tap, lane = 32 * (ci & 1) + (co & 31); 16 zero steps behind every copy), and the masked re-pack a
 captured training step uses (parallel.GraphedTrainStep): only the named copies change."""
 import ctypes

@@ -170,7 +170,7 @@ def test_wgrad_rows_kernel_declines_other_shapes():
 
 def test_winograd_instance_keeps_its_accumulators_to_itself():
     """The 128-row Winograd instance of conv_mfma_kernel (opt-in path) addresses its 256 accumulator registers a0..a255 by
-    NUMBER from inline asm (csrc/conv_mfma.hip, `WASM`): correct only while the compiler's own code never touches an AGPR
+    NUMBER from inline asm (csrc/conv_mfma_kernel.h, `WASM`; instantiated in csrc/conv_wino32.hip): correct only while the compiler's own code never touches an AGPR
     and never spills.  Checked on the disassembly of the built object: in that kernel every AGPR operand belongs to one of
     the three hand-written instruction forms, and there is no scratch access."""
     import re
@@ -178,9 +178,9 @@ def test_winograd_instance_keeps_its_accumulators_to_itself():
     import subprocess
     import tempfile
     llvm = "/opt/rocm/lib/llvm/bin"
-    obj = os.path.join(ROOT, "mcquic_amd", "_obj", "conv_mfma.o")
+    obj = os.path.join(ROOT, "mcquic_amd", "_obj", "conv_wino32.o")
     if not os.path.exists(obj) or not os.path.exists(os.path.join(llvm, "llvm-objdump")):
-        pytest.skip("needs the built object mcquic_amd/_obj/conv_mfma.o and the ROCm llvm tools")
+        pytest.skip("needs the built object mcquic_amd/_obj/conv_wino32.o and the ROCm llvm tools")
     tmp = tempfile.mkdtemp()
     try:
         fat, co = os.path.join(tmp, "fat.bin"), os.path.join(tmp, "dev.co")

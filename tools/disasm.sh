@@ -1,5 +1,5 @@
 #!/bin/bash
-# gfx950 ISA of one built object: tools/disasm.sh conv_mfma > /tmp/conv_mfma.s
+# gfx950 ISA of one built object (mcquic_amd/_obj/NAME.o): tools/disasm.sh conv_tiles_128 > /tmp/conv_tiles_128.s
 set -e
 L=/opt/rocm/lib/llvm/bin; T=$(mktemp -d)
 $L/llvm-objcopy --dump-section .hip_fatbin=$T/fat.bin mcquic_amd/_obj/$1.o $T/copy.o

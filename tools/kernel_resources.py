@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Registers / scratch / occupancy of every kernel in a HIP source, from hipcc's -Rpass-analysis=kernel-resource-usage remarks.
 
-    python tools/kernel_resources.py mcquic_amd/csrc/conv_mfma.hip [extra hipcc flags]"""
+    python tools/kernel_resources.py mcquic_amd/csrc/conv_tiles_128.hip [extra hipcc flags]
+
+(conv_mfma_kernel's instances: conv_tiles_128 / _41 / _64 / _32 and conv_wino32.hip; conv_head16 / conv_t16: conv_launch.hip)"""
 import os
 import re
 import subprocess

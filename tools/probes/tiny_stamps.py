@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Where a tiny-map conv launch spends its ~10 us (round-3 probe).  Needs a scratch build of conv_mfma.hip with s_memrealtime
-stamps (not in the tree: the STAMP() lines are patched into a copy under mcquic_amd/variants/), loaded
+"""Where a tiny-map conv launch spends its ~10 us (round-3 probe).  Needs a scratch build of the conv kernel with s_memrealtime
+stamps (not in the tree: the script that patched the STAMP() lines into a copy of csrc/conv_mfma.hip, tools/probes/make_stamped_conv.py,
+was last in the tree at commit aaa3736 and applies to that file), loaded
 through MCQUIC_AMD_LIB.  The stamp buffer travels in the otherwise unused gate_id pointer.
 
     MCQUIC_AMD_LIB=$PWD/mcquic_amd/variants/stamps.so python tools/probes/tiny_stamps.py
