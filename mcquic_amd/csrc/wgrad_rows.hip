@@ -332,73 +332,35 @@ struct WgRowsReduceK {
     int nconv, groups, Cout, Cin, taps;
 };
 
-// dW[conv][co][ci][tap] = sum_g part[conv][g][tap][co][ci]; db[conv][co] = sum_s bias_part[conv][s][co]   (fixed order)
-__global__ __launch_bounds__(256) void wgrad_rows_reduce_kernel(WgRowsReduceK p) {
-    // a workgroup = 64 outputs x 4 slices of the group range (eight independent loads in flight per thread; the slice sums
-    // meet in LDS and are added in slice order)
-    __shared__ float red[4][64];
-    const int conv = blockIdx.y;
-    float* dw = p.dw[0];
-    float* dbias = p.dbias[0];
-#pragma unroll
-    for (int c = 1; c < ROWS_MAX_CONVS; ++c)
-        if (c == conv) { dw = p.dw[c]; dbias = p.dbias[c]; }
-    const int Cout = p.Cout, Cin = p.Cin;
-    const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const size_t i = (size_t)blockIdx.x * 64 + lane;                    // index into [tap][co][ci], then [co] of the bias
-    const size_t per = (size_t)p.taps * Cout * Cin;
-    const bool is_bias = i >= per;
-    const size_t co_b = i - per;
-    const bool live = is_bias ? (dbias != nullptr && co_b < (size_t)Cout) : true;
-    const int count = is_bias ? p.groups * 4 : p.groups;
-    const int per_slice = (count + 3) / 4;
-    const int s0 = slice * per_slice, s1 = s0 + per_slice < count ? s0 + per_slice : count;
-    const float* src = is_bias ? p.bias_part + (size_t)conv * p.groups * 4 * Cout + co_b : p.part + (size_t)conv * p.groups * per + i;
-    const size_t stride = is_bias ? (size_t)Cout : per;
-    float s = 0.0f;
-    if (live) {
-        int g = s0;
-        for (; g + 8 <= s1; g += 8) {
-            float v[8];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) v[k] = src[(size_t)(g + k) * stride];
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += v[k];
-        }
-        for (; g < s1; ++g) s += src[(size_t)g * stride];
-    }
-    red[slice][lane] = s;
-    __syncthreads();
-    if (slice != 0 || !live) return;
-    s = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
-    if (is_bias) { dbias[co_b] = s; return; }
-    const int ci = (int)(i % Cin);
-    const size_t r = i / Cin;
-    const int co = (int)(r % Cout);
-    const int tap = (int)(r / Cout);
-    dw[((size_t)co * Cin + ci) * p.taps + tap] = s;
+// The workspace of a launch, stated once: part[conv][group][tap][co][ci], then bias_part[conv][group * 4][co].
+struct RowsLayout { size_t part, bias, bias_at, total; };      // floats per group (partial sums, bias partials); where bias_part starts; all of it
+__host__ __device__ inline RowsLayout rows_layout(int taps, int Cout, int Cin, int groups, int nconv = 1) {
+    const size_t part = (size_t)taps * Cout * Cin, bias = (size_t)4 * Cout, all = (size_t)nconv * groups;
+    return RowsLayout{part, bias, all * part, all * (part + bias)};
 }
 
-// ---- the reduce passes of a whole backward pass in a few launches (round 5) ------------------------------------------------------
-// A captured training step held 56 reduce launches, 44 of them 5-9 us of latency for microseconds of traffic.  While deferral is
-// on (mcq_wgrad_defer; mcquic_amd.autograd.backward switches it on around a backward pass it owns) the entry points below record
-// their reduce pass per convolution instead of launching it, and mcq_wgrad_flush launches all recorded passes, up to
-// REDUCE_BATCH per launch (blockIdx.y = the convolution).  Same sums in the same order as the
-// one-by-one kernel.  The caller keeps every workspace alive until the flush and reads no weight gradient before it.
-constexpr int REDUCE_BATCH = 80;
+// One convolution's reduce pass: dW[co][ci][tap] = sum_g part[g][tap][co][ci]; db[co] = sum_s bias_part[s][co]   (fixed order)
 struct ReduceJob { const float* part; const float* bias_part; float* dw; float* dbias; int groups, Cout, Cin, taps; };
-struct ReduceBatch { ReduceJob job[REDUCE_BATCH]; };
 
-// grid (blocks of the largest job, jobs): a job's surplus blocks leave at once.  (The first form put the jobs' blocks back to back
-// on blockIdx.x and searched a prefix table: 72 dependent scalar loads per workgroup, 3 us each -- four times the one-by-one passes.)
-__global__ __launch_bounds__(256) void wgrad_rows_reduce_batch_kernel(ReduceBatch b) {
+__host__ __device__ inline ReduceJob reduce_job(const WgRowsReduceK& q, int conv, float* dw, float* dbias) {
+    const RowsLayout l = rows_layout(q.taps, q.Cout, q.Cin, q.groups);
+    return ReduceJob{q.part + (size_t)conv * q.groups * l.part, q.bias_part ? q.bias_part + (size_t)conv * q.groups * l.bias : nullptr,
+                     dw, dbias, q.groups, q.Cout, q.Cin, q.taps};
+}
+
+// a job's outputs, 64 to a workgroup: [tap][co][ci], then [co] of the bias
+__host__ __device__ inline size_t reduce_outputs(const ReduceJob& q, bool bias) {
+    return rows_layout(q.taps, q.Cout, q.Cin, q.groups).part + (bias ? (size_t)q.Cout : 0);
+}
+
+// a workgroup = 64 outputs x 4 slices of the group range (eight independent loads in flight per thread; the slice sums
+// meet in LDS and are added in slice order)
+__device__ __forceinline__ void reduce_block(const ReduceJob& q, unsigned block) {
     __shared__ float red[4][64];
-    const ReduceJob q = b.job[blockIdx.y];                              // (uniform index into the kernel-argument table)
     const int Cout = q.Cout, Cin = q.Cin;
     const int lane = threadIdx.x & 63, slice = threadIdx.x >> 6;
-    const size_t per = (size_t)q.taps * Cout * Cin;
-    if ((size_t)blockIdx.x * 64 >= per + (q.dbias ? (size_t)Cout : 0)) return;      // (workgroup-uniform)
-    const size_t i = (size_t)blockIdx.x * 64 + lane;
+    const size_t i = (size_t)block * 64 + lane;                         // index into [tap][co][ci], then [co] of the bias
+    const size_t per = reduce_outputs(q, false);
     const bool is_bias = i >= per;
     const size_t co_b = i - per;
     const bool live = is_bias ? (q.dbias != nullptr && co_b < (size_t)Cout) : true;
@@ -431,6 +393,34 @@ __global__ __launch_bounds__(256) void wgrad_rows_reduce_batch_kernel(ReduceBatc
     q.dw[((size_t)co * Cin + ci) * q.taps + tap] = s;
 }
 
+// the reduce pass of one launch, right behind it: blockIdx.y = the convolution
+__global__ __launch_bounds__(256) void wgrad_rows_reduce_kernel(WgRowsReduceK p) {
+    const int conv = blockIdx.y;
+    float* dw = p.dw[0];
+    float* dbias = p.dbias[0];
+#pragma unroll
+    for (int c = 1; c < ROWS_MAX_CONVS; ++c)
+        if (c == conv) { dw = p.dw[c]; dbias = p.dbias[c]; }
+    reduce_block(reduce_job(p, conv, dw, dbias), blockIdx.x);
+}
+
+// ---- the reduce passes of a whole backward pass in a few launches (round 5) ------------------------------------------------------
+// A captured training step held 56 reduce launches, 44 of them 5-9 us of latency for microseconds of traffic.  While deferral is
+// on (mcq_wgrad_defer; mcquic_amd.autograd.backward switches it on around a backward pass it owns) the entry points below record
+// their reduce pass per convolution instead of launching it, and mcq_wgrad_flush launches all recorded passes, up to
+// REDUCE_BATCH per launch (blockIdx.y = the convolution).  Same sums in the same order as the one-by-one kernel: both run
+// reduce_block.  The caller keeps every workspace alive until the flush and reads no weight gradient before it.
+constexpr int REDUCE_BATCH = 80;
+struct ReduceBatch { ReduceJob job[REDUCE_BATCH]; };
+
+// grid (blocks of the largest job, jobs): a job's surplus blocks leave at once.  (The first form put the jobs' blocks back to back
+// on blockIdx.x and searched a prefix table: 72 dependent scalar loads per workgroup, 3 us each -- four times the one-by-one passes.)
+__global__ __launch_bounds__(256) void wgrad_rows_reduce_batch_kernel(ReduceBatch b) {
+    const ReduceJob q = b.job[blockIdx.y];                              // (uniform index into the kernel-argument table)
+    if ((size_t)blockIdx.x * 64 >= reduce_outputs(q, q.dbias != nullptr)) return;      // (workgroup-uniform)
+    reduce_block(q, blockIdx.x);
+}
+
 std::mutex g_defer_mu;
 bool g_defer = false;
 // recorded reduce passes, per device (a job is only ever flushed onto a stream of the device its buffers live on)
@@ -438,19 +428,16 @@ std::unordered_map<int, std::vector<ReduceJob>> g_jobs;
 inline int current_device() { int d = 0; (void)hipGetDevice(&d); return d; }
 
 // the second pass of a weight-gradient launch: now, or recorded per convolution for mcq_wgrad_flush
-inline void reduce_pass(const WgRowsReduceK& q, unsigned gx, unsigned nconv, hipStream_t s) {
+inline void reduce_pass(const WgRowsReduceK& q, unsigned gx, hipStream_t s) {
     {
         std::lock_guard<std::mutex> lock(g_defer_mu);
         if (g_defer) {
-            const size_t per = (size_t)q.taps * q.Cout * q.Cin;
             std::vector<ReduceJob>& mine = g_jobs[current_device()];
-            for (unsigned c = 0; c < nconv; ++c)
-                mine.push_back(ReduceJob{q.part + (size_t)c * q.groups * per, q.bias_part ? q.bias_part + (size_t)c * q.groups * 4 * q.Cout : nullptr,
-                                           q.dw[c], q.dbias[c], q.groups, q.Cout, q.Cin, q.taps});
+            for (int c = 0; c < q.nconv; ++c) mine.push_back(reduce_job(q, c, q.dw[c], q.dbias[c]));
             return;
         }
     }
-    hipLaunchKernelGGL(wgrad_rows_reduce_kernel, dim3(gx, nconv), dim3(256), 0, s, q);
+    hipLaunchKernelGGL(wgrad_rows_reduce_kernel, dim3(gx, (unsigned)q.nconv), dim3(256), 0, s, q);
 }
 
 // ---- 3x3 stride-2 convolutions (ResidualBlockWithStride's two convs, the 3-channel stem) --------------------------------
@@ -802,23 +789,54 @@ inline bool tiny_shape(int N, int Cin, int H, int W, int Cout) {
 
 #include "wgrad_t16.h"
 
+namespace {
+// a launch's pointer table as kernel arguments: the slots past nconv repeat slot 0 (the kernels' select chains read every slot)
+template <class T>
+inline void fill_slots(T* (&slot)[ROWS_MAX_CONVS], T* const* table, int nconv) {
+    for (int c = 0; c < ROWS_MAX_CONVS; ++c) slot[c] = table ? table[c < nconv ? c : 0] : nullptr;
+}
+
+// the arguments of a strip walk (over an H x W map, r its plan) and of its reduce pass; returns the reduce pass's grid.x
+inline unsigned rows_fill(WgRowsK& p, WgRowsReduceK& q, const RowsPlan& r, const float* const* x, const float* const* dy, float* const* dw,
+                          float* const* dbias, int nconv, bool any_bias, float* workspace, int taps, int N, int Cin, int H, int W, int Cout) {
+    p = WgRowsK{};
+    fill_slots(p.x, x, nconv); fill_slots(p.dy, dy, nconv);
+    fill_slots(q.dw, dw, nconv); fill_slots(q.dbias, dbias, nconv);
+    const RowsLayout l = rows_layout(taps, Cout, Cin, r.groups, nconv);
+    p.part = workspace;
+    p.bias_part = any_bias ? workspace + l.bias_at : nullptr;
+    p.nconv = nconv; p.groups = r.groups;
+    p.N = N; p.Cin = Cin; p.Cout = Cout; p.H = H; p.W = W;
+    p.strips = r.strips; p.row_chunks = r.row_chunks; p.rpc = r.rpc; p.units = r.units; p.splits = r.splits; p.ups = r.ups;
+    q.part = workspace; q.bias_part = p.bias_part; q.nconv = nconv; q.groups = r.groups; q.Cout = Cout; q.Cin = Cin; q.taps = taps;
+    return (unsigned)((l.part + (any_bias ? (size_t)Cout : 0) + 63) / 64);
+}
+
+// a single problem's one-element pointer tables
+struct OneConv { const float* x[1]; const float* dy[1]; float* dw[1]; float* dbias[1]; };
+}  // namespace
+
 extern "C" int32_t mcq_conv2d_wgrad_nchw_max_group(void) { return ROWS_MAX_CONVS; }
 
 extern "C" size_t mcq_conv2d_wgrad_nchw_workspace_floats(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout) {
     if (wgt16_shape(N, Cin, H, W, Cout)) return 1;                                            // (wgrad_t16.h: one pass, no workspace)
     RowsPlan r;
     if (!rows_plan(N, Cin, H, W, Cout, r)) return tiny_shape(N, Cin, H, W, Cout) ? 1 : 0;      // (the small-map kernel needs no workspace)
-    return (size_t)r.gmax * 9 * Cout * Cin + (size_t)r.gmax * 4 * Cout;
+    return rows_layout(9, Cout, Cin, r.gmax).total;
 }
 
 extern "C" int mcq_conv2d_wgrad_nchw_group_f32(const float* const* x, const float* const* dy, float* const* dw, float* const* dbias,
                                                int32_t nconv, float* workspace, int32_t N, int32_t Cin, int32_t H, int32_t W,
                                                int32_t Cout, void* stream) {
     if (!x || !dy || !dw || !workspace || nconv < 1 || nconv > ROWS_MAX_CONVS) return MCQ_EINVAL;
+    bool any_bias = false;
+    for (int c = 0; c < nconv; ++c) {
+        if (!x[c] || !dy[c] || !dw[c]) return MCQ_EINVAL;
+        any_bias = any_bias || (dbias && dbias[c]);
+    }
+    hipStream_t s = (hipStream_t)stream;
     if (wgt16_shape(N, Cin, H, W, Cout)) {                          // few pixels: 16 x 16 tiles, one pass (wgrad_t16.h)
-        for (int c = 0; c < nconv; ++c)
-            if (!x[c] || !dy[c] || !dw[c]) return MCQ_EINVAL;
-        wgt16_launch(x, dy, dw, dbias, nconv, N, Cin, H, W, Cout, 9, false, (hipStream_t)stream);
+        wgt16_launch(x, dy, dw, dbias, nconv, N, Cin, H, W, Cout, 9, false, s);
         return mcq_check_launch();
     }
     RowsPlan r;
@@ -832,34 +850,15 @@ extern "C" int mcq_conv2d_wgrad_nchw_group_f32(const float* const* x, const floa
     if (!planned) {      // (never more groups than the nconv = 1 plan the workspace query assumes)
         if (!tiny_shape(N, Cin, H, W, Cout)) return MCQ_EINVAL;
         WgTinyK t;
-        for (int c = 0; c < ROWS_MAX_CONVS; ++c) {
-            const int k = c < nconv ? c : 0;
-            if (!x[k] || !dy[k] || !dw[k]) return MCQ_EINVAL;
-            t.x[c] = x[k]; t.dy[c] = dy[k]; t.dw[c] = dw[k]; t.dbias[c] = dbias ? dbias[k] : nullptr;
-        }
+        fill_slots(t.x, x, nconv); fill_slots(t.dy, dy, nconv); fill_slots(t.dw, dw, nconv); fill_slots(t.dbias, dbias, nconv);
         t.N = N; t.Cin = Cin; t.Cout = Cout; t.H = H; t.W = W;
         const dim3 grid((unsigned)((Cin + 15) / 16), (unsigned)((Cout + 15) / 16), (unsigned)nconv);
-        hipLaunchKernelGGL(conv_wgrad_tiny_kernel, grid, dim3(256), tiny_lds_bytes(H, W), (hipStream_t)stream, t);
+        hipLaunchKernelGGL(conv_wgrad_tiny_kernel, grid, dim3(256), tiny_lds_bytes(H, W), s, t);
         return mcq_check_launch();
     }
-    WgRowsK p{};
+    WgRowsK p;
     WgRowsReduceK q;
-    bool any_bias = false;
-    for (int c = 0; c < ROWS_MAX_CONVS; ++c) {
-        const int k = c < nconv ? c : 0;
-        if (!x[k] || !dy[k] || !dw[k]) return MCQ_EINVAL;
-        p.x[c] = x[k]; p.dy[c] = dy[k];
-        q.dw[c] = dw[k]; q.dbias[c] = dbias ? dbias[k] : nullptr;
-        any_bias = any_bias || q.dbias[c] != nullptr;
-    }
-    const size_t per_conv = (size_t)r.groups * 9 * Cout * Cin;
-    p.part = workspace;
-    p.bias_part = any_bias ? workspace + (size_t)nconv * per_conv : nullptr;
-    p.nconv = nconv; p.groups = r.groups;
-    p.N = N; p.Cin = Cin; p.Cout = Cout; p.H = H; p.W = W;
-    p.strips = r.strips; p.row_chunks = r.row_chunks; p.rpc = r.rpc; p.units = r.units; p.splits = r.splits; p.ups = r.ups;
-    q.part = workspace; q.bias_part = p.bias_part; q.nconv = nconv; q.groups = r.groups; q.Cout = Cout; q.Cin = Cin; q.taps = 9;
-    hipStream_t s = (hipStream_t)stream;
+    const unsigned gx = rows_fill(p, q, r, x, dy, dw, dbias, nconv, any_bias, workspace, 9, N, Cin, H, W, Cout);
     const dim3 grid((unsigned)(r.groups * nconv), (unsigned)((Cin + 31) / 32), (unsigned)((Cout + 31) / 32));
     if (r.F == 8) {
         if (any_bias) hipLaunchKernelGGL((conv_wgrad_rows_kernel<true, 8>), grid, dim3(256), 0, s, p);
@@ -868,53 +867,40 @@ extern "C" int mcq_conv2d_wgrad_nchw_group_f32(const float* const* x, const floa
         if (any_bias) hipLaunchKernelGGL((conv_wgrad_rows_kernel<true, 4>), grid, dim3(256), 0, s, p);
         else hipLaunchKernelGGL((conv_wgrad_rows_kernel<false, 4>), grid, dim3(256), 0, s, p);
     }
-    const size_t per = (size_t)9 * Cout * Cin + (any_bias ? (size_t)Cout : 0);
-    reduce_pass(q, (unsigned)((per + 63) / 64), (unsigned)nconv, s);
+    reduce_pass(q, gx, s);
     return mcq_check_launch();
 }
 
 extern "C" int mcq_conv2d_wgrad_nchw_f32(const float* x, const float* dy, float* dw, float* dbias, float* workspace, int32_t N,
                                          int32_t Cin, int32_t H, int32_t W, int32_t Cout, void* stream) {
-    const float* xs[1] = {x};
-    const float* dys[1] = {dy};
-    float* dws[1] = {dw};
-    float* dbs[1] = {dbias};
-    return mcq_conv2d_wgrad_nchw_group_f32(xs, dys, dws, dbias ? dbs : nullptr, 1, workspace, N, Cin, H, W, Cout, stream);
+    const OneConv one{{x}, {dy}, {dw}, {dbias}};
+    return mcq_conv2d_wgrad_nchw_group_f32(one.x, one.dy, one.dw, one.dbias, 1, workspace, N, Cin, H, W, Cout, stream);
 }
 
 extern "C" size_t mcq_conv2d_wgrad1x1_nchw_workspace_floats(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout) {
     if (wgt16_shape(N, Cin, H, W, Cout)) return 1;
     RowsPlan r;
     if ((H & 1) || !rows_plan(N, Cin, H, W, Cout, r, 1)) return 0;
-    return (size_t)r.groups * Cout * Cin + (size_t)r.groups * 4 * Cout;
+    return rows_layout(1, Cout, Cin, r.gmax).total;
 }
 
 extern "C" int mcq_conv2d_wgrad1x1_nchw_f32(const float* x, const float* dy, float* dw, float* dbias, float* workspace, int32_t N,
                                             int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t square_x, void* stream) {
     if (!x || !dy || !dw || !workspace) return MCQ_EINVAL;
+    const OneConv one{{x}, {dy}, {dw}, {dbias}};
+    hipStream_t s = (hipStream_t)stream;
     if (wgt16_shape(N, Cin, H, W, Cout)) {                          // few pixels: 16 x 16 tiles, one pass (wgrad_t16.h)
-        const float* xs[1] = {x};
-        const float* dys[1] = {dy};
-        float* dws[1] = {dw};
-        float* dbs[1] = {dbias};
-        wgt16_launch(xs, dys, dws, dbias ? dbs : nullptr, 1, N, Cin, H, W, Cout, 1, square_x != 0, (hipStream_t)stream);
+        wgt16_launch(one.x, one.dy, one.dw, one.dbias, 1, N, Cin, H, W, Cout, 1, square_x != 0, s);
         return mcq_check_launch();
     }
     RowsPlan r;
     if ((H & 1) || !rows_plan(N, Cin, H, W, Cout, r, 1)) return MCQ_EINVAL;
-    WgRowsK p{};
+    WgRowsK p;
     WgRowsReduceK q;
-    for (int c = 0; c < ROWS_MAX_CONVS; ++c) { p.x[c] = x; p.dy[c] = dy; q.dw[c] = dw; q.dbias[c] = dbias; }
-    p.part = workspace;
-    p.bias_part = dbias ? workspace + (size_t)r.groups * Cout * Cin : nullptr;
-    p.nconv = 1; p.groups = r.groups;
-    p.N = N; p.Cin = Cin; p.Cout = Cout; p.H = H; p.W = W;
-    p.strips = r.strips; p.row_chunks = r.row_chunks; p.rpc = r.rpc; p.units = r.units; p.splits = r.splits; p.ups = r.ups;
-    q.part = workspace; q.bias_part = p.bias_part; q.nconv = 1; q.groups = r.groups; q.Cout = Cout; q.Cin = Cin; q.taps = 1;
-    hipStream_t s = (hipStream_t)stream;
+    const bool b = dbias != nullptr, sq = square_x != 0;
+    const unsigned gx = rows_fill(p, q, r, one.x, one.dy, one.dw, one.dbias, 1, b, workspace, 1, N, Cin, H, W, Cout);
     const dim3 grid((unsigned)r.groups, (unsigned)((Cin + 63) / 64), (unsigned)((Cout + 63) / 64));
 #define MCQ_LAUNCH_ROWS1(B_, S_, F_) hipLaunchKernelGGL((conv_wgrad_rows1_kernel<B_, S_, F_>), grid, dim3(256), 0, s, p)
-    const bool b = dbias != nullptr, sq = square_x != 0;
     if (r.F == 8) {
         if (b) { if (sq) MCQ_LAUNCH_ROWS1(true, true, 8); else MCQ_LAUNCH_ROWS1(true, false, 8); }
         else { if (sq) MCQ_LAUNCH_ROWS1(false, true, 8); else MCQ_LAUNCH_ROWS1(false, false, 8); }
@@ -923,15 +909,14 @@ extern "C" int mcq_conv2d_wgrad1x1_nchw_f32(const float* x, const float* dy, flo
         else { if (sq) MCQ_LAUNCH_ROWS1(false, true, 4); else MCQ_LAUNCH_ROWS1(false, false, 4); }
     }
 #undef MCQ_LAUNCH_ROWS1
-    const size_t per = (size_t)Cout * Cin + (dbias ? (size_t)Cout : 0);
-    reduce_pass(q, (unsigned)((per + 63) / 64), 1u, s);
+    reduce_pass(q, gx, s);
     return mcq_check_launch();
 }
 
 extern "C" size_t mcq_conv2d_wgrad_s2_nchw_workspace_floats(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout) {
     RowsPlan r;
     if ((H & 1) || (W & 1) || !rows_plan(N, Cin, H / 2, W / 2, Cout, r, 9, true)) return 0;
-    return (size_t)r.gmax * 9 * Cout * Cin + (size_t)r.gmax * 4 * Cout;
+    return rows_layout(9, Cout, Cin, r.gmax).total;
 }
 
 extern "C" int mcq_conv2d_wgrad_s2_nchw_f32(const float* x, const float* dy, float* dw, float* dbias, float* workspace, int32_t N,
@@ -939,21 +924,15 @@ extern "C" int mcq_conv2d_wgrad_s2_nchw_f32(const float* x, const float* dy, flo
     if (!x || !dy || !dw || !workspace) return MCQ_EINVAL;
     RowsPlan r;
     if ((H & 1) || (W & 1) || !rows_plan(N, Cin, H / 2, W / 2, Cout, r, 9, true)) return MCQ_EINVAL;
-    WgRowsK p{};
+    const OneConv one{{x}, {dy}, {dw}, {dbias}};
+    WgRowsK p;
     WgRowsReduceK q;
-    for (int c = 0; c < ROWS_MAX_CONVS; ++c) { p.x[c] = x; p.dy[c] = dy; q.dw[c] = dw; q.dbias[c] = dbias; }
-    p.part = workspace;
-    p.bias_part = dbias ? workspace + (size_t)r.groups * 9 * Cout * Cin : nullptr;
-    p.nconv = 1; p.groups = r.groups;
-    p.N = N; p.Cin = Cin; p.Cout = Cout; p.H = H / 2; p.W = W / 2;          // the walk's map = dY's
-    p.strips = r.strips; p.row_chunks = r.row_chunks; p.rpc = r.rpc; p.units = r.units; p.splits = r.splits; p.ups = r.ups;
-    q.part = workspace; q.bias_part = p.bias_part; q.nconv = 1; q.groups = r.groups; q.Cout = Cout; q.Cin = Cin; q.taps = 9;
+    const unsigned gx = rows_fill(p, q, r, one.x, one.dy, one.dw, one.dbias, 1, dbias != nullptr, workspace, 9, N, Cin, H / 2, W / 2, Cout);   // the walk's map = dY's
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)r.groups, (unsigned)((Cin + 31) / 32), (unsigned)((Cout + 31) / 32));
     if (dbias) hipLaunchKernelGGL(conv_wgrad_rows_s2_kernel<true>, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(conv_wgrad_rows_s2_kernel<false>, grid, dim3(256), 0, s, p);
-    const size_t per = (size_t)9 * Cout * Cin + (dbias ? (size_t)Cout : 0);
-    reduce_pass(q, (unsigned)((per + 63) / 64), 1u, s);
+    reduce_pass(q, gx, s);
     return mcq_check_launch();
 }
 
@@ -980,7 +959,7 @@ extern "C" int mcq_wgrad_flush(int32_t discard, void* stream) {
     // a launch's grid.x is its LARGEST job's block count: jobs go largest first, and a launch ends where the next job would leave
     // more than a quarter of its row of blocks empty (the first form mixed 128 -> 512 shuffle convolutions with 1x1 ones:
     // three quarters of 738 k workgroups were dispatched to leave at once, 233 us)
-    auto blocks_of = [](const ReduceJob& q) { return (unsigned)(((size_t)q.taps * q.Cout * q.Cin + (q.dbias ? (size_t)q.Cout : 0) + 63) / 64); };
+    auto blocks_of = [](const ReduceJob& q) { return (unsigned)((reduce_outputs(q, q.dbias != nullptr) + 63) / 64); };
     std::stable_sort(jobs.begin(), jobs.end(), [&](const ReduceJob& a, const ReduceJob& b) { return blocks_of(a) > blocks_of(b); });
     size_t at = 0;
     while (at < jobs.size()) {

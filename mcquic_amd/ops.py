@@ -1172,6 +1172,12 @@ _defer = {"on": False, "keep": []}
 # (round 6, built and dropped: the weight-gradient launches queued onto a side stream, docs/experiments.md section 11.8)
 
 
+def _set_deferral(on: bool) -> None:
+    """The deferral state lives in two places, this module's flag and the library's: they only ever change together."""
+    _lib.load().mcq_wgrad_defer(int(on))
+    _defer["on"] = on
+
+
 class wgrad_deferral:
     """`with ops.wgrad_deferral():` around a backward pass this library owns end to end (autograd.backward, parallel.GraphedTrainStep):
     inside, weight-gradient launches leave their partial tiles in their workspaces and record the reduce pass; on exit ALL recorded
@@ -1181,24 +1187,24 @@ class wgrad_deferral:
     def __enter__(self):
         self.active = _WGRAD_DEFER and not _defer["on"]
         if self.active:
-            _defer["on"] = True
-            _lib.load().mcq_wgrad_defer(1)
+            _set_deferral(True)
         return self
 
     def __exit__(self, exc_type, exc, tb):
         if not self.active:
             return False
         lib = _lib.load()
-        lib.mcq_wgrad_defer(0)
-        _defer["on"] = False
+        _set_deferral(False)
         try:
-            if exc_type is None and lib.mcq_wgrad_pending():
-                dev = _defer["keep"][0].device if _defer["keep"] else torch.device("cuda", torch.cuda.current_device())
-                with _guard(dev):
-                    check(lib.mcq_wgrad_flush(0, _stream()), "mcq_wgrad_flush")
-            else:
-                lib.mcq_wgrad_flush(1, None)
+            if exc_type is None:
+                # the library records a reduce pass under the device its launch ran on and flushes the current device's: every
+                # device that holds a kept workspace flushes its own passes on its own stream
+                for dev in dict.fromkeys(k.device for k in _defer["keep"] if isinstance(k, torch.Tensor)):
+                    with _guard(dev):
+                        if lib.mcq_wgrad_pending():
+                            check(lib.mcq_wgrad_flush(0, _stream()), "mcq_wgrad_flush")
         finally:
+            lib.mcq_wgrad_flush(1, None)                     # (whatever is left: the pass it belonged to is gone)
             del _defer["keep"][:]
         return False
 
@@ -1209,14 +1215,12 @@ class wgrad_now:
     def __enter__(self):
         self.was = _defer["on"]
         if self.was:
-            _lib.load().mcq_wgrad_defer(0)
-            _defer["on"] = False
+            _set_deferral(False)
         return self
 
     def __exit__(self, *exc):
         if self.was:
-            _lib.load().mcq_wgrad_defer(1)
-            _defer["on"] = True
+            _set_deferral(True)
         return False
 
 
@@ -1231,9 +1235,19 @@ def _keep(*tensors) -> None:
         _defer["keep"].extend(t.untyped_storage() for t in tensors[1:] if t is not None)
 
 
-def _wgrad_outputs(x, dy, ksize: int, want_bias: bool):
-    dw = torch.empty((dy.shape[1], x.shape[1], ksize, ksize), dtype=torch.float32, device=x.device)
-    return dw, (torch.empty((dy.shape[1],), dtype=torch.float32, device=x.device) if want_bias else None)
+def _wgrad_outputs(shapes, device):
+    return [None if shape is None else torch.empty(shape, dtype=torch.float32, device=device) for shape in shapes]
+
+
+def _wgrad_rows_launch(nws: int, device, shapes, launch):
+    """One row-kernel launch (csrc/wgrad_rows.hip): a workspace of `nws` floats and an empty output per shape, `launch(ws, outs)`
+    on `device`, and everything kept alive for a deferred reduce pass.  Returns the outputs (None where the shape is None)."""
+    ws = torch.empty(nws, dtype=torch.float32, device=device)
+    outs = _wgrad_outputs(shapes, device)
+    with _guard(device):
+        launch(ws, outs)
+    _keep(ws, *outs)
+    return outs
 
 
 def conv2d_wgrad_group(xs, dys, want_bias: bool = True):
@@ -1259,17 +1273,15 @@ def conv2d_wgrad_group(xs, dys, want_bias: bool = True):
         gx = [_dev(t, "x") for t in xs[lo:lo + cap]]
         gd = [_dev(t, "dy") for t in dys[lo:lo + cap]]
         k = len(gx)
-        ws = torch.empty(nws * k, dtype=torch.float32, device=gx[0].device)
-        dws = [torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=gx[0].device) for _ in range(k)]
-        dbs = [torch.empty((cout,), dtype=torch.float32, device=gx[0].device) for _ in range(k)] if want_bias else None
         table = ctypes.c_void_p * k
-        with _guard(gx[0].device):
+
+        def launch(ws, outs):
             check(lib.mcq_conv2d_wgrad_nchw_group_f32(table(*[t.data_ptr() for t in gx]), table(*[t.data_ptr() for t in gd]),
-                                                      table(*[t.data_ptr() for t in dws]),
-                                                      table(*[t.data_ptr() for t in dbs]) if want_bias else None, k, _ptr(ws),
+                                                      table(*[t.data_ptr() for t in outs[:k]]),
+                                                      table(*[t.data_ptr() for t in outs[k:]]) if want_bias else None, k, _ptr(ws),
                                                       n, cin, h, w, cout, _stream()), "mcq_conv2d_wgrad_nchw_group_f32")
-        _keep(ws, *dws, *(dbs or []))
-        out.extend(zip(dws, dbs if want_bias else [None] * k))
+        outs = _wgrad_rows_launch(nws * k, gx[0].device, [(cout, cin, 3, 3)] * k + [(cout,) if want_bias else None] * k, launch)
+        out.extend(zip(outs[:k], outs[k:]))
     return out
 
 
@@ -1280,41 +1292,25 @@ def conv2d_wgrad(x: torch.Tensor, dy: torch.Tensor, ksize: int, stride: int, squ
     n, cin, h, w = x.shape
     cout, ho, wo = dy.shape[1], dy.shape[2], dy.shape[3]
     lib = _lib.load()
-    if ksize == 3 and stride == 1 and not square_x and _WGRAD_ROWS:
-        # straight from the NCHW tensors (csrc/wgrad_rows.hip); 0 = a shape that kernel does not take
-        nws = lib.mcq_conv2d_wgrad_nchw_workspace_floats(n, cin, h, w, cout)
+    shapes = [(cout, cin, ksize, ksize), (cout,) if want_bias else None]
+    # straight from the NCHW tensors (csrc/wgrad_rows.hip), the first form that applies: (applies?, workspace query, launch, its
+    # extra arguments); a query's 0 = a shape that kernel does not take
+    rows = ((ksize == 3 and stride == 1 and not square_x,
+             lib.mcq_conv2d_wgrad_nchw_workspace_floats, lib.mcq_conv2d_wgrad_nchw_f32, ()),
+            (ksize == 3 and stride == 2 and not square_x and (ho, wo) == (h // 2, w // 2),
+             lib.mcq_conv2d_wgrad_s2_nchw_workspace_floats, lib.mcq_conv2d_wgrad_s2_nchw_f32, ()),
+            (ksize == 1 and stride == 1,
+             lib.mcq_conv2d_wgrad1x1_nchw_workspace_floats, lib.mcq_conv2d_wgrad1x1_nchw_f32, (int(square_x),)))
+    for applies, query, fn, extra in rows if _WGRAD_ROWS else ():
+        nws = query(n, cin, h, w, cout) if applies else 0
         if nws:
-            ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-            dw, db = _wgrad_outputs(x, dy, 3, want_bias)
-            with _guard(x.device):
-                check(lib.mcq_conv2d_wgrad_nchw_f32(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), n, cin, h, w, cout, _stream()),
-                      "mcq_conv2d_wgrad_nchw_f32")
-            _keep(ws, dw, db)
-            return (dw, db) if want_bias else dw
-    if ksize == 3 and stride == 2 and not square_x and _WGRAD_ROWS and (ho, wo) == (h // 2, w // 2):
-        nws = lib.mcq_conv2d_wgrad_s2_nchw_workspace_floats(n, cin, h, w, cout)
-        if nws:
-            ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-            dw, db = _wgrad_outputs(x, dy, 3, want_bias)
-            with _guard(x.device):
-                check(lib.mcq_conv2d_wgrad_s2_nchw_f32(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), n, cin, h, w, cout, _stream()),
-                      "mcq_conv2d_wgrad_s2_nchw_f32")
-            _keep(ws, dw, db)
-            return (dw, db) if want_bias else dw
-    if ksize == 1 and stride == 1 and _WGRAD_ROWS:
-        nws = lib.mcq_conv2d_wgrad1x1_nchw_workspace_floats(n, cin, h, w, cout)
-        if nws:
-            ws = torch.empty(nws, dtype=torch.float32, device=x.device)
-            dw, db = _wgrad_outputs(x, dy, 1, want_bias)
-            with _guard(x.device):
-                check(lib.mcq_conv2d_wgrad1x1_nchw_f32(_ptr(x), _ptr(dy), _ptr(dw), _ptr(db), _ptr(ws), n, cin, h, w, cout,
-                                                       int(square_x), _stream()), "mcq_conv2d_wgrad1x1_nchw_f32")
-            _keep(ws, dw, db)
+            dw, db = _wgrad_rows_launch(nws, x.device, shapes, lambda ws, outs: check(
+                fn(_ptr(x), _ptr(dy), _ptr(outs[0]), _ptr(outs[1]), _ptr(ws), n, cin, h, w, cout, *extra, _stream()), fn.__name__))
             return (dw, db) if want_bias else dw
     xt = torch.empty((n, h, w, cin), dtype=torch.float32, device=x.device)
     dyt = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
     ws = torch.empty(lib.mcq_conv2d_wgrad_workspace_floats(n, cin, h, w, cout, ksize, stride), dtype=torch.float32, device=x.device)
-    dw, db = _wgrad_outputs(x, dy, ksize, want_bias)
+    dw, db = _wgrad_outputs(shapes, x.device)
     with _guard(x.device):
         check(lib.mcq_nchw_to_nhwc_pair_f32(_ptr(x), _ptr(xt), cin, h * w, int(square_x), _ptr(dy), _ptr(dyt), cout, ho * wo, n,
                                             _stream()), "mcq_nchw_to_nhwc_pair_f32")

@@ -404,6 +404,70 @@ def test_deferred_reduce_passes_match_plain_backward(dev, kind):
         assert torch.equal(grads["plain"][n], grads["deferred"][n]), n
 
 
+def _wgrad_entry_point(form, cin, cout, want_bias, dev):
+    """(run, workspace floats) of one weight-gradient entry point of csrc/wgrad_rows.hip at its smallest strip-walk shape: 768
+    pixels of dY, above the 512-pixel one-pass form.  run() -> the flat list of its dW and db tensors."""
+    from mcquic_amd import ops
+    lib = ops._lib.load()
+    g = torch.Generator().manual_seed(cin * 100 + cout)
+    n, h, w = 2, 16, 24
+    k = 3 if form == "s1_group" else 1
+    ksize, stride, hi, wi = (1, 1, h, w) if form.startswith("1x1") else (3, 2, 16, 32) if form == "s2" else (3, 1, h, w)
+    xs = [torch.randn((n, cin, hi, wi), generator=g).to(dev) for _ in range(k)]
+    dys = [torch.randn((n, cout, hi // stride, wi // stride), generator=g).to(dev) for _ in range(k)]
+    query = {"s1": lib.mcq_conv2d_wgrad_nchw_workspace_floats, "s1_group": lib.mcq_conv2d_wgrad_nchw_workspace_floats,
+             "s2": lib.mcq_conv2d_wgrad_s2_nchw_workspace_floats, "1x1": lib.mcq_conv2d_wgrad1x1_nchw_workspace_floats,
+             "1x1_sq": lib.mcq_conv2d_wgrad1x1_nchw_workspace_floats}[form]
+
+    def run():
+        if form == "s1_group":
+            return [t for pair in ops.conv2d_wgrad_group(xs, dys, want_bias=want_bias) for t in pair if t is not None]
+        r = ops.conv2d_wgrad(xs[0], dys[0], ksize, stride, square_x=form == "1x1_sq", want_bias=want_bias)
+        return list(r) if want_bias else [r]
+    return run, query(n, cin, hi, wi, cout)
+
+
+@pytest.mark.parametrize("form,cin,cout,want_bias", [("s1", 32, 32, False), ("s1_group", 32, 32, True), ("s2", 32, 32, True),
+                                                      ("1x1", 32, 32, True), ("1x1_sq", 32, 32, True),
+                                                      # a partial 32 x 32 (64 x 64) tile, and a bias tail of 40 in the reduce grid's last block
+                                                      ("s1", 24, 40, True), ("s1_group", 24, 40, True), ("1x1_sq", 24, 40, True)])
+def test_deferred_reduce_equals_immediate_per_entry_point(dev, form, cin, cout, want_bias):
+    """Every row-walk entry point, reduced right away (wgrad_rows_reduce_kernel) and inside ops.wgrad_deferral() (recorded, then
+    wgrad_rows_reduce_batch_kernel at the exit): the same sums in the same order, so dW and db bit for bit."""
+    from mcquic_amd import ops
+    run, nws = _wgrad_entry_point(form, cin, cout, want_bias, dev)
+    assert nws > 1, "outside the strip walk's domain: the reduce pass would not run"
+    assert ops._WGRAD_ROWS and ops._WGRAD_DEFER
+    now = run()
+    with ops.wgrad_deferral():
+        later = run()
+        assert ops._lib.load().mcq_wgrad_pending() == (3 if form == "s1_group" else 1)
+    torch.cuda.synchronize()
+    assert ops._lib.load().mcq_wgrad_pending() == 0 and not ops._defer["keep"]
+    assert len(now) == len(later) == (3 if form == "s1_group" else 1) * (2 if want_bias else 1)
+    for a, b in zip(now, later):
+        assert torch.equal(a, b)
+
+
+def test_deferral_flushes_on_the_tensors_device():
+    """the library records a reduce pass under the device its launch ran on.  With the operands on cuda:1 while cuda:0
+    is current, the exit must flush cuda:1's passes there -- it used to ask the current device, hear of none and discard them."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two devices")
+    from mcquic_amd import ops
+    assert torch.cuda.current_device() == 0
+    run, nws = _wgrad_entry_point("s1", 32, 32, True, torch.device("cuda:1"))
+    assert nws > 1
+    now = run()
+    with ops.wgrad_deferral():
+        later = run()
+    torch.cuda.synchronize(1)
+    assert torch.cuda.current_device() == 0
+    assert not ops._defer["keep"]
+    for a, b in zip(now, later):
+        assert a.device == torch.device("cuda:1") and torch.equal(a, b)
+
+
 def test_deferral_steps_aside_for_accumulation_hooks_and_frozen_weights(dev):
     """the deferred reduce passes hand the engine dW tensors that are only written by the flush.  (1) a second
     backward() onto existing .grad (gradient accumulation) must add REDUCED values: autograd.backward then reduces launch by
