@@ -300,19 +300,23 @@ def mse_loss(a, b):
     return torch.nn.functional.mse_loss(a, b)
 
 
-# ---- ResidualBlock / AttentionBlock as whole autograd nodes ---------------------------------------------------------
+# ---- ResidualBlock / AttentionBlock as whole autograd nodes, alone and in lockstep ------------------------------------------
+# One walk per block kind, written over k problems of one shape: `ResidualBlockFn` / `AttentionBlockFn` are its k = 1 use,
+# `LockstepFn` runs it over k same-structure stacks (`latentHead` / `quantizationHead`: RB, AttentionBlock, conv3x3 on the same z,
+# mcquic/modules/compressor.py:148-160; `dequantizationHead` / `sideHead`: AttentionBlock, conv3x3, RB, :166-175, independent until
+# their sum): layer by layer the k problems share ONE multi-problem launch (2k inside AttentionBlocks; the paired heads' 15 + 15
+# convolutions become 10 launches each way), and with one problem every such launch is the single launch with the same operands.
+# A forward body returns (outputs, each carrying its SiLU twin; what backward needs); a backward body returns the input gradients,
+# appends the 3x3 weight-gradient operand pairs and the convolutions they belong to to `pairs` / `owners` (one grouped launch at the
+# end of the node, `_wgrads_into`) and records every other parameter gradient in `grads` (id(parameter) -> tensor).
 # `denseNorm` blocks (mcquic/nn/blocks.py:179-200: nn.GroupNorm where the second activation was; what configs/neon.yaml trains) take
-# the same nodes: the middle of the block is  t1 -> GroupNorm -> u  instead of  t1 -> SiLU -> s1  (the SiLU rode in conv1's epilogue;
+# the same bodies: the middle of the block is  t1 -> GroupNorm -> u  instead of  t1 -> SiLU -> s1  (the SiLU rode in conv1's epilogue;
 # the normalisation is launches of its own, csrc/norm.hip), everything around it -- multi-problem launches, the input gradient's
 # `* silu'(x) + dy` epilogue, grouped weight gradients -- is shared.  A normalised block's tape entry carries six tensors
 # (x, sx, t1, u, mean, rstd) where a plain one carries four (x, sx, t1, s1); its parameters are (w1, b1, w2, b2, gamma, beta).
 def _rb_norm(block):
     """The block's GroupNorm module, or None for a plain block."""
     return block._branch[2] if getattr(block, "denseNorm", False) else None
-
-
-def _rb_nsaved(block) -> int:
-    return 6 if _rb_norm(block) is not None else 4
 
 
 def _rb_params(block):
@@ -324,25 +328,15 @@ def _rb_params(block):
     return ps
 
 
-def _rb_forward(block, x, sx):
-    """y = conv2(act2(conv1(silu(x)))) + x, act2 = SiLU (two fused launches) or GroupNorm; returns (y, silu(y), what backward needs)."""
-    ys, sys_, saved = _rb_forward_multi([block], [x], [sx])
-    return ys[0], sys_[0], saved[0]
-
-
-def _rb_backward(block, saved, dy, pairs, need_dx: bool = True, norm_grads=None):
-    """Input gradient of a ResidualBlock; the two weight-gradient operand pairs are appended to `pairs` for a grouped launch:
-    d_t1 = conv(dy, W2^T) * silu'(t1);  dx = conv(d_t1, W1^T) * silu'(x) + dy   (normalised: d_t1 = GroupNorm'(conv(dy, W2^T)))."""
-    return _rb_backward_multi([block], [saved], [dy], pairs, norm_grads=norm_grads, need_dx=need_dx)[0]
-
-
-def _wgrads(pairs):
-    """[(dW, db), ...] of the 3x3 stride-1 convs whose (input, output-gradient) pairs are given: one grouped launch."""
-    return ops.conv2d_wgrad_group([a for a, _ in pairs], [b for _, b in pairs], want_bias=True)
+def _attn_params(block):
+    """Main RB 0..2 then side RB 0..2, each `_rb_params`, then the 1x1 conv's (w, b)."""
+    c11 = block._sideBranch[3]
+    return [p for stack in (block._mainBranch, block._sideBranch) for i in range(3) for p in _rb_params(stack[i])] + [c11.weight, c11.bias]
 
 
 def _rb_forward_multi(blocks, xs, sxs):
-    """Several ResidualBlocks of one shape side by side: each of the two layers is ONE launch for all of them."""
+    """y = conv2(act2(conv1(silu(x)))) + x for several ResidualBlocks of one shape side by side, act2 = SiLU or GroupNorm: each of
+    the two layers is ONE launch for all of them, and every y carries silu(y) from its launch."""
     norm = _rb_norm(blocks[0]) is not None
     t1s = ops.conv2d_multi(sxs, [blk._branch[1].packed() for blk in blocks], dual_silu=not norm)
     if norm:
@@ -356,227 +350,76 @@ def _rb_forward_multi(blocks, xs, sxs):
         mids = [ops.silu_twin(t) for t in t1s]
     ys = ops.conv2d_multi(mids, [blk._branch[3].packed() for blk in blocks], per_problem=[dict(res=x) for x in xs], dual_silu=True)
     if norm:
-        saved = [(x, sx, t1, u, st[0], st[1]) for x, sx, t1, u, st in zip(xs, sxs, t1s, mids, stats)]
-    else:
-        saved = [(x, sx, t1, s1) for x, sx, t1, s1 in zip(xs, sxs, t1s, mids)]
-    return ys, [ops.silu_twin(y) for y in ys], saved
+        return ys, [(x, sx, t1, u, st[0], st[1]) for x, sx, t1, u, st in zip(xs, sxs, t1s, mids, stats)]
+    return ys, [(x, sx, t1, s1) for x, sx, t1, s1 in zip(xs, sxs, t1s, mids)]
 
 
-def _rb_backward_multi(blocks, saveds, dys, pairs, norm_grads=None, need_dx: bool = True):
-    """Input gradients of several ResidualBlocks of one shape, two launches in all (+ the normalisations' own); operand pairs
-    appended per block as (conv1 pair, conv2 pair); a normalised block's (d gamma, d beta) go into `norm_grads` (one entry per block)."""
+def _rb_backward_multi(blocks, saveds, dys, pairs, owners, grads, need_dx: bool = True):
+    """Input gradients of several ResidualBlocks of one shape, two launches in all (+ the normalisations' own):
+    d_t1 = conv(dy, W2^T) * silu'(t1);  dx = conv(d_t1, W1^T) * silu'(x) + dy   (normalised: d_t1 = GroupNorm'(conv(dy, W2^T)));
+    operand pairs appended per block as (conv1 pair, conv2 pair)."""
     c1s, c2s = [blk._branch[1] for blk in blocks], [blk._branch[3] for blk in blocks]
-    norm = _rb_norm(blocks[0]) is not None
-    if norm:
+    if _rb_norm(blocks[0]) is not None:
         d_us = ops.conv2d_multi(dys, [_dgrad_packed(c, c.weight) for c in c2s])
         d_t1s = []
         for blk, sv, d_u in zip(blocks, saveds, d_us):
             gn = blk._branch[2]
-            d_t1, dgw, dgb = ops.group_norm_bwd(sv[2], d_u, gn.weight, sv[4], sv[5], gn.num_groups, want_params=True)
+            d_t1, grads[id(gn.weight)], grads[id(gn.bias)] = ops.group_norm_bwd(sv[2], d_u, gn.weight, sv[4], sv[5], gn.num_groups, want_params=True)
             d_t1s.append(d_t1)
-            if norm_grads is not None:
-                norm_grads.append((dgw, dgb))
     else:
         d_t1s = ops.conv2d_multi(dys, [_dgrad_packed(c, c.weight) for c in c2s], per_problem=[dict(dsilu_mul=sv[2]) for sv in saveds])
     dxs = [None] * len(blocks)
     if need_dx:
         dxs = ops.conv2d_multi(d_t1s, [_dgrad_packed(c, c.weight) for c in c1s],
                                per_problem=[dict(dsilu_mul=sv[0], res=dy) for sv, dy in zip(saveds, dys)])
-    for sv, d_t1, dy in zip(saveds, d_t1s, dys):
-        pairs.append((sv[1], d_t1))
-        pairs.append((sv[3], dy))
+    for c1, c2, sv, d_t1, dy in zip(c1s, c2s, saveds, d_t1s, dys):
+        pairs.extend([(sv[1], d_t1), (sv[3], dy)])
+        owners.extend([c1, c2])
     return dxs
 
 
-class ResidualBlockFn(torch.autograd.Function):
-    """y = conv2(act2(conv1(silu(x)))) + x  (mcquic/nn/blocks.py:179-200) as two fused launches each way:
-         forward   t1, silu(t1) = conv1(silu(x))                      (SiLU twin stored by the producing launch)
-                   y,  silu(y)  = conv2(silu(t1)) + x
-         backward  d_t1 = conv(dy, W2^T) * silu'(t1)                   (MCQ_CONV_DSILU_MUL epilogue)
-                   dx   = conv(d_t1, W1^T) * silu'(x) + dy             (... + MCQ_CONV_RESIDUAL: the skip path's gradient)
-                   dW1, db1, dW2, db2: ONE grouped weight-gradient launch over (silu(x), d_t1) and (silu(t1), dy)
-       No stand-alone SiLU / SiLU-backward / add kernels, no channel-major copies.  `sx` = silu(x) is an input so that a
-       producer's twin is reused; the second output silu(y) is the next block's `sx` (no gradient flows through it: every
-       consumer differentiates through y itself).  `denseNorm`: act2 = GroupNorm (see above), parameters + (gamma, beta)."""
-
-    @staticmethod
-    def forward(ctx, x, sx, *rest):
-        block = rest[-1]
-        y, sy, saved = _rb_forward(block, x, sx)
-        ctx.save_for_backward(*saved)
-        ctx.block = block
-        ctx.wgrad_slots = range(2, 1 + len(rest))
-        ctx.mark_non_differentiable(sy)
-        ctx.set_materialize_grads(False)        # (or autograd fills a zero tensor of sy's size for `_dsy` on every backward)
-        return y, sy
-
-    @staticmethod
-    def backward(ctx, dy, _dsy):
-        pairs, ng = [], []
-        dx = _rb_backward(ctx.block, ctx.saved_tensors, dy.contiguous(), pairs, ctx.needs_input_grad[0], norm_grads=ng)
-        (dw1, db1), (dw2, db2) = _wgrads(pairs)
-        extra = list(ng[0]) if ng else []
-        return (dx, None, dw1, db1, dw2, db2, *extra, None)
+def _attn_forward_multi(layer, xs, sxs):
+    """out = a * sigmoid(b) + x,  a = RB^3(x),  b = conv1x1(RB^3(x))   (mcquic/nn/blocks.py:245-288) for several AttentionBlocks
+    of one shape.  The main and side stacks apply the same layer shapes to different tensors: RB by RB they share a launch like the
+    blocks themselves do (on the 16x16 ... 4x4 maps of a training crop a launch is latency, not work)."""
+    k = len(layer)
+    a, b, sa, sb = list(xs), list(xs), list(sxs), list(sxs)
+    saved = []
+    for i in range(3):
+        ys, sv = _rb_forward_multi([m._mainBranch[i] for m in layer] + [m._sideBranch[i] for m in layer], a + b, sa + sb)
+        sys_ = [ops.silu_twin(y) for y in ys]
+        a, b, sa, sb = ys[:k], ys[k:], sys_[:k], sys_[k:]
+        saved.append(sv)
+    # a * sigmoid(conv1x1(b)) + x as the 1x1 launch's epilogue (like inference), silu(out) for the block that follows from the same
+    # launch; the 1x1 output itself is not kept: backward recomputes it in the launch that needs it (MCQ_CONV_GATE_BWD)
+    outs = ops.conv2d_multi(b, [m._sideBranch[3].packed() for m in layer],
+                            per_problem=[dict(gate_mul=ai, gate_id=xi) for ai, xi in zip(a, xs)], dual_silu=True)
+    return outs, (a, b, saved)
 
 
-class AttentionBlockFn(torch.autograd.Function):
-    """out = a * sigmoid(b) + x,  a = RB^3(x),  b = conv1x1(RB^3(x))   (mcquic/nn/blocks.py:245-288) as ONE autograd node.
-    The two stacks apply the same layer shapes to different tensors: layer by layer they share a launch (mcq_conv2d_multi_f32),
-    in both directions -- on the 16x16 ... 4x4 maps of a training crop a launch is latency, not work --, every ResidualBlock
-    is two fused launches each way, and the twelve 3x3 weight gradients of the block leave in ONE grouped launch.
-    Parameter order: main RB 0..2 then side RB 0..2, each (w1, b1, w2, b2[, gamma, beta]), then the 1x1 conv's (w, b)."""
-
-    @staticmethod
-    def forward(ctx, x, sx, *rest):
-        block = rest[-1]
-        saved = []
-        a, sa, b, sb = x, sx, x, sx
-        for i in range(3):
-            (a, b), (sa, sb), keep = _rb_forward_multi([block._mainBranch[i], block._sideBranch[i]], [a, b], [sa, sb])
-            saved.extend(keep[0])
-            saved.extend(keep[1])
-        # a * sigmoid(conv1x1(b)) + x as the 1x1 launch's epilogue (like inference), silu(out) for the block that follows from the same
-        # launch; the 1x1 output itself is not kept: backward recomputes it in the launch that needs it (MCQ_CONV_GATE_BWD)
-        out = ops.conv2d(b, block._sideBranch[3].packed(), gate_mul=a, gate_id=x, dual_silu=True)
-        sout = ops.silu_twin(out)
-        ctx.save_for_backward(a, b, *saved)
-        ctx.block = block
-        ctx.wgrad_slots = range(2, 1 + len(rest))
-        ctx.mark_non_differentiable(sout)
-        ctx.set_materialize_grads(False)
-        return out, sout
-
-    @staticmethod
-    def backward(ctx, dout, _dsout):
-        block = ctx.block
-        a, b = ctx.saved_tensors[:2]
-        saved = ctx.saved_tensors[2:]
-        ns = _rb_nsaved(block._mainBranch[0])
-        main = [saved[2 * ns * i: 2 * ns * i + ns] for i in range(3)]
-        side = [saved[2 * ns * i + ns: 2 * ns * i + 2 * ns] for i in range(3)]
-        dout = dout.contiguous()
-        c11 = block._sideBranch[3]
-        (h, dbb), = ops.conv2d_gate_bwd([b], [c11.packed()], [a], [dout])     # d a, d (conv1x1 output)
-        g = ops.conv2d(dbb, _dgrad_packed(c11, c11.weight))
-        dw11, db11 = ops.conv2d_wgrad(b, dbb, 1, 1, want_bias=True)
-        pairs = []                                               # appended RB 2, 1, 0; per RB: main (conv1, conv2), side (conv1, conv2)
-        norms = {}                                               # RB index -> [(d gamma, d beta) of main, of side]
-        for i in (2, 1, 0):
-            ng = []
-            h, g = _rb_backward_multi([block._mainBranch[i], block._sideBranch[i]], [main[i], side[i]], [h, g], pairs, norm_grads=ng)
-            norms[i] = ng
-        dx = ops.add3(h, g, dout)
-        grads = _wgrads(pairs)
-        by_rb = {i: grads[4 * k: 4 * k + 4] for k, i in enumerate((2, 1, 0))}
-        flat = []
-        for stack in (0, 1):                                     # main RB 0..2, then side RB 0..2
-            for i in range(3):
-                (dw1, db1), (dw2, db2) = by_rb[i][2 * stack], by_rb[i][2 * stack + 1]
-                flat.extend([dw1, db1, dw2, db2])
-                if norms[i]:
-                    flat.extend(norms[i][stack])
-        return (dx, None, *flat, dw11, db11, None)
+def _attn_backward_multi(layer, saved, dys, pairs, owners, grads):
+    """Input gradients of several AttentionBlocks of one shape: all their gates in one launch, every ResidualBlock layer two."""
+    k = len(layer)
+    a, b, rbsaved = saved
+    c11s = [m._sideBranch[3] for m in layer]
+    gates = ops.conv2d_gate_bwd(b, [c.packed() for c in c11s], a, dys)              # [(d a, d (conv1x1 output))]
+    hs = [h for h, _ in gates]
+    gs = ops.conv2d_multi([dbb for _, dbb in gates], [_dgrad_packed(c, c.weight) for c in c11s])
+    for c11, bi, (_, dbb) in zip(c11s, b, gates):
+        grads[id(c11.weight)], grads[id(c11.bias)] = ops.conv2d_wgrad(bi, dbb, 1, 1, want_bias=True)
+    for i in (2, 1, 0):
+        blocks = [m._mainBranch[i] for m in layer] + [m._sideBranch[i] for m in layer]
+        out = _rb_backward_multi(blocks, rbsaved[i], hs + gs, pairs, owners, grads)
+        hs, gs = out[:k], out[k:]
+    return [ops.add3(h, g, dout) for h, g, dout in zip(hs, gs, dys)]
 
 
-# ---- same-structure stacks in lockstep ------------------------------------------------------------------------------------
-# `latentHead` / `quantizationHead` (RB, AttentionBlock, conv3x3; mcquic/modules/compressor.py:148-160) consume the same z, and
-# `dequantizationHead` / `sideHead` (AttentionBlock, conv3x3, RB; :166-175) are independent until their sum: layer by layer the
-# two stacks are the same shapes on different tensors, so every layer is ONE multi-problem launch for both (four problems inside
-# their AttentionBlocks).  15 + 15 convolutions become 10 launches each way.
-def _kind(m) -> str:
-    name = type(m).__name__
-    if name == "ResidualBlock" and m._skip is None and not getattr(m, "denseNorm", False):
-        return "rb"
-    if name == "AttentionBlock" and not getattr(m, "denseNorm", False):
-        return "attn"
-    if name == "Conv2d" and m.kernelSize == 3 and m.stride == 1:
-        return "conv"
-    raise NotImplementedError(f"lockstep: {name} is not a layer of the paired heads")
-
-
-def lockstep_compatible(stacks) -> bool:
-    try:
-        kinds = [[_kind(m) for m in st] for st in stacks]
-    except NotImplementedError:
-        return False
-    return all(k == kinds[0] for k in kinds[1:])
-
-
-def _lockstep_forward(stacks, xs, keep: bool):
-    """Run the k stacks layer by layer; with `keep` returns the tape backward needs."""
-    k = len(stacks)
-    xs = list(xs)
-    tape = []
-    nlayers = len(stacks[0])
-    for li, layer in enumerate(zip(*stacks)):
-        kind = _kind(layer[0])
-        if kind == "rb":
-            ys, sys_, saved = _rb_forward_multi(list(layer), xs, [_silu_of(x) for x in xs])
-            for y, sy in zip(ys, sys_):
-                ops.set_silu_twin(y, sy)
-            tape.append((kind, layer, saved))
-            xs = ys
-        elif kind == "attn":
-            a, b = list(xs), list(xs)
-            sa = [_silu_of(x) for x in xs]
-            sb = list(sa)
-            saved = []
-            for i in range(3):
-                blocks = [m._mainBranch[i] for m in layer] + [m._sideBranch[i] for m in layer]
-                ys, sys_, sv = _rb_forward_multi(blocks, a + b, sa + sb)
-                a, b, sa, sb = ys[:k], ys[k:], sys_[:k], sys_[k:]
-                saved.append(sv)
-            outs = ops.conv2d_multi(b, [m._sideBranch[3].packed() for m in layer],
-                                    per_problem=[dict(gate_mul=ai, gate_id=xi) for ai, xi in zip(a, xs)], dual_silu=True)
-            tape.append((kind, layer, (a, b, saved)))
-            xs = outs
-        else:
-            # (a conv3x3 in the middle of a head feeds a ResidualBlock: its launch writes the SiLU twin that block starts from)
-            ys = ops.conv2d_multi(xs, [m.packed() for m in layer], dual_silu=li + 1 < nlayers)
-            tape.append((kind, layer, xs))
-            xs = ys
-    return xs, (tape if keep else None)
-
-
-def _lockstep_backward(tape, dys, grads):
-    """Input gradients of the k stacks; parameter gradients go into `grads` (id(parameter) -> tensor)."""
-    dys = [d.contiguous() for d in dys]
-    pairs, owners = [], []                                     # 3x3 weight-gradient operand pairs and the convs they belong to
-    for kind, layer, saved in reversed(tape):
-        k = len(layer)
-        if kind == "rb":
-            before = len(pairs)
-            dys = _rb_backward_multi(list(layer), saved, dys, pairs)
-            for m in layer:
-                owners.extend([m._branch[1], m._branch[3]])
-            assert len(pairs) - before == 2 * k
-        elif kind == "attn":
-            a, b, rbsaved = saved
-            c11s = [m._sideBranch[3] for m in layer]
-            pairs11 = ops.conv2d_gate_bwd(b, [c.packed() for c in c11s], a, dys)        # all stacks' gates in one launch
-            hs = [h for h, _ in pairs11]
-            gs = ops.conv2d_multi([dbb for _, dbb in pairs11], [_dgrad_packed(c, c.weight) for c in c11s])
-            for c11, bi, (_, dbb) in zip(c11s, b, pairs11):
-                dw11, db11 = ops.conv2d_wgrad(bi, dbb, 1, 1, want_bias=True)
-                grads[id(c11.weight)], grads[id(c11.bias)] = dw11, db11
-            for i in (2, 1, 0):
-                blocks = [m._mainBranch[i] for m in layer] + [m._sideBranch[i] for m in layer]
-                out = _rb_backward_multi(blocks, rbsaved[i], hs + gs, pairs)
-                hs, gs = out[:k], out[k:]
-                for blk in blocks:
-                    owners.extend([blk._branch[1], blk._branch[3]])
-            dys = [ops.add3(h, g, dout) for h, g, dout in zip(hs, gs, dys)]
-        else:
-            xs = saved
-            for m, x, dy in zip(layer, xs, dys):
-                pairs.append((x, dy))
-                owners.append(m)
-            dys = ops.conv2d_multi(dys, [_dgrad_packed(m, m.weight) for m in layer])
-    for conv, (dw, db) in zip(owners, _wgrads(pairs)):
+def _wgrads_into(pairs, owners, grads):
+    """(dW, db) of the 3x3 stride-1 convs `owners` from their (input, output-gradient) `pairs`: one grouped launch."""
+    for conv, (dw, db) in zip(owners, ops.conv2d_wgrad_group([a for a, _ in pairs], [b for _, b in pairs], want_bias=True)):
         grads[id(conv.weight)] = dw
         if conv.bias is not None:
             grads[id(conv.bias)] = db
-    return dys
 
 
 def _tape_flatten(obj, tensors):
@@ -597,25 +440,135 @@ def _tape_restore(spec, tensors):
     return spec
 
 
+def _tape_save(ctx, tape):
+    """The taped activations go through ctx.save_for_backward (version-checked, released with the graph, readable by a second
+    backward under retain_graph=True); ctx keeps only the tape's structure."""
+    tensors = []
+    ctx.tape_spec = _tape_flatten(tape, tensors)
+    ctx.save_for_backward(*tensors)
+
+
+def _single_forward(ctx, body, x, sx, rest):
+    """A single node's forward, `body` over one problem: apply(x, silu(x), *parameters, block) -> (y, silu(y)).
+    Unlike LockstepFn, `sx` = silu(x) is an input, so that a producer's twin is reused, and silu(y) is an output, the next block's
+    `sx`: non-differentiable (every consumer differentiates through y itself), and nothing is materialised for its gradient (or
+    autograd fills a zero tensor of its size on every backward)."""
+    block = rest[-1]
+    (y,), saved = body([block], [x], [sx])
+    sy = ops.silu_twin(y)
+    _tape_save(ctx, saved)
+    ctx.block = block
+    ctx.wgrad_slots = range(2, 1 + len(rest))
+    ctx.mark_non_differentiable(sy)
+    ctx.set_materialize_grads(False)
+    return y, sy
+
+
+def _single_backward(ctx, body, params, dy, **options):
+    """A single node's backward: (dx, None, the gradients of `params(block)` in that order -- the order forward received them --, None)."""
+    pairs, owners, grads = [], [], {}
+    (dx,) = body([ctx.block], _tape_restore(ctx.tape_spec, ctx.saved_tensors), [dy.contiguous()], pairs, owners, grads, **options)
+    _wgrads_into(pairs, owners, grads)
+    return (dx, None, *[grads.get(id(p)) for p in params(ctx.block)], None)
+
+
+class ResidualBlockFn(torch.autograd.Function):
+    """y = conv2(act2(conv1(silu(x)))) + x  (mcquic/nn/blocks.py:179-200) as two fused launches each way:
+         forward   t1, silu(t1) = conv1(silu(x))                      (SiLU twin stored by the producing launch)
+                   y,  silu(y)  = conv2(silu(t1)) + x
+         backward  d_t1 = conv(dy, W2^T) * silu'(t1)                   (MCQ_CONV_DSILU_MUL epilogue)
+                   dx   = conv(d_t1, W1^T) * silu'(x) + dy             (... + MCQ_CONV_RESIDUAL: the skip path's gradient)
+                   dW1, db1, dW2, db2: ONE grouped weight-gradient launch over (silu(x), d_t1) and (silu(t1), dy)
+       No stand-alone SiLU / SiLU-backward / add kernels, no channel-major copies.  `denseNorm`: act2 = GroupNorm, parameters +
+       (gamma, beta)."""
+
+    @staticmethod
+    def forward(ctx, x, sx, *rest):
+        return _single_forward(ctx, _rb_forward_multi, x, sx, rest)
+
+    @staticmethod
+    def backward(ctx, dy, _dsy):
+        # (the one node that leaves the input gradient's launch out when x needs none)
+        return _single_backward(ctx, _rb_backward_multi, _rb_params, dy, need_dx=ctx.needs_input_grad[0])
+
+
+class AttentionBlockFn(torch.autograd.Function):
+    """AttentionBlock as ONE autograd node: every ResidualBlock layer is one launch for the main and the side stack each way, and
+    the twelve 3x3 weight gradients of the block leave in ONE grouped launch."""
+
+    @staticmethod
+    def forward(ctx, x, sx, *rest):
+        return _single_forward(ctx, _attn_forward_multi, x, sx, rest)
+
+    @staticmethod
+    def backward(ctx, dout, _dsout):
+        return _single_backward(ctx, _attn_backward_multi, _attn_params, dout)
+
+
+def lockstep_kind(m) -> Optional[str]:
+    """What a layer of the paired heads is to the lockstep walks (here and nn/blocks.py's inference one), or None for a module they
+    do not take: normalised and width-changing blocks run on their own."""
+    name = type(m).__name__
+    if name == "ResidualBlock" and m._skip is None and not getattr(m, "denseNorm", False):
+        return "rb"
+    if name == "AttentionBlock" and not getattr(m, "denseNorm", False):
+        return "attn"
+    if name == "Conv2d" and m.kernelSize == 3 and m.stride == 1:
+        return "conv"
+    return None
+
+
+def lockstep_compatible(stacks) -> bool:
+    kinds = [[lockstep_kind(m) for m in st] for st in stacks]
+    return None not in kinds[0] and all(k == kinds[0] for k in kinds[1:])
+
+
+def _lockstep_forward(stacks, xs):
+    """Run the k stacks layer by layer; returns the outputs and the tape backward needs."""
+    xs = list(xs)
+    tape = []
+    nlayers = len(stacks[0])
+    for li, layer in enumerate(zip(*stacks)):
+        kind = lockstep_kind(layer[0])
+        if kind == "conv":
+            # (a conv3x3 in the middle of a head feeds a ResidualBlock: its launch writes the SiLU twin that block starts from)
+            ys, saved = ops.conv2d_multi(xs, [m.packed() for m in layer], dual_silu=li + 1 < nlayers), xs
+        else:
+            ys, saved = (_rb_forward_multi if kind == "rb" else _attn_forward_multi)(list(layer), xs, [_silu_of(x) for x in xs])
+        tape.append((kind, layer, saved))
+        xs = ys
+    return xs, tape
+
+
+def _lockstep_backward(tape, dys, grads):
+    """Input gradients of the k stacks; parameter gradients go into `grads` (id(parameter) -> tensor)."""
+    dys = [d.contiguous() for d in dys]
+    pairs, owners = [], []                                     # 3x3 weight-gradient operand pairs and the convs they belong to
+    for kind, layer, saved in reversed(tape):
+        if kind == "conv":
+            pairs.extend(zip(saved, dys))
+            owners.extend(layer)
+            dys = ops.conv2d_multi(dys, [_dgrad_packed(m, m.weight) for m in layer])
+        else:
+            dys = (_rb_backward_multi if kind == "rb" else _attn_backward_multi)(list(layer), saved, dys, pairs, owners, grads)
+    _wgrads_into(pairs, owners, grads)
+    return dys
+
+
 class LockstepFn(torch.autograd.Function):
     """k same-structure stacks (nn.Sequential of ResidualBlock / AttentionBlock / conv3x3) on k inputs as ONE autograd node.
     apply(x_1 .. x_k, *parameters (all stacks', in `stack.parameters()` order), stacks) -> (y_1 .. y_k).
-    The taped activations go through ctx.save_for_backward (version-checked, released with the graph, readable by a second
-    backward under retain_graph=True); ctx keeps only the tape's structure."""
+    Unlike the single nodes it finds silu(x_i) itself (`_silu_of`) and returns the y_i alone (they carry their twins)."""
 
     @staticmethod
     def forward(ctx, *args):
         stacks, shared = args[-1]
         k = len(stacks)
         ctx.shared = shared
-        # (`shared`: ONE input feeds all k stacks -- latentHead / quantizationHead on the same z: its k gradients are summed here,
-        #  by this library's add, instead of by the autograd engine)
-        ys, tape = _lockstep_forward(stacks, args[:1] * k if shared else args[:k], keep=True)
-        tensors = []
-        ctx.tape_spec = _tape_flatten([(kind, saved) for kind, _, saved in tape], tensors)
+        ys, tape = _lockstep_forward(stacks, args[:1] * k if shared else args[:k])
+        _tape_save(ctx, [(kind, saved) for kind, _, saved in tape])
         ctx.layers = [layer for _, layer, _ in tape]
-        ctx.save_for_backward(*tensors)
-        ctx.stacks, ctx.k = stacks, k
+        ctx.stacks = stacks
         ctx.wgrad_slots = range(1 if shared else k, len(args) - 1)
         return tuple(ys)
 
@@ -627,6 +580,8 @@ class LockstepFn(torch.autograd.Function):
         dxs = _lockstep_backward(tape, list(dys), grads)
         params = [p for st in ctx.stacks for p in st.parameters()]
         if ctx.shared:
+            # (`shared`: ONE input feeds all k stacks -- latentHead / quantizationHead on the same z: its k gradients are summed
+            #  here, by this library's add, instead of by the autograd engine)
             dx = dxs[0]
             for i in range(1, len(dxs) - 1, 2):
                 dx = ops.add3(dx, dxs[i], dxs[i + 1])
@@ -935,12 +890,7 @@ def _silu_of(x: torch.Tensor) -> torch.Tensor:
 
 def attention_block(x, block):
     """AttentionBlock in the training graph (AttentionBlockFn)."""
-    params = []
-    for stack in (block._mainBranch, block._sideBranch):
-        for i in range(3):
-            params.extend(_rb_params(stack[i]))
-    c11 = block._sideBranch[3]
-    out, sout = AttentionBlockFn.apply(x, _silu_of(x), *params, c11.weight, c11.bias, block)
+    out, sout = AttentionBlockFn.apply(x, _silu_of(x), *_attn_params(block), block)
     ops.set_silu_twin(out, sout)
     return out
 

@@ -1,5 +1,7 @@
 """GPU: backward kernels of the training step against torch.autograd on the CPU (the same formulas the reference
 gets from autograd over nn.Conv2d / SiLU / GDN / sigmoid)."""
+import functools
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -231,6 +233,146 @@ def test_blocks_backward(dev, c):
             want = params[name].grad
             assert want is not None, name
             _close(p.grad, want, 2e-5, f"{type(mod).__name__} d{name}")
+
+
+HEAD_RB_ATTN_CONV = ("rb", "attn", "conv")       # latentHead / quantizationHead (oracle: head_rb_attn_conv)
+HEAD_ATTN_CONV_RB = ("attn", "conv", "rb")       # dequantizationHead / sideHead (oracle: head_attn_conv_rb)
+_HEAD_C = 8                                      # with the 2 x c x 8 x 12 input: test_blocks_backward's shape (tile remainders in both map axes)
+
+
+def _head_state(order, seed):
+    """The oracle's state_dict of one head: layer i under the prefix `i.`."""
+    sd = {}
+    for i, kind in enumerate(order):
+        if kind == "conv":
+            R._conv_params(sd, f"{i}.", _HEAD_C, _HEAD_C, 3, seed)
+        else:
+            (R._rb if kind == "rb" else R._attn)(sd, f"{i}.", _HEAD_C, seed)
+    return sd
+
+
+def _head_modules(order, sds, dev):
+    from mcquic_amd import nn as N
+    make = {"rb": lambda: N.ResidualBlock(_HEAD_C, _HEAD_C), "attn": lambda: N.AttentionBlock(_HEAD_C), "conv": lambda: N.conv3x3(_HEAD_C, _HEAD_C)}
+    stacks = []
+    for sd in sds:
+        stack = torch.nn.Sequential(*[make[kind]() for kind in order])
+        stack.load_state_dict(sd, strict=True)
+        stacks.append(stack.to(dev).train())
+    return stacks
+
+
+@functools.lru_cache(maxsize=None)
+def _heads_reference(order, shared):
+    """Two heads of `order` on one shared input or on two inputs through the oracle on the CPU, with every gradient of
+    sum_j <y_j, G_j>.  Computed once, read by the tests below."""
+    fn = R.head_rb_attn_conv if order == HEAD_RB_ATTN_CONV else R.head_attn_conv_rb
+    sds = [_head_state(order, 9 + j) for j in range(2)]
+    xs = [_rand((2, _HEAD_C, 8, 12), 5 + (0 if shared else j)) for j in range(2)]
+    xr = [x.clone().requires_grad_() for x in (xs[:1] if shared else xs)]
+    leaves = [{k: v.clone().requires_grad_() for k, v in sd.items()} for sd in sds]
+    ys = [fn(leaf, "", xr[0 if shared else j]) for j, leaf in enumerate(leaves)]
+    gys = [_rand(tuple(y.shape), 6 + j) for j, y in enumerate(ys)]
+    torch.autograd.backward(ys, gys)
+    return dict(sds=sds, xs=xs, gys=gys, ys=[y.detach() for y in ys], dxs=[x.grad for x in xr],
+                grads=[{k: v.grad for k, v in leaf.items()} for leaf in leaves])
+
+
+def _run_heads(stacks, ref, shared, dev, run):
+    """(outputs, input gradients, [name -> parameter gradient] per stack) of `run(stacks, inputs)` on the reference's inputs."""
+    for st in stacks:
+        for p in st.parameters():
+            p.grad = None
+    xd = [x.to(dev).requires_grad_() for x in (ref["xs"][:1] if shared else ref["xs"])]
+    ys = run(stacks, [xd[0], xd[0]] if shared else xd)
+    torch.autograd.backward(ys, [g.to(dev) for g in ref["gys"]])
+    return ys, [x.grad for x in xd], [{n: p.grad.clone() for n, p in st.named_parameters()} for st in stacks]
+
+
+@pytest.mark.parametrize("order,shared", [(HEAD_RB_ATTN_CONV, True), (HEAD_ATTN_CONV_RB, False)], ids=["rb-attn-conv-shared", "attn-conv-rb"])
+def test_lockstep_heads_against_the_oracle(dev, order, shared):
+    """The paired heads as ONE autograd node (autograd.lockstep): two (ResidualBlock, AttentionBlock, conv3x3) stacks on one
+    shared input -- its two gradients are summed inside the node -- and two (AttentionBlock, conv3x3, ResidualBlock) stacks on
+    two inputs: outputs, input gradients and every parameter gradient against CPU autograd through the oracle, at
+    test_blocks_backward's bars; a head that ends in a block hands silu(out) on as its twin."""
+    from mcquic_amd import autograd as AG, ops
+    ref = _heads_reference(order, shared)
+    stacks = _head_modules(order, ref["sds"], dev)
+    ys, dxs, grads = _run_heads(stacks, ref, shared, dev, AG.lockstep)
+    assert all(type(y.grad_fn).__name__ == "LockstepFnBackward" for y in ys)
+    for j, (y, want) in enumerate(zip(ys, ref["ys"])):
+        _close(y, want, 5e-6, f"stack {j} forward")
+        if order[-1] != "conv":                  # (whatever follows a head's closing block starts with an activation)
+            tw = ops.silu_twin(y)
+            assert tw is not None and tw.grad_fn is None and not tw.requires_grad
+            assert torch.equal(tw, ops.silu(y.detach()))
+    for j, (dx, want) in enumerate(zip(dxs, ref["dxs"])):
+        _close(dx, want, 2e-5, f"dx {j}")
+    for j, (got, want) in enumerate(zip(grads, ref["grads"])):
+        assert set(got) == set(want)
+        for name in want:
+            _close(got[name], want[name], 2e-5, f"stack {j} d{name}")
+
+
+def test_single_nodes_equal_lockstep_of_the_same_blocks(dev):
+    """The same two (AttentionBlock, conv3x3, ResidualBlock) stacks once in lockstep and once stack by stack through the single
+    nodes (nn.blocks.run_stack): the outputs are the same bits -- a multi-problem launch computes each problem as its single launch
+    does --, the gradients agree within test_blocks_backward's bar (a grouped weight-gradient launch plans its pixel splits by group
+    size, so its sums may run in another order)."""
+    from mcquic_amd import autograd as AG
+    from mcquic_amd.nn import blocks
+    ref = _heads_reference(HEAD_ATTN_CONV_RB, False)
+    stacks = _head_modules(HEAD_ATTN_CONV_RB, ref["sds"], dev)
+    ys, dxs, grads = _run_heads(stacks, ref, False, dev, AG.lockstep)
+    ys1, dxs1, grads1 = _run_heads(stacks, ref, False, dev, lambda sts, xs: [blocks.run_stack(st, x) for st, x in zip(sts, xs)])
+    assert all(type(y.grad_fn).__name__ == "ResidualBlockFnBackward" for y in ys1)
+    for j in range(2):
+        assert torch.equal(ys1[j], ys[j]), f"stack {j} forward"
+        _close(dxs1[j], dxs[j].cpu(), 2e-5, f"dx {j}")
+        for name, want in grads[j].items():
+            _close(grads1[j][name], want.cpu(), 2e-5, f"stack {j} d{name}")
+
+
+@pytest.mark.parametrize("groups", [2, 8])
+def test_dense_norm_attention_block_against_the_oracle(dev, groups):
+    """AttentionBlock(c, groups, denseNorm=True) in training mode (one autograd node, GroupNorm where the second activation was):
+    forward and every gradient against CPU autograd through the oracle's normalised blocks (oracle/neon_ref.py), at 2 x 8 x 8 x 12
+    with several channels per group and with one.  Bars: those of test_neon.py's small denseNorm case -- forward 1e-4 absolute,
+    gradients NEON_GRAD_BAR[("small", True)] (4x what was measured there), taken as there against the larger of the tensor's
+    own largest entry and 1e-3 of the largest gradient of all: a conv bias in front of a one-channel-per-group GroupNorm has a
+    structurally zero gradient, both sides hold rounding noise."""
+    from oracle import neon_ref as NR
+    from test_neon import NEON_GRAD_BAR
+    from mcquic_amd import nn as N
+    c = _HEAD_C
+    sd = {}
+    NR._DENSE_NORM[0] = True
+    try:
+        NR._attn(sd, "", c, 9)
+    finally:
+        NR._DENSE_NORM[0] = False
+    params = {k: v.clone().requires_grad_() for k, v in sd.items()}
+    x = _rand((2, c, 8, 12), 5)
+    xr = x.clone().requires_grad_()
+    y = NR.attention_block(params, "", xr, groups)
+    gy = _rand(tuple(y.shape), 6)
+    y.backward(gy)
+    mod = N.AttentionBlock(c, groups, denseNorm=True)
+    mod.load_state_dict(sd, strict=True)
+    mod = mod.to(dev).train()
+    xd = x.to(dev).requires_grad_()
+    yd = mod(xd)
+    assert type(yd.grad_fn).__name__ == "AttentionBlockFnBackward"
+    assert float((yd.detach().cpu() - y.detach()).abs().max()) <= 1e-4
+    yd.backward(gy.to(dev))
+    bar = NEON_GRAD_BAR[("small", True)]
+    scale = max(float(v.grad.abs().max()) for v in params.values())
+    named = dict(mod.named_parameters())
+    assert set(named) == set(params)
+    for name, got, want in [("x", xd.grad, xr.grad)] + [(n, p.grad, params[n].grad) for n, p in named.items()]:
+        assert got is not None and torch.isfinite(got).all(), name
+        rel = (got.detach().cpu() - want).abs().max().item() / max(want.abs().max().item(), 1e-3 * scale, 1e-6)
+        assert rel < bar, f"d{name}: {rel:.3e}"
 
 
 def _train_setup(ch, m, ks, n, hw, seed):
