@@ -351,6 +351,9 @@ __global__ void vq_dequant_soft_kernel(const int64_t* __restrict__ index, const 
 // One wave per latent vector.  y = softmax(logit + gumbel) is recomputed from the saved (post-drop) logits and the
 // gumbel draw; dS[k] = <dDeq_v, c_k> comes in and is overwritten by d dist[k]:
 //   dz = y (dS - <y, dS>)            (straight-through: the gradient reaches the sample through y_soft only)
+// evaluated as y ((dS - r) - <y, dS - r>) with r = dS at the row's arg-max, the same number since sum y = 1: where one entry holds
+// nearly all of the row (y -> 1), dS - <y, dS> of that entry is a difference of nearly equal numbers, and float32 left it -- the
+// row's LARGEST d dist -- with a relative error of 6e-8 / (1 - y); with r taken out that entry's term is -<y, dS - r> over the others.
 //   d dist = dz * (-Tb / sqrt(k)),   d Tb += sum_k dz[k] * logit[k] / Tb,   rowsum = sum_k d dist[k]
 __global__ __launch_bounds__(256) void vq_softmax_bwd_kernel(const float* __restrict__ logits, const float* __restrict__ u_gumbel,
                                                              const unsigned long long* __restrict__ rng_state,
@@ -374,30 +377,35 @@ __global__ __launch_bounds__(256) void vq_softmax_bwd_kernel(const float* __rest
     const float* dl = dlogits ? dlogits + (size_t)row * k : nullptr;
     const float* rw = raw_logits ? raw_logits + (size_t)row * k : nullptr;
     const float eps = 1.1920928955078125e-07f;
-    float mx = -INFINITY;
+    float mx = -INFINITY, ref = 0.0f;
     for (int c = lane; c < k; c += 64) {
         const float u = fminf(fmaxf(MCQ_U(ug, 1u, c), eps), 1.0f - eps);
-        mx = fmaxf(mx, lr[c] + gumbel_noise(u));
+        const float y = lr[c] + gumbel_noise(u);
+        if (y > mx) { mx = y; ref = dr[c]; }
     }
+    // (equal maxima: the larger dS, so that every lane ends with the same pair)
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) mx = fmaxf(mx, __shfl_xor(mx, off));
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float om = __shfl_xor(mx, off), orf = __shfl_xor(ref, off);
+        if (om > mx || (om == mx && orf > ref)) { mx = om; ref = orf; }
+    }
     float sum = 0.0f, dot = 0.0f;
     for (int c = lane; c < k; c += 64) {
         const float u = fminf(fmaxf(MCQ_U(ug, 1u, c), eps), 1.0f - eps);
         const float e = exp_nonpos((lr[c] + gumbel_noise(u)) - mx);
         sum += e;
-        dot += e * dr[c];
+        dot += e * (dr[c] - ref);
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) { sum += __shfl_xor(sum, off); dot += __shfl_xor(dot, off); }
     const float inv = 1.0f / sum;
-    dot *= inv;                                   // <y, dS>
+    dot *= inv;                                   // <y, dS - r>
     float rs = 0.0f, dt = 0.0f;
     const float dscale = -tb / scale;
     for (int c = lane; c < k; c += 64) {
         const float u = fminf(fmaxf(MCQ_U(ug, 1u, c), eps), 1.0f - eps);
         const float y = exp_nonpos((lr[c] + gumbel_noise(u)) - mx) * inv;
-        float dz = y * (dr[c] - dot);
+        float dz = y * ((dr[c] - ref) - dot);
         if (dl) {
             dz += dl[c];
             dt += dz * (rw[c] / tb);
@@ -425,8 +433,16 @@ __global__ __launch_bounds__(256) void vq_dx_kernel(const float* __restrict__ dd
     const float* cg = cb + (size_t)g * k * d;
     const float rs = rowsum[row];
     for (int j = lane; j < d; j += 64) {
+        // (in runs of 64 codewords: one chain over all k lets every term round at the size of the whole partial sum; with a gradient
+        //  on the logits -- k terms of like size and random sign -- dx at k = 8193 was 2.3e-6 of its largest entry off float64 where
+        //  the float32 reference is 2.7e-7 off, and is 3.0e-7 off in runs: tests/test_gpu_soft_assign_leaf.py, test_soft_quantize_chain)
         float acc = 0.0f;
-        for (int c = 0; c < k; ++c) acc = __builtin_fmaf(dr[c], cg[(size_t)c * d + j], acc);
+        for (int c0 = 0; c0 < k; c0 += 64) {
+            const int c1 = c0 + 64 < k ? c0 + 64 : k;
+            float part = 0.0f;
+            for (int c = c0; c < c1; ++c) part = __builtin_fmaf(dr[c], cg[(size_t)c * d + j], part);
+            acc += part;
+        }
         const size_t xi = ((size_t)ng * d + j) * hw + pix;
         dx[xi] = 2.0f * x[xi] * rs - 2.0f * acc;
     }
@@ -514,19 +530,26 @@ __device__ __forceinline__ void row_sum2(float& a, float& b, RowShared<T>& sm, c
     }
 }
 
+// the row's maximum `a` and the value `r` that travels with it (equal maxima: the larger r, so that every thread gets the same
+// pair); slots 0 / 1 of the shared scratch
 template <int T>
-__device__ __forceinline__ float row_max(float a, RowShared<T>& sm) {
+__device__ __forceinline__ void row_max_with(float& a, float& r, RowShared<T>& sm) {
 #pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) a = fmaxf(a, __shfl_xor(a, off));
+    for (int off = 32; off >= 1; off >>= 1) {
+        const float oa = __shfl_xor(a, off), orr = __shfl_xor(r, off);
+        if (oa > a || (oa == a && orr > r)) { a = oa; r = orr; }
+    }
     if constexpr (T > 64) {
         const int wave = threadIdx.x >> 6;
-        if ((threadIdx.x & 63) == 0) sm.v[0][wave] = a;
+        if ((threadIdx.x & 63) == 0) { sm.v[0][wave] = a; sm.v[1][wave] = r; }
         __syncthreads();
-        a = sm.v[0][0];
+        a = sm.v[0][0]; r = sm.v[1][0];
 #pragma unroll
-        for (int w = 1; w < T / 64; ++w) a = fmaxf(a, sm.v[0][w]);
+        for (int w = 1; w < T / 64; ++w) {
+            const float oa = sm.v[0][w], orr = sm.v[1][w];
+            if (oa > a || (oa == a && orr > r)) { a = oa; r = orr; }
+        }
     }
-    return a;
 }
 
 // (two 1024-thread workgroups per CU = eight waves per SIMD = 64 registers: with one, the load / arithmetic / reduction phases of a row -- separated by
@@ -628,22 +651,23 @@ __global__ __launch_bounds__(T < 256 ? 256 : T, T == 1024 ? 8 : 1) void vq_softm
         const bool ok = c < k;
         l[e] = ok ? lr[c] : -INFINITY; y[e] = ok ? MCQ_U(ug, 1u, c) : 0.5f; dd[e] = ok ? dr[c] : 0.0f;
     }
-    float mx = -INFINITY;
+    float mx = -INFINITY, ref = 0.0f;                            // ref: dS at the row's arg-max (see vq_softmax_bwd_kernel)
 #pragma unroll
     for (int e = 0; e < ROW_E; ++e) {
         const float u = fminf(fmaxf(y[e], eps), 1.0f - eps);
         y[e] = l[e] + gumbel_noise(u);                           // (-inf beyond the row)
-        mx = fmaxf(mx, y[e]);
+        if (y[e] > mx) { mx = y[e]; ref = dd[e]; }
     }
-    mx = row_max<T>(mx, sm);
+    row_max_with<T>(mx, ref, sm);
     float sum = 0.0f, dot = 0.0f;
 #pragma unroll
     for (int e = 0; e < ROW_E; ++e) {
         y[e] = tid + T * e < k ? exp_nonpos(y[e] - mx) : 0.0f;
+        dd[e] -= ref;
         sum += y[e];
         dot += y[e] * dd[e];
     }
-    row_sum2<T>(sum, dot, sm, 1);
+    row_sum2<T>(sum, dot, sm, 2);                                // (slots 0 / 1 may still be read by a slower wave's maximum)
     const float inv = 1.0f / sum;
     dot *= inv;
     float rs = 0.0f, dt = 0.0f;
@@ -662,8 +686,7 @@ __global__ __launch_bounds__(T < 256 ? 256 : T, T == 1024 ? 8 : 1) void vq_softm
             rs += dv;
         }
     }
-    if constexpr (T > 64) __syncthreads();                       // (slot 1 / 2 of the scratch are read by the sum above: reuse 2 / 3)
-    row_sum2<T>(rs, dt, sm, 2);
+    row_sum2<T>(rs, dt, sm, 0);                                  // (every wave has left the maximum's slots: it passed the sum's barrier)
     if (tid == 0) { rowsum[row] = rs; dtrow[row] = dt; }
 }
 

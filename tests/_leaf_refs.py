@@ -1,5 +1,6 @@
-"""Inputs and references for the leaf kernels of the training step (tests/test_gpu_leaf_ops.py holds the HIP kernels to them,
-tests/test_leaf_ops_reference.py holds the float32 restatements to float64 autograd on the CPU).  Nothing here imports
+"""Inputs and references for the leaf kernels of the training step (tests/test_gpu_leaf_ops.py and, for the training quantizer's
+soft assignment, tests/test_gpu_soft_assign_leaf.py hold the HIP kernels to them, tests/test_leaf_ops_reference.py holds the
+float32 restatements to float64 autograd on the CPU and soft_bwd64 to the oracle's own derivative).  Nothing here imports
 mcquic_amd: every reference is the mathematics, written with torch on the CPU.
 
 Two kinds of reference per op:
@@ -268,3 +269,109 @@ def views_of(t):
         assert torch.equal(v, t), name
     assert out[-1][1].storage_offset() == 1
     return out
+
+
+# ---- soft assignment of the training quantizer: Gumbel soft-max backward, <dDeq, c_k> ---------------------------------------------------
+EPS_F32 = float(torch.finfo(F32).eps)
+TINY = 1e-300                                                        # keeps 0 / 0 out of a relative error whose scale is exactly zero
+
+
+def row_tb(temperature, bound, m, hw, rows, dtype):
+    """max(T_g, bound) of every row, g = (row / hw) % m; `bound` as the float32 a `float` kernel argument receives."""
+    g = (torch.arange(rows) // hw) % m
+    return torch.maximum(temperature.reshape(-1).to(dtype)[g], f32(bound).to(dtype))
+
+
+def soft_bwd64(post_logits, raw_logits, u_gumbel, ds, dlogits, temperature, bound, m, hw):
+    """(d dist [.., k], rowsum [..], dtrow [..]) of one soft assignment from float64 autograd through the mathematics:
+        tb = max(T_g, bound) per ROW, a leaf of its own per row, so that its gradient is the row's temperature term
+        raw = (-dist / sqrt(k)) tb, dist a leaf (its value follows from the given raw logits)
+        p = post + (raw - raw.detach()): the random drop adds a constant; the given float32 post-drop values are used exactly
+        y = softmax(p - log(-log(clamp(u, eps32, 1 - eps32)))),   loss = sum y dS (+ sum p dlogits)
+    `raw_logits`: the logits before the drop, always (a kernel may be handed less).  rowsum = sum_k d dist[k]."""
+    k = post_logits.shape[-1]
+    post, raw0 = post_logits.double().reshape(-1, k), raw_logits.double().reshape(-1, k)
+    rows = post.shape[0]
+    tb = row_tb(temperature, bound, m, hw, rows, torch.float64).clone().requires_grad_()
+    root = torch.tensor(float(k), dtype=torch.float64).sqrt()
+    dist = (-raw0 * root / tb.detach()[:, None]).requires_grad_()
+    raw = (-dist / root) * tb[:, None]
+    p = post + (raw - raw.detach())
+    gumbel = -torch.log(-torch.log(u_gumbel.double().reshape(-1, k).clamp(EPS_F32, 1.0 - EPS_F32)))
+    y = torch.softmax(p + gumbel, -1)
+    loss = (y * ds.double().reshape(-1, k)).sum()
+    if dlogits is not None:
+        loss = loss + (p * dlogits.double().reshape(-1, k)).sum()
+    loss.backward()
+    lead = post_logits.shape[:-1]
+    return dist.grad.reshape(post_logits.shape), dist.grad.sum(-1).reshape(lead), tb.grad.reshape(lead)
+
+
+def soft_bwd_f32(post_logits, raw_logits, u_gumbel, ds, dlogits, temperature, bound, m, hw):
+    """The same three results from the backward formulas written out, every operation in float32 (sums by torch.sum):
+        dz = y (dS - <y, dS>) (+ dlogits),  d dist = dz (-tb / sqrt(k)),  dtrow = sum_k dz raw / tb,  rowsum = sum_k d dist."""
+    k = post_logits.shape[-1]
+    post, raw, dsv = post_logits.reshape(-1, k), raw_logits.reshape(-1, k), ds.reshape(-1, k)
+    assert post.dtype == F32 and raw.dtype == F32 and dsv.dtype == F32 and u_gumbel.dtype == F32
+    tb = row_tb(temperature, bound, m, hw, post.shape[0], F32)[:, None]
+    u = u_gumbel.reshape(-1, k).clamp(EPS_F32, 1.0 - EPS_F32)
+    z = post + -torch.log(-torch.log(u))
+    e = torch.exp(z - z.max(-1, keepdim=True)[0])
+    inv = 1.0 / e.sum(-1, keepdim=True)
+    dot = (e * dsv).sum(-1, keepdim=True) * inv
+    dz = (e * inv) * (dsv - dot)
+    if dlogits is not None:
+        dz = dz + dlogits.reshape(-1, k)
+    dd = dz * (-tb / torch.tensor(float(k), dtype=torch.float64).sqrt().to(F32))
+    dt = (dz * (raw / tb)).sum(-1)
+    lead = post_logits.shape[:-1]
+    return dd.reshape(post_logits.shape), dd.sum(-1).reshape(lead), dt.reshape(lead)
+
+
+def soft_bwd_scales64(ddist64, raw_logits, temperature, bound, m, hw):
+    """What the three results are accurate relative to: d dist to the largest |d dist| of its row; rowsum -- a sum that cancels,
+    analytically to zero without dlogits -- to sum_k |d dist[k]|; dtrow, which cancels the same way, to sum_k |dz[k] raw[k] / tb|."""
+    k = ddist64.shape[-1]
+    dd, raw = ddist64.reshape(-1, k), raw_logits.double().reshape(-1, k)
+    tb = row_tb(temperature, bound, m, hw, dd.shape[0], torch.float64)[:, None]
+    dz = dd / (-tb / torch.tensor(float(k), dtype=torch.float64).sqrt())
+    lead = ddist64.shape[:-1]
+    return (dd.abs().max(-1, keepdim=True)[0].reshape(lead + (1,)), dd.abs().sum(-1).reshape(lead), (dz * raw / tb).abs().sum(-1).reshape(lead))
+
+
+def scaled_err(got, want64, scale64, where=None):
+    """max |got - want| / scale (over the rows `where` selects)."""
+    assert torch.isfinite(got).all(), "non-finite result"
+    err = (got.double() - want64).abs() / scale64.clamp_min(TINY)
+    if where is not None:
+        err = err[where]
+    return float(err.max())
+
+
+def soft_bwd_errs(got, want64, scales64, dtrow_rows=None):
+    """(d dist, rowsum, dtrow) errors of a result triple in the scales above; `dtrow_rows`: the rows whose dtrow counts."""
+    return (scaled_err(got[0], want64[0], scales64[0]), scaled_err(got[1], want64[1], scales64[1]),
+            scaled_err(got[2], want64[2], scales64[2], dtrow_rows))
+
+
+def inner64(x, codebook):
+    """<x_v, c_k> -> [n, m, h, w, k] in float64, x [n, m d, h, w], codebook [m, k, d]."""
+    m, k, d = codebook.shape
+    n, _, h, w = x.shape
+    return torch.einsum("ngdhw,gkd->nghwk", x.double().reshape(n, m, d, h, w), codebook.double())
+
+
+def inner_scale64(x, codebook):
+    """sum_j |x_j c_kj|: what a d-term inner product is accurate relative to."""
+    return inner64(x.abs(), codebook.abs())
+
+
+def inner_f32(x, codebook):
+    """The inner product as a float32 chain in channel order, product and addition rounded separately."""
+    m, k, d = codebook.shape
+    n, _, h, w = x.shape
+    xv = x.reshape(n, m, d, h, w)
+    acc = torch.zeros((n, m, h, w, k), dtype=F32)
+    for j in range(d):
+        acc = acc + xv[:, :, j, :, :, None] * codebook[None, :, None, None, :, j]
+    return acc

@@ -2,6 +2,7 @@
 backward formula (tests/_leaf_refs.py, `*_f32`) must agree with float64 torch.autograd through the FORWARD formula on the same
 special-value inputs the GPU tests use -- a wrong restatement would otherwise bless a wrong kernel -- and the soundness walk of
 mcquic_amd.autograd in front of a deferred backward is exercised on CPU graphs."""
+import pytest
 import torch
 
 import _leaf_refs as R
@@ -138,3 +139,93 @@ def test_deferral_walk_refuses_shared_and_derived_weights():
     assert ok([_Defers.apply(x, w.detach(), b).sum()])                                # a frozen weight has no edge at all
     w.grad = torch.zeros(4)
     assert not ok([_Defers.apply(x, w, b).sum()])                                     # accumulation onto an existing .grad
+
+
+# ---- soft assignment: the float64 reference is the oracle's own derivative ----------------------------------------------------------------
+def _oracle_soft_case(k, seed):
+    """Float64 inputs of one level: (x, codebook, temperature [m,1,1,1] with group 1 below `bound`, bound, freq, u_drop, u_gumbel,
+    dS, W) on 30 latent vectors (n, m, h, w = 2, 3, 1, 5).  The Gumbel draw is float32's grid clamped to [eps32, 1 - eps32]: the
+    oracle in float64 would clamp at float64's eps where soft_bwd64 clamps at float32's, as the kernels do."""
+    m, d, n, h, w = 3, 4, 2, 1, 5
+    g = torch.Generator().manual_seed(seed)
+    cb = (torch.randn((m, k, d), generator=g) * (2 / (5 * d)) ** 0.5).double()
+    x = (torch.randn((n, m * d, h, w), generator=g) * 0.5).double()
+    temp = torch.tensor([1.3, 0.2, 0.8], dtype=torch.float64).reshape(m, 1, 1, 1)
+    freq = (torch.rand((m, k), generator=g) ** 3 + 1e-3) * (torch.rand((m, k), generator=g) < 0.5)      # half the codes unused: the
+    freq = (freq / freq.sum(-1, keepdim=True)).double()                  # drop's exponent grows, a fifth of the entries is dropped
+    shape = (n, m, h, w, k)
+    u1 = torch.rand(shape, generator=g).double()
+    u2 = torch.rand(shape, generator=g).clamp(R.EPS_F32, 1.0 - R.EPS_F32).double()
+    ds = (torch.randn(shape, generator=g) * 0.1).double()
+    wl = ((torch.rand(shape, generator=g) - 0.5) * 0.05).double()
+    return x, cb, temp, 0.5, freq, u1, u2, ds, wl, m, h * w
+
+
+@pytest.mark.parametrize("with_dlogits", [False, True])
+@pytest.mark.parametrize("k", [8, 65, 513])
+def test_soft_bwd64_is_the_oracles_own_derivative(monkeypatch, k, with_dlogits):
+    """oracle.mcquic_ref's vq_logit -> random_drop -> gumbel_softmax_hard in float64 with loss sum sample dS (+ sum logit W): its
+    autograd gradients with respect to the distance and to max(temperature, bound) -- per group: the temperature's own where it is
+    above the bound, the bound's where it is not -- equal R.soft_bwd64's d dist and the group sums of its dtrow to 1e-12 of the
+    largest value.  That ties the reference of tests/test_gpu_soft_assign_leaf.py to the oracle, which test_oracle_vs_reference.py
+    ties to the reference implementation."""
+    from oracle import mcquic_ref as O
+    x, cb, temp, bound, freq, u1, u2, ds, wl, m, hw = _oracle_soft_case(k, 700 + k)
+    seen = []
+    distance = O.vq_distance
+
+    def kept(*a):
+        out = distance(*a)
+        out.retain_grad()
+        seen.append(out)
+        return out
+
+    monkeypatch.setattr(O, "vq_distance", kept)
+    x.requires_grad_()
+    temp.requires_grad_()
+    bnd = torch.tensor([bound], dtype=torch.float64, requires_grad=True)
+    raw = O.vq_logit(x, cb, temp, bnd)
+    post = O.random_drop(raw, freq, u1)
+    assert 0.05 < float((post < -1e8).double().mean()) < 0.5              # the drop is there, and is not everything
+    sample, _, _ = O.gumbel_softmax_hard(post, u2)
+    loss = (sample * ds).sum() + ((post * wl).sum() if with_dlogits else 0.0)
+    loss.backward()
+    (dist,) = seen
+    dd, rowsum, dtrow = R.soft_bwd64(post.detach(), raw.detach(), u2, ds, wl if with_dlogits else None, temp.detach(), bound, m, hw)
+    assert float((dd - dist.grad).abs().max()) <= 1e-12 * float(dist.grad.abs().max())
+    assert float((rowsum - dist.grad.sum(-1)).abs().max()) <= 1e-12 * float(dist.grad.abs().sum(-1).max())
+    per_group = dtrow.sum((0, 2, 3))                                      # [n, m, h, w] -> [m]
+    want = torch.stack([temp.grad.reshape(-1)[0], bnd.grad[0], temp.grad.reshape(-1)[2]])
+    assert float(temp.grad.reshape(-1)[1]) == 0.0                         # group 1 sits below the bound
+    assert float((per_group - want).abs().max()) <= 1e-12 * float(want.abs().max())
+
+
+@pytest.mark.parametrize("k", [8, 65, 513])
+def test_soft_bwd_restatement(k):
+    """R.soft_bwd_f32 (the backward formulas, float32 throughout) against R.soft_bwd64 (autograd, float64) on float32 inputs, in
+    the scales of R.soft_bwd_scales64.  Bar: 8 (k + 64) 2^-24 -- k 2^-24 is the worst-case bound of a k-term float32 sum relative to
+    the sum of its terms' magnitudes, 64 2^-24 stands for the soft-max's exponent (|logit + noise - max| <= 40, rounded at that
+    size, is that much relative error in y), 8 for the handful of such steps in a row.  A wrong sign is off by order one."""
+    x, cb, temp, bound, freq, u1, u2, ds, wl, m, hw = _oracle_soft_case(k, 800 + k)
+    from oracle import mcquic_ref as O
+    raw = O.vq_logit(x.float(), cb.float(), temp.float(), torch.tensor([bound]))
+    post = O.random_drop(raw, freq.float(), u1.float())
+    for dl in (None, wl.float()):
+        args = (post, raw, u2.float(), ds.float(), dl, temp.float(), bound, m, hw)
+        want = R.soft_bwd64(*args)
+        scales = R.soft_bwd_scales64(want[0], raw, temp.float(), bound, m, hw)
+        errs = R.soft_bwd_errs(R.soft_bwd_f32(*args), want, scales)
+        assert max(errs) <= 8 * (k + 64) * 2.0 ** -24, errs
+        flipped = tuple(-t for t in R.soft_bwd_f32(*args))
+        assert min(R.soft_bwd_errs(flipped, want, scales)[::2]) > 0.1     # (rowsum may vanish: d dist and dtrow do not)
+
+
+def test_inner_restatement():
+    """R.inner_f32, a float32 chain over d channels, against R.inner64: within (d + 1) 2^-24 of sum_j |x_j c_kj|, the standard bound
+    of a d-term inner product (Higham, Accuracy and Stability of Numerical Algorithms, 3.1)."""
+    for m, k, d, n, h, w in ((2, 40, 64, 1, 2, 3), (3, 7, 1, 2, 1, 1), (1, 130, 10, 1, 3, 3)):
+        x, cb = R.randn((n, m * d, h, w), 900 + d), R.randn((m, k, d), 901 + d, 0.3)
+        want = R.inner64(x, cb)
+        assert want.shape == (n, m, h, w, k)
+        assert R.scaled_err(R.inner_f32(x, cb), want, R.inner_scale64(x, cb)) <= (d + 1) * 2.0 ** -24
+        assert torch.allclose(want[0, m - 1, h - 1, 0, k - 1], (x.double()[0, (m - 1) * d:, h - 1, 0] * cb.double()[m - 1, k - 1]).sum(), rtol=1e-13)
