@@ -545,8 +545,9 @@ int mcq_wgrad_flush(int32_t discard, void* stream);
  * activation when denseNorm is set (mcquic/nn/blocks.py:179-200).  gamma / beta may be NULL (1 / 0).  y_silu (NULL = none)
  * receives silu(y).  mean_out / rstd_out [N * groups] (both or neither): what the backward pass needs. */
 /* `workspace` (round 5; mcq_group_norm_workspace_floats floats, 0 = none needed, NULL = take the one-workgroup-per-run kernel):
- * planes of 256 pixels and more are cut into 8192-float chunks, one workgroup each, whose (mean, M2) pairs are merged in
- * (plane, chunk) order -- Neon's GroupNorm(32, 32) on 512 x 512 maps is 32 chunks per run instead of one workgroup. */
+ * planes of 256 pixels and more are cut into 8192-float chunks, one workgroup each, whose three statistics -- the chunk's float32
+ * mean m_c, the residue sum (x - m_c) its rounding left, and sum (x - m_c)^2: 3 floats per chunk -- are merged in (plane, chunk)
+ * order about one point -- Neon's GroupNorm(32, 32) on 512 x 512 maps is 32 chunks per run instead of one workgroup. */
 size_t mcq_group_norm_workspace_floats(int32_t N, int32_t C, int32_t HW, int32_t groups);
 int mcq_group_norm_f32(const float* x, const float* gamma, const float* beta, float* y, float* y_silu, float* mean_out,
                        float* rstd_out, float* workspace /* or NULL */, int32_t N, int32_t C, int32_t HW, int32_t groups, float eps,

@@ -375,3 +375,105 @@ def inner_f32(x, codebook):
     for j in range(d):
         acc = acc + xv[:, :, j, :, :, None] * codebook[None, :, None, None, :, j]
     return acc
+
+
+# ---- GroupNorm (csrc/norm.hip) ------------------------------------------------------------------------------------------------------------
+# gamma / beta None mean 1 / 0.  A run = the cg * h * w elements one (image, group) normalises over; statistics come back as [n, groups].
+def _per_channel(p, c, dtype, fill):
+    return (torch.full((c,), fill, dtype=dtype) if p is None else p.to(dtype)).reshape(1, c, 1, 1)
+
+
+def _gn_forward(x, gamma, beta, groups, eps, sqrt, div):
+    """The definition in x's dtype: mean, then centred squares (biased), y = (x - mean) rstd gamma + beta."""
+    n, c, h, w = x.shape
+    runs = x.reshape(n, groups, -1)
+    count = runs.shape[-1]
+    mean = div(runs.sum(-1), torch.tensor(float(count), dtype=x.dtype))
+    centred = runs - mean[..., None]
+    var = div((centred * centred).sum(-1), torch.tensor(float(count), dtype=x.dtype))
+    rstd = div(torch.ones((), dtype=x.dtype), sqrt(var + f32(eps).to(x.dtype)))          # eps as the float32 the kernel receives
+    xhat = (centred * rstd[..., None]).reshape(x.shape)
+    return xhat * _per_channel(gamma, c, x.dtype, 1.0) + _per_channel(beta, c, x.dtype, 0.0), mean, rstd, xhat
+
+
+def group_norm64(x, gamma, beta, groups, eps):
+    """(y, mean [n, groups], rstd [n, groups], silu(y)) in float64."""
+    y, mean, rstd, _ = _gn_forward(x.double(), gamma, beta, groups, eps, torch.sqrt, lambda a, b: a / b)
+    return y, mean, rstd, silu64(y)
+
+
+def group_norm_f32(x, gamma, beta, groups, eps):
+    """The same definition with every operation rounded to float32 (sums by torch.sum) -- one rounding per operation where the kernel fuses its last two."""
+    assert x.dtype == F32
+    y, mean, rstd, _ = _gn_forward(x, gamma, beta, groups, eps, sqrt_f32, div_f32)
+    return y, mean, rstd, silu_f32(y)
+
+
+def group_norm_bwd64(x, dy, gamma, groups, eps):
+    """(dx, dgamma, dbeta) from float64 autograd through the definition."""
+    c = x.shape[1]
+    xd = x.double().requires_grad_()
+    gd = (torch.ones(c, dtype=torch.float64) if gamma is None else gamma.double()).requires_grad_()
+    bd = torch.zeros(c, dtype=torch.float64, requires_grad=True)
+    _gn_forward(xd, gd, bd, groups, eps, torch.sqrt, lambda a, b: a / b)[0].backward(dy.double())
+    return xd.grad, gd.grad, bd.grad
+
+
+def group_norm_bwd_f32(x, dy, gamma, groups, eps):
+    """The centred backward formulas, every operation in float32, on the float32 definition's own statistics:
+        dx = rstd (g dy - mean_run(g dy) - xhat mean_run(g dy xhat)),  dgamma = sum_n sum_p dy xhat,  dbeta = sum_n sum_p dy."""
+    assert x.dtype == F32 and dy.dtype == F32
+    n, c, h, w = x.shape
+    _, _, rstd, xhat = _gn_forward(x, None, None, groups, eps, sqrt_f32, div_f32)
+    gdy = dy * _per_channel(gamma, c, F32, 1.0)
+    count = torch.tensor(float(c // groups * h * w), dtype=F32)
+    m1 = div_f32(gdy.reshape(n, groups, -1).sum(-1), count)[..., None]
+    m2 = div_f32((gdy * xhat).reshape(n, groups, -1).sum(-1), count)[..., None]
+    dx = (rstd[..., None] * (gdy.reshape(n, groups, -1) - m1 - xhat.reshape(n, groups, -1) * m2)).reshape(x.shape)
+    return dx, (dy * xhat).sum((0, 2, 3)), dy.sum((0, 2, 3))
+
+
+def group_norm_scales64(x, dy, gamma, beta, groups, eps):
+    """What each result is accurate relative to (a sum that cancels: the sum of its terms' magnitudes), as tensors that broadcast
+    against the result: y / silu(y) -- the run's max |y64|; mean -- |mean64| + the run's standard deviation; rstd -- itself;
+    dx -- the run's rstd64 max |gamma dy|; dgamma[c] -- sum |dy xhat|; dbeta[c] -- sum |dy|."""
+    n, c, h, w = x.shape
+    xd = x.double()
+    y, mean, rstd, _ = group_norm64(x, gamma, beta, groups, eps)
+    runs = xd.reshape(n, groups, -1)
+    sigma = ((runs - mean[..., None]) ** 2).mean(-1).sqrt()
+    xhat = ((runs - mean[..., None]) * rstd[..., None]).reshape(x.shape)
+    per_run = lambda t: t.reshape(n, groups, -1).abs().max(-1)[0].repeat_interleave(c // groups, 1).reshape(n, c, 1, 1)
+    gdy = dy.double() * _per_channel(gamma, c, torch.float64, 1.0)
+    return dict(y=per_run(y), mean=mean.abs() + sigma, rstd=rstd,
+                dx=per_run(gdy) * rstd.repeat_interleave(c // groups, 1).reshape(n, c, 1, 1),
+                dgamma=(dy.double() * xhat).abs().sum((0, 2, 3)), dbeta=dy.double().abs().sum((0, 2, 3)))
+
+
+GN_REGIMES = ("plain", "biased", "bias_dominated", "bias_dominated_dy1", "channel_offsets", "quiet", "large", "outlier", "outlier_first")
+_GN_X = dict(plain=(0.3, 1.5, 0.4), biased=(10.0, 1.0, 1.0), bias_dominated=(10.0, 0.1, 1.0), bias_dominated_dy1=(10.0, 0.1, 1.0),
+             channel_offsets=(0.0, 0.1, 1.0), quiet=(0.0, 1e-3, 1e-3), large=(0.0, 1e4, 5e3), outlier=(0.0, 1.0, 0.5), outlier_first=(0.0, 1.0, 0.5))
+
+
+def gn_case(shape, groups, regime, seed, constant_run=False, affine=True):
+    """(x, dy, gamma, beta) of one GroupNorm case.  x = mean + sigma N(0, 1) per regime (_GN_X: mean, sigma, step), image i moved by
+    (i % 7) step and spread by 1 + (i % 4) / 4 so that neighbouring images of a batch share neither mean nor rstd; `channel_offsets` adds 5 N(0, 1) per channel (only meaningful
+    with more than one channel per group); `outlier` sets one element of image 0's first run to 1e3, `outlier_first` the FIRST element of every run of image 0; dy ~ N(0, 1), plus 1 in
+    `bias_dominated_dy1`.  `constant_run`: the last run of the last image is 2.5 throughout.  gamma, beta ~ N(0, 1) of mixed sign."""
+    n, c, h, w = shape
+    g = torch.Generator().manual_seed(seed)
+    mean, sigma, step = _GN_X[regime]
+    img = torch.arange(n, dtype=F32).reshape(n, 1, 1, 1)
+    x = torch.randn(shape, generator=g) * (sigma * (1.0 + 0.25 * (img % 4))) + mean + (img % 7) * step
+    if regime == "channel_offsets":
+        assert c // groups > 1
+        x = x + 5.0 * torch.randn((1, c, 1, 1), generator=g)
+    if regime == "outlier":
+        x.view(-1)[(h * w) // 2] = 1e3
+    if regime == "outlier_first":                                    # (where a kernel that shifts by a sample of the run would take it)
+        x.reshape(n, groups, -1)[0, :, 0] = 1e3
+    dy = torch.randn(shape, generator=g) + (1.0 if regime == "bias_dominated_dy1" else 0.0)
+    gamma, beta = torch.randn(c, generator=g), torch.randn(c, generator=g)
+    if constant_run:
+        x.reshape(n, groups, -1)[n - 1, groups - 1] = 2.5
+    return x.to(F32).contiguous(), dy.to(F32).contiguous(), (gamma if affine else None), (beta if affine else None)

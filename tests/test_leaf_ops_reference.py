@@ -229,3 +229,66 @@ def test_inner_restatement():
         assert want.shape == (n, m, h, w, k)
         assert R.scaled_err(R.inner_f32(x, cb), want, R.inner_scale64(x, cb)) <= (d + 1) * 2.0 ** -24
         assert torch.allclose(want[0, m - 1, h - 1, 0, k - 1], (x.double()[0, (m - 1) * d:, h - 1, 0] * cb.double()[m - 1, k - 1]).sum(), rtol=1e-13)
+
+
+# ---- GroupNorm: the references of tests/test_gpu_group_norm_leaf.py ---------------------------------------------------------------------
+GN_SHAPES = ((3, 8, 5, 51, 2), (2, 4, 1, 8193, 2), (2, 6, 1, 1, 3), (1, 4, 3, 5, 2), (5, 8, 16, 16, 4))
+
+
+@pytest.mark.parametrize("affine", [True, False])
+@pytest.mark.parametrize("sg", GN_SHAPES)
+def test_group_norm_references_are_torch_group_norm(sg, affine):
+    """group_norm64 / group_norm_bwd64 (the definition written out, autograd through it) against torch.nn.functional.group_norm in
+    float64 to 1e-12 in the scales of R.group_norm_scales64, with and without gamma / beta, on the cancelling regime too.  (The scales,
+    not each tensor's largest entry: ATen's own backward forms (ds - mean db) rstd, and in `bias_dominated_dy1` on runs of 16386
+    elements that difference of two sums of 1.6e5 leaves 1e-9 of absolute error in a dgamma of 190 -- in float64.)"""
+    for regime in ("plain", "bias_dominated_dy1"):
+        x, dy, gamma, beta = R.gn_case(sg[:4], sg[4], regime, 17, affine=affine)
+        c = sg[1]
+        xd = x.double().requires_grad_()
+        gd, bd = (None, None) if not affine else (gamma.double().requires_grad_(), beta.double().requires_grad_())
+        want = torch.nn.functional.group_norm(xd, sg[4], gd, bd, float(R.f32(1e-5)))
+        want.backward(dy.double())
+        y, mean, rstd, twin = R.group_norm64(x, gamma, beta, sg[4], 1e-5)
+        dx, dgamma, dbeta = R.group_norm_bwd64(x, dy, gamma, sg[4], 1e-5)
+        assert mean.shape == rstd.shape == (sg[0], sg[4])
+        pairs = [(y, want.detach()), (dx, xd.grad), (twin, torch.nn.functional.silu(want.detach()))]
+        if affine:
+            pairs += [(dgamma, gd.grad), (dbeta, bd.grad)]
+        else:                                                        # (the gradients of the implied gamma = 1, beta = 0)
+            xhat = torch.nn.functional.group_norm(x.double(), sg[4], None, None, float(R.f32(1e-5)))
+            pairs += [(dgamma, (dy.double() * xhat).sum((0, 2, 3))), (dbeta, dy.double().sum((0, 2, 3)))]
+        sc = R.group_norm_scales64(x, dy, gamma, beta, sg[4], 1e-5)
+        for (got, ref), scale in zip(pairs, (sc["y"], sc["dx"], sc["y"], sc["dgamma"], sc["dbeta"])):
+            assert got.dtype == torch.float64 and got.shape == ref.shape
+            assert R.scaled_err(got, ref, scale.expand_as(ref)) <= 1e-12
+        runs = x.double().reshape(sg[0], sg[4], -1)
+        assert torch.allclose(mean, runs.mean(-1), rtol=0, atol=1e-12 * float(runs.abs().max()))
+        assert torch.allclose(rstd, 1.0 / torch.sqrt(runs.var(-1, unbiased=False) + float(R.f32(1e-5))), rtol=1e-12, atol=0)
+
+
+@pytest.mark.parametrize("regime", R.GN_REGIMES)
+@pytest.mark.parametrize("sg", GN_SHAPES[:2] + GN_SHAPES[4:])
+def test_group_norm_float32_definition(sg, regime):
+    """The float32 definition (group_norm_f32 / group_norm_bwd_f32: the yardstick of the GPU bars) against float64 in every input
+    regime, in the scales of R.group_norm_scales64.  Its error has two sources: a few roundings at the scale of the result (u = 2^-24
+    each), and the rounding of the mean -- up to u max |x| -- seen from the run's 1 / rstd, i.e. u kappa with kappa = max |x| rstd
+    (100 .. 170 in the bias-dominated regimes, sqrt(count) with one outlier).  So: mean, rstd and dbeta, which never see xhat,
+    within 8 u; everything built on xhat within 8 u (1 + kappa).  A sign error or a dropped term is off by O(1)."""
+    u = 2.0 ** -24
+    groups = sg[4]
+    x, dy, gamma, beta = R.gn_case(sg[:4], groups, regime, 23)
+    y64, mean64, rstd64, silu64 = R.group_norm64(x, gamma, beta, groups, 1e-5)
+    dx64, dg64, db64 = R.group_norm_bwd64(x, dy, gamma, groups, 1e-5)
+    sc = R.group_norm_scales64(x, dy, gamma, beta, groups, 1e-5)
+    y, mean, rstd, silu = R.group_norm_f32(x, gamma, beta, groups, 1e-5)
+    dx, dg, db = R.group_norm_bwd_f32(x, dy, gamma, groups, 1e-5)
+    kappa = float((x.double().reshape(sg[0], groups, -1).abs().max(-1)[0] * rstd64).max())
+    for name, got, want, scale, bound in (("y", y, y64, sc["y"], 8 * u * (1 + kappa)), ("silu", silu, silu64, sc["y"], 8 * u * (1 + kappa)),
+                                          ("mean", mean, mean64, sc["mean"], 8 * u), ("rstd", rstd, rstd64, sc["rstd"], 8 * u),
+                                          ("dx", dx, dx64, sc["dx"], 8 * u * (1 + kappa)), ("dgamma", dg, dg64, sc["dgamma"], 8 * u * (1 + kappa)),
+                                          ("dbeta", db, db64, sc["dbeta"], 8 * u)):
+        assert got.dtype == R.F32
+        err = R.scaled_err(got, want, scale.expand_as(want))
+        assert err <= bound, (name, err, bound, kappa)
+    assert R.scaled_err(-dx, dx64, sc["dx"].expand_as(dx64)) > 0.1 and R.scaled_err(dg.flip(0), dg64, sc["dgamma"]) > 1e-3
