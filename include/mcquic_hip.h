@@ -421,6 +421,27 @@ int mcq_adam_step_f32(const void* ptr_tables, int32_t ntensors, const int64_t* n
                       int32_t nblocks, float* step, const float* lr_dev /* or NULL */, double lr, double beta1, double beta2, double eps,
                       double weight_decay, int32_t decoupled, int32_t maximize, void* scalars, void* stream);
 
+/* LAMB over many tensors with per-tensor trust ratios (the reference's `FusedLAMB` registry entry, mcquic/train/ddp.py:53-69; the
+ * arithmetic is written out in mcquic_amd/optim.py `Lamb`).  Tables as for mcq_adam_step_f32, chunks of mcq_adam_chunk() elements,
+ * plus tensor_first_blk[ntensors + 1]: tensor t owns chunks [tensor_first_blk[t], tensor_first_blk[t + 1]).
+ *   mcq_lamb_grad_partials_f32  partials[b] = sum of g^2 over chunk b, b < nblocks (double; one launch).  Called once per parameter
+ *                               group into consecutive slices of ONE array: the gradient norm spans all groups.
+ *   mcq_lamb_step_f32           four launches: the n_grad_partials partials summed in a fixed order -> G (to grad_norm[0]), the clip
+ *                               divisor G / max_grad_norm (1 unless G > max_grad_norm), `step` += 1, bias corrections; m and v
+ *                               updated with (sum p^2, sum u^2) per chunk; per tensor ratios[t] = ||p|| / ||u|| and the rate lr * that
+ *                               (lr alone unless use_nvlamb or weight_decay != 0, or where a norm is zero); p -= rate * u.
+ *                               Gradients are only read.  `workspace`: mcq_lamb_workspace_bytes(ntensors, nblocks) bytes (0 for
+ *                               non-positive arguments), 8-byte aligned; `scalars` = 16 bytes of device scratch; `lr_dev` as above.
+ * All sums are doubles reduced in fixed trees (no atomics): equal inputs give equal bits.  Nothing is read by the host. */
+size_t mcq_lamb_workspace_bytes(int32_t ntensors, int32_t nblocks);
+int mcq_lamb_grad_partials_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor,
+                               const int64_t* blk_first, int32_t nblocks, double* partials, void* stream);
+int mcq_lamb_step_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                      const int32_t* tensor_first_blk, int32_t nblocks, const double* grad_partials, int32_t n_grad_partials,
+                      float* step, const float* lr_dev /* or NULL */, double lr, double beta1, double beta2, double eps, double weight_decay,
+                      int32_t bias_correction, int32_t adam_w_mode, int32_t grad_averaging, int32_t use_nvlamb, double max_grad_norm,
+                      float* grad_norm, float* ratios, void* workspace, void* scalars, void* stream);
+
 /* u8 = trunc(clamp(((x + 1) / 2) * 255.999, 0, 255))   (mcquic/utils/vision.py:143-146 DeTransform). */
 int mcq_detransform_u8(const float* x, uint8_t* out, int64_t n, void* stream);
 

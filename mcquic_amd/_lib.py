@@ -128,6 +128,11 @@ SYMBOLS = {
     "mcq_adam_chunk": (c_int32, []),
     "mcq_adam_step_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_double, c_double, c_double, c_double,
                                     c_double, c_int32, c_int32, c_void_p, c_void_p]),
+    "mcq_lamb_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "mcq_lamb_grad_partials_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "mcq_lamb_step_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                    c_double, c_double, c_double, c_double, c_double, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p,
+                                    c_void_p, c_void_p, c_void_p, c_void_p]),
     "mcq_sumsq_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mcq_clip_by_norm_f32": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_int64, c_void_p]),
     "mcq_detransform_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),

@@ -8,34 +8,27 @@ this object owns; the update is a one-thread kernel (step count, bias correction
 element.  Arithmetic and state layout are torch.optim.Adam's / AdamW's: `state_dict()` / `load_state_dict()` exchange checkpoints with
 them (per-parameter `step`, `exp_avg`, `exp_avg_sq`), a learning rate given as a device tensor is read by the kernel on every
 call (a scheduler fills it; a captured step needs no re-capture), and nothing is read back by the host, so
-`parallel.GraphedTrainStep` captures it like any capturable optimizer.  float32 parameters on a HIP device only: there is no CPU path."""
-from __future__ import annotations
+`parallel.GraphedTrainStep` captures it like any capturable optimizer.  float32 parameters on a HIP device only: there is no CPU path.
 
-from typing import Optional
+`Lamb` (alias `FusedLAMB`) is the reference's third optimizer (mcquic/train/ddp.py:53-69, apex FusedLAMB's arithmetic) on the same tables
+and flat moment buffers: csrc/lamb.hip, five launches; `REGISTRY` maps the reference's `optim.key` names to these classes."""
+from __future__ import annotations
 
 import torch
 
 from . import _lib
 from .ops import check, _guard, _stream
 
-__all__ = ["Adam", "AdamW"]
+__all__ = ["Adam", "AdamW", "Lamb", "FusedLAMB", "REGISTRY"]
 
 
-class Adam(torch.optim.Optimizer):
-    """torch.optim.Adam(params, lr, betas, eps, weight_decay, maximize=...) without `amsgrad` / `foreach` / `differentiable`;
-    `decoupled=True` makes the decay AdamW's (`AdamW` below sets it and AdamW's default of 1e-2)."""
+class _Planned(torch.optim.Optimizer):
+    """What the optimizers of this module share: both moments in two flat buffers the object owns, and the device tables (pointers,
+    sizes, chunks) the kernels walk, built once per parameter group and refilled only when an address changes."""
+    _NAME = "?"
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, *, decoupled: bool = False,
-                 maximize: bool = False):
-        if not torch.is_tensor(lr) and not lr >= 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid betas: {betas}")
-        if not eps >= 0.0 or not weight_decay >= 0.0:
-            raise ValueError("eps and weight_decay must be non-negative")
-        # (capturable=True is what torch's load_state_dict looks at to keep `step` a float32 device tensor)
-        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, decoupled=bool(decoupled),
-                                      maximize=bool(maximize), capturable=True))
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         self._plans = {}                                      # group index -> _Plan
 
     # ---- state in flat buffers -------------------------------------------------------------------------------------------------
@@ -53,7 +46,7 @@ class Adam(torch.optim.Optimizer):
         sizes = [p.numel() for p in params]
         if plan is None or plan.ids != ids or plan.flat_m.device != params[0].device:
             # (also when the set of parameters that carry a gradient changed: fresh buffers, the old state is copied over below)
-            plan = self._plans[gi] = Adam._Plan()
+            plan = self._plans[gi] = type(self)._Plan()
             dev = params[0].device
             plan.sizes, plan.ids = sizes, ids
             offs, at = [], 0
@@ -79,6 +72,7 @@ class Adam(torch.optim.Optimizer):
             plan.blk_first = torch.tensor(blk_f, dtype=torch.int64).to(dev)
             plan.nblocks = len(blk_t)
             plan.tables = torch.zeros(4 * len(params), dtype=torch.int64, device=dev)
+            self._extend_plan(plan, blk_t, dev)
         for p, (mv, vv) in zip(params, plan.views):
             st = self.state[p]
             old_m, old_v, old_s = st.get("exp_avg"), st.get("exp_avg_sq"), st.get("step")
@@ -92,12 +86,15 @@ class Adam(torch.optim.Optimizer):
         plan.adopted = True
         return plan
 
+    def _extend_plan(self, plan, blk_t, dev) -> None:
+        """What a subclass adds to a new plan (`blk_t`: the tensor of every chunk, on the host)."""
+
     def _tables(self, plan, params):
         key = tuple((p.data_ptr(), p.grad.data_ptr()) for p in params)
         if plan.key == key:
             return
         if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("mcquic_amd.optim.Adam: parameter / gradient addresses changed since the last step; call `prepare()` "
+            raise RuntimeError(f"mcquic_amd.optim.{self._NAME}: parameter / gradient addresses changed since the last step; call `prepare()` "
                                "before capturing (a host-to-device copy of the pointer table cannot be part of a graph)")
         ptrs = [p.data_ptr() for p in params] + [p.grad.data_ptr() for p in params] + [m.data_ptr() for m, _ in plan.views] + \
                [v.data_ptr() for _, v in plan.views]
@@ -110,10 +107,10 @@ class Adam(torch.optim.Optimizer):
             g = p.grad
             if not (p.is_cuda and g.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and p.is_contiguous() and g.is_contiguous()
                     and not g.is_sparse):
-                raise RuntimeError("mcquic_amd.optim.Adam: contiguous float32 parameters and gradients on a HIP device only "
+                raise RuntimeError(f"mcquic_amd.optim.{self._NAME}: contiguous float32 parameters and gradients on a HIP device only "
                                    "(there is no CPU path)")
             if p.device != params[0].device:
-                raise RuntimeError("mcquic_amd.optim.Adam: the parameters of one group must live on one device (one launch per group)")
+                raise RuntimeError(f"mcquic_amd.optim.{self._NAME}: the parameters of one group must live on one device (one launch per group)")
         return params
 
     @torch.no_grad()
@@ -124,6 +121,34 @@ class Adam(torch.optim.Optimizer):
             params = self._checked(group)
             if params:
                 self._tables(self._flat_state(gi, params), params)
+
+    def _rate(self, group):
+        """(device tensor or None, host value) of a group's learning rate."""
+        lr = group["lr"]
+        if torch.is_tensor(lr):
+            if lr.is_cuda:
+                if lr.dtype != torch.float32 or lr.numel() != 1:
+                    raise TypeError(f"mcquic_amd.optim.{self._NAME}: a device learning rate must be one float32")
+                return lr, 0.0
+        return None, float(lr)
+
+
+class Adam(_Planned):
+    _NAME = "Adam"
+    """torch.optim.Adam(params, lr, betas, eps, weight_decay, maximize=...) without `amsgrad` / `foreach` / `differentiable`;
+    `decoupled=True` makes the decay AdamW's (`AdamW` below sets it and AdamW's default of 1e-2)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, *, decoupled: bool = False,
+                 maximize: bool = False):
+        if not torch.is_tensor(lr) and not lr >= 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid betas: {betas}")
+        if not eps >= 0.0 or not weight_decay >= 0.0:
+            raise ValueError("eps and weight_decay must be non-negative")
+        # (capturable=True is what torch's load_state_dict looks at to keep `step` a float32 device tensor)
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, decoupled=bool(decoupled),
+                                      maximize=bool(maximize), capturable=True))
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -136,16 +161,7 @@ class Adam(torch.optim.Optimizer):
                 continue
             plan = self._flat_state(gi, params)
             self._tables(plan, params)
-            lr = group["lr"]
-            lr_dev: Optional[torch.Tensor] = None
-            if torch.is_tensor(lr):
-                if lr.is_cuda:
-                    if lr.dtype != torch.float32 or lr.numel() != 1:
-                        raise TypeError("mcquic_amd.optim.Adam: a device learning rate must be one float32")
-                    lr_dev = lr
-                lr_host = 0.0 if lr_dev is not None else float(lr)
-            else:
-                lr_host = float(lr)
+            lr_dev, lr_host = self._rate(group)
             b1, b2 = group["betas"]
             with _guard(params[0].device):
                 check(lib.mcq_adam_step_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
@@ -190,3 +206,161 @@ class AdamW(Adam):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, *, maximize: bool = False):
         super().__init__(params, lr, betas, eps, weight_decay, decoupled=True, maximize=maximize)
+
+
+class Lamb(_Planned):
+    """LAMB with apex `FusedLAMB`'s arithmetic and constructor (the reference's `"FusedLAMB"` registry entry, mcquic/train/ddp.py:53-69;
+    apex is not available on this platform and torch ships no LAMB): csrc/lamb.hip, five launches per parameter group whatever the
+    number of tensors, nothing read back by the host.  One `step()`:
+
+      1. G = sqrt(sum g^2) over every parameter that has a gradient, in EVERY group, before any group is updated;
+      2. c = G / max_grad_norm if G > max_grad_norm else 1 (a NaN G compares false);
+      3. per group t += 1; beta3 = 1 - beta1 if grad_averaging else 1; bc1 = 1 - beta1^t, bc2 = 1 - beta2^t (1 without bias_correction);
+      4. g^ = g / c.  L2 mode (adam_w_mode=False): g^ += wd p; m = beta1 m + beta3 g^; v = beta2 v + (1 - beta2) g^2;
+         u = (m / bc1) / (sqrt(v / bc2) + eps).  AdamW mode: m, v from the plain g^ and u += wd p;
+      5. per tensor ||p|| (before the update) and ||u||;
+      6. r = lr; if use_nvlamb or wd != 0: r = lr ||p|| / ||u|| where both norms are non-zero.  p -= r u.
+
+    Gradients are left as they were (apex overwrites them with u).  `amsgrad` is not supported; `set_grad_none` only sets the default
+    of `zero_grad`.  State layout is Adam's (per-parameter `step`, `exp_avg`, `exp_avg_sq`); `load_state_dict` also takes apex's
+    (an integer `step` in the param group, none per parameter).  All groups live on one device: the gradient norm spans them.
+    After a step, without any host synchronisation: `grad_norm` (G, a 0-dim device tensor) and `trust_ratios(group)`."""
+    _NAME = "Lamb"
+
+    class _Plan(_Planned._Plan):
+        __slots__ = ("tensor_first_blk", "workspace", "ratios")
+
+    def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, amsgrad=False,
+                 adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0, use_nvlamb=False):
+        if amsgrad:
+            raise RuntimeError("mcquic_amd.optim.Lamb does not support the AMSGrad variant.")
+        if not torch.is_tensor(lr) and not lr >= 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid betas: {betas}")
+        if not eps >= 0.0 or not weight_decay >= 0.0:
+            raise ValueError("eps and weight_decay must be non-negative")
+        if not max_grad_norm >= 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
+        super().__init__(params, dict(lr=lr, bias_correction=bool(bias_correction), betas=tuple(betas), eps=eps, weight_decay=weight_decay,
+                                      grad_averaging=bool(grad_averaging), max_grad_norm=max_grad_norm, adam_w_mode=bool(adam_w_mode),
+                                      use_nvlamb=bool(use_nvlamb), capturable=True))
+        self.set_grad_none = bool(set_grad_none)
+        self._norm = None                                     # (key, double partials of sum g^2 for all groups, G)
+
+    def zero_grad(self, set_to_none=None):
+        super().zero_grad(self.set_grad_none if set_to_none is None else set_to_none)
+
+    def _extend_plan(self, plan, blk_t, dev) -> None:
+        first, at = [0], 0
+        for i in range(plan.ntensors):
+            while at < len(blk_t) and blk_t[at] == i:
+                at += 1
+            first.append(at)
+        plan.tensor_first_blk = torch.tensor(first, dtype=torch.int32).to(dev)
+        nbytes = _lib.load().mcq_lamb_workspace_bytes(plan.ntensors, max(plan.nblocks, 1))
+        plan.workspace = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+        plan.ratios = torch.zeros(plan.ntensors, dtype=torch.float32, device=dev)
+
+    def _planned(self):
+        """[(group, plan)] of the groups that hold gradients, tables current, and the buffers of the gradient norm they share."""
+        live = []
+        for gi, group in enumerate(self.param_groups):
+            params = self._checked(group)
+            if params:
+                if live and params[0].device != live[0][2][0].device:
+                    raise RuntimeError("mcquic_amd.optim.Lamb: all param groups must live on one device (the gradient norm spans them)")
+                live.append((gi, group, params))
+        out = []
+        for gi, group, params in live:
+            plan = self._flat_state(gi, params)
+            self._tables(plan, params)
+            out.append((group, plan))
+        key = tuple((id(plan), plan.nblocks) for _, plan in out)
+        if out and (self._norm is None or self._norm[0] != key):
+            dev = out[0][1].flat_m.device
+            gnorm = self._norm[2] if self._norm is not None and self._norm[2].device == dev else torch.zeros((), dtype=torch.float32, device=dev)
+            self._norm = (key, torch.zeros(max(sum(plan.nblocks for _, plan in out), 1), dtype=torch.float64, device=dev), gnorm)
+        return out
+
+    @torch.no_grad()
+    def prepare(self) -> None:
+        """As `Adam.prepare`, for every group at once (the norm's buffers depend on all of them)."""
+        self._planned()
+
+    @property
+    def grad_norm(self) -> torch.Tensor:
+        """G of the last step: the norm of all gradients before clipping (0-dim float32 on the device)."""
+        if self._norm is None:
+            raise RuntimeError("mcquic_amd.optim.Lamb: no step has run yet")
+        return self._norm[2]
+
+    def trust_ratios(self, group: int = 0) -> torch.Tensor:
+        """||p|| / ||u|| of the last step for every tensor of `group` that had a gradient, in the group's order ([ntensors] float32 on the
+        device; inf / 0 / NaN where a norm is zero -- the update uses the plain learning rate there)."""
+        plan = self._plans.get(group)
+        if plan is None:
+            raise RuntimeError("mcquic_amd.optim.Lamb: no step has run yet for this group")
+        return plan.ratios
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise NotImplementedError("mcquic_amd.optim.Lamb: closures are not supported (the reference's trainer passes none)")
+        lib = _lib.load()
+        todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
+        if not todo:
+            return None
+        _, partials, gnorm = self._norm
+        total = sum(plan.nblocks for _, plan in todo)
+        with _guard(gnorm.device):
+            at = 0
+            for _, plan in todo:                              # the norm of ALL gradients first ...
+                check(lib.mcq_lamb_grad_partials_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
+                                                     plan.blk_first.data_ptr(), plan.nblocks, partials.data_ptr() + 8 * at, _stream()),
+                      "mcq_lamb_grad_partials_f32")
+                at += plan.nblocks
+            for group, plan in todo:                          # ... then every group's update reads the same partials
+                lr_dev, lr_host = self._rate(group)
+                b1, b2 = group["betas"]
+                check(lib.mcq_lamb_step_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
+                                            plan.blk_first.data_ptr(), plan.tensor_first_blk.data_ptr(), plan.nblocks, partials.data_ptr(), total,
+                                            plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(b1),
+                                            float(b2), float(group["eps"]), float(group["weight_decay"]), 1 if group["bias_correction"] else 0,
+                                            1 if group["adam_w_mode"] else 0, 1 if group["grad_averaging"] else 0,
+                                            1 if group["use_nvlamb"] else 0, float(group["max_grad_norm"]), gnorm.data_ptr(),
+                                            plan.ratios.data_ptr(), plan.workspace.data_ptr(), plan.scalars.data_ptr(), _stream()),
+                      "mcq_lamb_step_f32")
+        return None
+
+    def state_dict(self):
+        """Adam's layout; every parameter gets a `step` tensor of its own (here a group shares one)."""
+        sd = super().state_dict()
+        sd["state"] = {k: {n: (v.clone() if n == "step" and torch.is_tensor(v) else v) for n, v in st.items()} for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """Our own checkpoints, and apex FusedLAMB's: there the count is an integer `step` of the param group and the per-parameter
+        state holds the two moments only.  The tensors move into the flat buffers on the next `step()`, at the same addresses."""
+        groups = [dict(g) for g in state_dict["param_groups"]]
+        state = {k: dict(v) for k, v in state_dict["state"].items()}
+        for g in groups:
+            if "step" in g:
+                count = g.pop("step")
+                for pid in g["params"]:
+                    if pid in state and "step" not in state[pid]:
+                        state[pid]["step"] = torch.tensor(float(count), dtype=torch.float32)
+        super().load_state_dict({"state": state, "param_groups": groups})
+        for group in self.param_groups:
+            if group.get("amsgrad"):
+                raise NotImplementedError("mcquic_amd.optim.Lamb: `amsgrad` checkpoints are not supported")
+            for k in ("bias_correction", "grad_averaging", "max_grad_norm", "adam_w_mode", "use_nvlamb"):
+                group.setdefault(k, self.defaults[k])         # (apex keeps adam_w_mode / use_nvlamb on the object, not in the groups)
+            group["capturable"] = True
+        for plan in self._plans.values():
+            plan.adopted = False
+
+
+FusedLAMB = Lamb
+# the reference's optimizer registry (mcquic/train/ddp.py:53-69), with its meanings: `"Adam"` is AdamW there
+REGISTRY = {"FusedLAMB": Lamb, "Adam": AdamW, "SGD": torch.optim.SGD}

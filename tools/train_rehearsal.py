@@ -54,6 +54,8 @@ def main():
                                                           "the rate is a device tensor the captured update reads, refilled by the host every step")
     ap.add_argument("--fused", action="store_true", help="torch.optim.Adam(fused=True): torch's multi-tensor kernel (19 launches for this model)")
     ap.add_argument("--own-adam", action="store_true", help="mcquic_amd.optim.Adam: the whole model in one launch")
+    ap.add_argument("--lamb", action="store_true", help="mcquic_amd.optim.Lamb(max_grad_norm=4.0): the reference's FusedLAMB entry; the optimizer clips, "
+                                                        "so the step itself does not")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from mcquic_amd import Compressor, parallel
@@ -64,13 +66,16 @@ def main():
     gen = torch.Generator(device=dev).manual_seed(1)
     val = images(4, args.crop, torch.Generator(device=dev).manual_seed(99), dev)
     lr = torch.tensor(args.lr, device=dev)
-    if args.own_adam:
+    if args.lamb:
+        from mcquic_amd import optim
+        opt = optim.Lamb(model.parameters(), lr=lr, max_grad_norm=4.0)
+    elif args.own_adam:
         from mcquic_amd import optim
         opt = optim.Adam(model.parameters(), lr=lr)
     else:
         opt = torch.optim.Adam(model.parameters(), lr=lr, capturable=True, **({"fused": True} if args.fused else {}))
     x = images(args.batch, args.crop, gen, dev)
-    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=4.0)
+    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if args.lamb else 4.0)
     trace = {"loss": [], "grad_norm": [], "psnr": [], "reassigned": [], "non_finite": 0}
     model.eval()
     step.invalidate()
@@ -90,7 +95,7 @@ def main():
         lv = loss.item()                                           # (what a logger does every step)
         if i % max(10, args.steps // 200) == 0 or i == 1 or os.environ.get("REHEARSAL_TRACE_ALL"):
             trace["loss"].append((i, round(lv, 6)))
-            trace["grad_norm"].append((i, round(float(step.grad_norm), 5)))
+            trace["grad_norm"].append((i, round(float(opt.grad_norm if args.lamb else step.grad_norm), 5)))
         if lv != lv:
             trace["non_finite"] += 1
         if i == args.every:
@@ -111,7 +116,7 @@ def main():
     last = sum(v for _, v in trace["loss"][-3:]) / 3
     out = {"what": "GraphedTrainStep(Adam, lr in a device tensor, max_grad_norm=4.0) on fresh synthetic batches; loss.item() every step; every "
                    f"{args.every} steps: finiteness of all parameters, eager encode/decode PSNR on 4 held-out images, codebook re-assignment every {2 * args.every}",
-           "model": f"Compressor({args.channel}, {args.m}, {ks})", "lr": args.lr, "lr_warmup_steps": args.warmup, "optimizer": "mcquic_amd.optim.Adam" if args.own_adam else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "crop": args.crop, "steps": args.steps,
+           "model": f"Compressor({args.channel}, {args.m}, {ks})", "lr": args.lr, "lr_warmup_steps": args.warmup, "optimizer": "mcquic_amd.optim.Lamb(max_grad_norm=4.0), no clipping in the step" if args.lamb else "mcquic_amd.optim.Adam" if args.own_adam else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "crop": args.crop, "steps": args.steps,
            "ms_per_step": round(t_steps / args.steps * 1e3, 3), "loss_first": round(first, 6), "loss_last": round(last, 6),
            "psnr_first": trace["psnr"][0][1], "psnr_last": trace["psnr"][-1][1], "memset_nodes_ok": parallel.memset_nodes_replay_correctly(dev), "memory": mem, **trace}
     line = json.dumps(out)
