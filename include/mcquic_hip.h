@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   9
+#define MCQ_ABI_VERSION   10
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -579,6 +579,56 @@ size_t mcq_group_norm_bwd_workspace_floats(int32_t N, int32_t C, int32_t HW, int
 int mcq_group_norm_bwd_f32(const float* x, const float* dy, const float* gamma, const float* mean, const float* rstd, float* dx,
                            float* dgamma, float* dbeta, float* workspace, int32_t N, int32_t C, int32_t HW, int32_t groups,
                            void* stream);
+
+/* ---- the training input transform (ABI 10) ---------------------------------------------------------------------------------
+ * What the reference's loader and trainer run in front of every step (mcquic/data/transforms.py:14-21 getTrainingPreprocess:
+ * RandomResizedCrop + RandomGamma; :37-43 getTrainingTransform: RandomPlanckianJitter, the two flips, Normalize(0.5, 0.5);
+ * mcquic/train/trainer.py:266) as two launches.  The jitter and the flips are the INTENDED operations (the reference's in-place
+ * forms act on copies, mcquic/utils/vision.py:99-104, 167-169, 192-194); with gain 1 and no flip the pass is the reference's
+ * effective clamp(x, 0, 1) then (x - 0.5) / 0.5.
+ * The decisions of image n are row n of a table [N, MCQ_AUG_COLUMNS] float32: */
+#define MCQ_AUG_COLUMNS     16
+#define MCQ_AUG_TOP          0   /* crop box inside the source, in pixels: top, left, height, width (clamped into it by the pass) */
+#define MCQ_AUG_LEFT         1
+#define MCQ_AUG_H            2
+#define MCQ_AUG_W            3
+#define MCQ_AUG_GAMMA_MODE   4   /* one of MCQ_AUG_GAMMA_* */
+#define MCQ_AUG_GAMMA        5   /* the exponent g of MCQ_AUG_GAMMA_POWER */
+#define MCQ_AUG_GAIN0        6   /* factor on channel 0 */
+#define MCQ_AUG_GAIN2        7   /* factor on channel 2 */
+#define MCQ_AUG_HFLIP        8   /* 0 / 1 */
+#define MCQ_AUG_VFLIP        9   /* 0 / 1 */
+#define MCQ_AUG_GAIN_ROW    10   /* informational: the row of `coeffs` the gains came from, -1 = none drawn */
+#define MCQ_AUG_FALLBACK    11   /* informational: 1 = the ten attempts failed and the box is the central crop */
+#define MCQ_AUG_OUTPUT      12   /* one of MCQ_AUG_OUT_*: what follows the gains */
+                                 /* 13..15: zero */
+#define MCQ_AUG_GAMMA_SRGB_TO_LINEAR 0  /* x < 0.0031308 ? 12.92 x : 1.055 |x|^(1/2.4) - 0.055   (vision.py:108-109, its naming) */
+#define MCQ_AUG_GAMMA_LINEAR_TO_SRGB 1  /* x < 0.04045 ? x / 12.92 : (|x + 0.055| / 1.055)^2.4     (vision.py:111-112)            */
+#define MCQ_AUG_GAMMA_POWER          2  /* clamp(clamp(x, 0)^g, 0, 1)                              (vision.py:114-116)            */
+#define MCQ_AUG_GAMMA_IDENTITY       3
+#define MCQ_AUG_OUT_NORMALIZED 0  /* clamp to [0, 1], then (v - 0.5) / 0.5: the whole pipeline, or its second half            */
+#define MCQ_AUG_OUT_CLAMPED    1  /* clamp to [0, 1] only (RandomPlanckianJitter on its own, vision.py:104)                    */
+#define MCQ_AUG_OUT_RAW        2  /* neither (the loader's half -- crop, gamma -- and a flip on its own: values pass unchanged) */
+/* mcq_augment_draw: fills `params` for N images of a [Hs, Ws] source from rng_state = {seed, offset} (device memory) and advances
+ * the offset by one, in stream order: a captured launch draws a fresh table on every replay.
+ *   crop != 0   torchvision's RandomResizedCrop box rule: up to 10 attempts of area = Hs Ws U(scale), log r ~ U(log ratio),
+ *               w = round(sqrt(area r)), h = round(sqrt(area / r)), accepted if it fits, then top / left uniform; after 10
+ *               failures the central crop with the aspect clamped into `ratio`.  Otherwise the box is the whole source.
+ *   gamma != 0  one of the four modes uniformly, g ~ U(0.05, 2.0) for MCQ_AUG_GAMMA_POWER.  Otherwise identity.
+ *   coeffs      [T, 2] gains or NULL: with probability p_gain one row, uniformly.  Otherwise gains of 1.
+ *   p_hflip / p_vflip   probability of each flip.
+ *   output      MCQ_AUG_OUT_*, copied into every row.
+ * mcq_augment_f32 / _u8: out[N, 3, H, W] float32 from src[N, 3, Hs, Ws] (float32 in [0, 1]; uint8 read as v / 255) under `params`:
+ * the box resampled to [H, W] like F.interpolate(mode="bilinear", antialias=True, align_corners=False) on the crop, then gamma,
+ * gains, clamp to [0, 1] and (v - 0.5) / 0.5 (as MCQ_AUG_OUTPUT says), with the flips as an index map on the output.  MCQ_ETOOLARGE: more than 65535 images, a
+ * side above 2^24, or a source more than ~30x the output along an axis. */
+int mcq_augment_draw(uint64_t* rng_state, float* params, int32_t N, int32_t Hs, int32_t Ws, int32_t crop, double scale_lo,
+                     double scale_hi, double ratio_lo, double ratio_hi, int32_t gamma, const float* coeffs /* or NULL */, int32_t T,
+                     float p_gain, float p_hflip, float p_vflip, int32_t output, void* stream);
+int mcq_augment_f32(const float* src, const float* params, float* out, int32_t N, int32_t Hs, int32_t Ws, int32_t H, int32_t W,
+                    void* stream);
+int mcq_augment_u8(const uint8_t* src, const float* params, float* out, int32_t N, int32_t Hs, int32_t Ws, int32_t H, int32_t W,
+                   void* stream);
 
 /* Library / build identification: returns a static string "mcquic_hip <ver> gfx950". */
 /* Launches a kernel with an invalid configuration on purpose and returns what every entry point returns when its launch is

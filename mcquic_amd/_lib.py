@@ -159,12 +159,16 @@ SYMBOLS = {
     "mcq_group_norm_f32": (c_int32, [c_void_p] * 8 + [c_int32, c_int32, c_int32, c_int32, c_float, c_void_p]),
     "mcq_group_norm_bwd_workspace_floats": (c_size_t, [c_int32, c_int32, c_int32, c_int32]),
     "mcq_group_norm_bwd_f32": (c_int32, [c_void_p] * 9 + [c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "mcq_augment_draw": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_double, c_double, c_double, c_double, c_int32,
+                                   c_void_p, c_int32, c_float, c_float, c_float, c_int32, c_void_p]),
+    "mcq_augment_f32": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
+    "mcq_augment_u8": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 5 + [c_void_p]),
     "mcq_selftest_launch_failure": (c_int32, [c_void_p]),
     "mcq_version": (c_char_p, []),
     "mcq_abi_version": (c_int32, []),
 }
 
-ABI_VERSION = 9          # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
+ABI_VERSION = 10         # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
 
 _lib = None
 

@@ -13,6 +13,7 @@
 // broadcast the assign kernel uses for |c|^2; |c|^2 is per column = per lane here.
 #include "mcq_common.h"
 #include "vq_common.h"
+#include "mcq_rng.h"
 #include "vq_bwd_mfma.h"
 #include "../../include/mcquic_hip.h"
 #include <math.h>
@@ -213,29 +214,8 @@ __global__ __launch_bounds__(256) void vq_logits_kernel(VqLogitK q) {
 // ---- uniform draws made inside the kernels (round 4) ------------------------------------------------------------------------
 // The reference draws two `torch.rand_like(logit)` tensors per level (quantizer.py:194-230): at the first level of a training
 // step that is 2 x 134 MB written by the generator and read back here (and the Gumbel draw once more in backward).  With
-// `rng_state` = {seed, offset} (two uint64 in device memory, so that a captured hipGraph sees a fresh offset on every replay)
-// the same numbers are made where they are used: u(stream, i) = a 24-bit uniform in [0, 1) from two rounds of a 32-bit
-// avalanche mixer over (seed, offset, stream, element index i = row * k + c) -- a counter-based generator: any kernel, any
-// thread layout and the backward pass reproduce element i's draw from its index alone.  Not torch's Philox stream (no RNG-stream
-// parity is promised by either side: the draws are i.i.d. uniforms); mcq_hash_uniform_f32 materialises them for tests.
-struct RngState { uint32_t s0, s1, o0, o1; };
-__device__ __forceinline__ RngState rng_load(const unsigned long long* st) {
-    RngState r = {0u, 0u, 0u, 0u};
-    if (st) {
-        const unsigned long long seed = st[0], off = st[1];
-        r.s0 = (uint32_t)seed; r.s1 = (uint32_t)(seed >> 32); r.o0 = (uint32_t)off; r.o1 = (uint32_t)(off >> 32);
-    }
-    return r;
-}
-__device__ __forceinline__ uint32_t rng_mix(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ float rng_uniform(const RngState& r, uint32_t stream, size_t idx) {
-    uint32_t h = rng_mix((uint32_t)idx ^ r.s0);
-    h = rng_mix(h + (uint32_t)((unsigned long long)idx >> 32) * 0x9E3779B1u + r.s1 + r.o0 * 0x85EBCA77u + r.o1 * 0x27D4EB2Fu + stream * 0xC2B2AE3Du);
-    return (float)(h >> 8) * 5.9604644775390625e-08f;            // k / 2^24, k in [0, 2^24): float32's own grid on [0, 1), like torch.rand
-}
+// `rng_state` = {seed, offset} the same numbers are made where they are used, element i = row * k + c of stream 0 (random drop)
+// or 1 (Gumbel noise): rng_uniform of mcq_rng.h, the generator every kernel of the library draws from.
 // element c of a row's draw: from the tensor the caller gave, or made here
 #define MCQ_U(ptr, stream, c) ((ptr) ? (ptr)[c] : rng_uniform(rng, (stream), rowbase + (size_t)(c)))
 

@@ -1076,6 +1076,93 @@ def detransform(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# ---- the training input transform (csrc/augment.hip) -----------------------------------------------------------------------------
+AUG_COLUMNS = 16
+(AUG_TOP, AUG_LEFT, AUG_H, AUG_W, AUG_GAMMA_MODE, AUG_GAMMA, AUG_GAIN0, AUG_GAIN2, AUG_HFLIP, AUG_VFLIP, AUG_GAIN_ROW,
+ AUG_FALLBACK, AUG_OUTPUT) = range(13)                                 # the MCQ_AUG_* columns of include/mcquic_hip.h
+AUG_GAMMA_SRGB_TO_LINEAR, AUG_GAMMA_LINEAR_TO_SRGB, AUG_GAMMA_POWER, AUG_GAMMA_IDENTITY = range(4)
+AUG_OUT_NORMALIZED, AUG_OUT_CLAMPED, AUG_OUT_RAW = range(3)     # what follows the gains: clamp + (v - 0.5) / 0.5, the clamp alone, neither
+
+
+def augment_identity_params(n: int, src_size, device=None) -> torch.Tensor:
+    """The table under which `augment` only resamples the whole [Hs, Ws] source: no gamma, gains of 1, no flips, then clamp and (v - 0.5) / 0.5 (a CPU tensor
+    unless `device` is given; a caller edits rows to fix decisions and moves it to the device)."""
+    t = torch.zeros((int(n), AUG_COLUMNS), dtype=torch.float32)
+    t[:, AUG_H], t[:, AUG_W] = float(src_size[0]), float(src_size[1])
+    t[:, AUG_GAMMA_MODE] = float(AUG_GAMMA_IDENTITY)
+    t[:, AUG_GAMMA] = t[:, AUG_GAIN0] = t[:, AUG_GAIN2] = 1.0
+    t[:, AUG_GAIN_ROW] = -1.0
+    return t if device is None else t.to(device)
+
+
+def augment_draw(rng: torch.Tensor, n: int, src_size, crop=None, gamma: bool = False, coeffs: Optional[torch.Tensor] = None,
+                 p_gain: float = 0.0, p_hflip: float = 0.0, p_vflip: float = 0.0, output: int = AUG_OUT_NORMALIZED) -> torch.Tensor:
+    """The decisions of the training input transform for `n` images of a [Hs, Ws] source as a device table [n, 16] float32
+    (mcq_augment_draw; columns AUG_*), drawn from `rng` = {seed, offset} (int64 [2] on the device), whose offset the launch
+    advances in place -- captured in a hipGraph, every replay draws a fresh table.  `crop` = (scale, ratio) of torchvision's
+    RandomResizedCrop or None (the whole source); `gamma`: draw one of RandomGamma's four modes; `coeffs` [T, 2]: with
+    probability `p_gain` the gains of one row (RandomPlanckianJitter); `p_hflip` / `p_vflip`: the flips; `output`: AUG_OUT_*."""
+    if not (torch.is_tensor(rng) and rng.is_cuda and rng.dtype == torch.int64 and rng.numel() == 2 and rng.is_contiguous()):
+        raise TypeError("augment_draw: `rng` must be a contiguous int64 [2] tensor {seed, offset} on a HIP device (it is advanced in place)")
+    hs, ws = int(src_size[0]), int(src_size[1])
+    if n <= 0 or hs <= 0 or ws <= 0:
+        raise ValueError(f"augment_draw: need a positive batch and source size, got n = {n}, source {hs}x{ws}")
+    (s0, s1), (r0, r1) = crop if crop is not None else ((1.0, 1.0), (1.0, 1.0))
+    if crop is not None and not (0.0 < s0 <= s1 and 0.0 < r0 <= r1):
+        raise ValueError(f"augment_draw: scale and ratio must be positive, ordered ranges, got {crop}")
+    t = 0
+    if coeffs is not None:
+        coeffs = _dev(coeffs.detach(), "coeffs")
+        if coeffs.dim() != 2 or coeffs.shape[1] != 2 or coeffs.shape[0] < 1 or coeffs.device != rng.device:
+            raise ValueError(f"augment_draw: `coeffs` must be a [T, 2] table of gains on the device of `rng`, got {tuple(coeffs.shape)}")
+        t = int(coeffs.shape[0])
+    for name, pr in (("p_gain", p_gain), ("p_hflip", p_hflip), ("p_vflip", p_vflip)):
+        if not 0.0 <= pr <= 1.0:
+            raise ValueError(f"augment_draw: `{name}` is a probability, got {pr}")
+    if output not in (AUG_OUT_NORMALIZED, AUG_OUT_CLAMPED, AUG_OUT_RAW):
+        raise ValueError(f"augment_draw: `output` must be one of AUG_OUT_*, got {output}")
+    params = torch.empty((int(n), AUG_COLUMNS), dtype=torch.float32, device=rng.device)
+    with _guard(rng.device):
+        check(_lib.load().mcq_augment_draw(_ptr(rng), _ptr(params), int(n), hs, ws, int(crop is not None), float(s0), float(s1), float(r0),
+                                           float(r1), int(bool(gamma)), _ptr(coeffs), t, float(p_gain), float(p_hflip), float(p_vflip),
+                                           int(output), _stream()), "mcq_augment_draw")
+    return params
+
+
+def augment(src: torch.Tensor, size, params: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[N, 3, Hs, Ws] uint8 (read as v / 255) or float32 in [0, 1] -> [N, 3, H, W] float32 under the table `params` [N, 16]
+    (augment_draw's, or a caller's): crop box resampled to `size` like F.interpolate(mode="bilinear", antialias=True) on the
+    crop, gamma, colour gains, clamp to [0, 1], flips, (v - 0.5) / 0.5 (column AUG_OUTPUT: a half of the pipeline stops earlier) -- one launch (mcq_augment_f32 / _u8).  `out`: write there."""
+    if not torch.is_tensor(src) or not src.is_cuda:
+        raise RuntimeError(f"mcquic_amd: `src` must live on a HIP device (got {getattr(src, 'device', type(src))}); "
+                           "the HIP kernels have no CPU fallback")
+    if src.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"augment: `src` must be uint8 or float32 (got {src.dtype})")
+    if src.dim() != 4 or src.shape[1] != 3:
+        raise ValueError(f"augment: `src` must be a [N, 3, Hs, Ws] batch, got {tuple(src.shape)}")
+    if not src.is_contiguous():
+        raise ValueError("augment: `src` must be contiguous (NCHW)")
+    n, _, hs, ws = src.shape
+    h, w = int(size[0]), int(size[1])
+    if h <= 0 or w <= 0:
+        raise ValueError(f"augment: the output size must be positive, got {h}x{w}")
+    if not torch.is_tensor(params) or not params.is_cuda or params.device != src.device:
+        raise RuntimeError("augment: `params` must live on the device of `src`; the HIP kernels have no CPU fallback")
+    if params.dtype != torch.float32:
+        raise TypeError(f"augment: `params` must be float32 (got {params.dtype})")
+    if tuple(params.shape) != (n, AUG_COLUMNS) or not params.is_contiguous():
+        raise ValueError(f"augment: `params` must be a contiguous [{n}, {AUG_COLUMNS}] table, got {tuple(params.shape)}")
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=src.device)
+    elif not (out.is_cuda and out.device == src.device and out.dtype == torch.float32 and tuple(out.shape) == (n, 3, h, w) and out.is_contiguous()):
+        raise ValueError(f"augment: `out` must be a contiguous float32 [{n}, 3, {h}, {w}] tensor on the device of `src`")
+    lib = _lib.load()
+    fn, name = (lib.mcq_augment_u8, "mcq_augment_u8") if src.dtype == torch.uint8 else (lib.mcq_augment_f32, "mcq_augment_f32")
+    with _guard(src.device):
+        check(fn(_ptr(src), _ptr(params), _ptr(out), n, hs, ws, h, w, _stream()), name)
+    return out
+
+
 # ---- validation metrics (mcquic/validate/handlers.py) ----------------------------------------------------------
 def _u8_pair(x: torch.Tensor, y: torch.Tensor):
     x, y = _dev(x, "x", torch.uint8), _dev(y, "y", torch.uint8)

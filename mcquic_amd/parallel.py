@@ -253,6 +253,10 @@ class GraphedTrainStep:
     A captured update bakes in whatever the optimizer read on the host at capture time: give a scheduled learning rate to the
     optimizer as a TENSOR (torch.optim reads it on the device then; Adam / AdamW additionally need `capturable=True`), or pass
     `capture_post=False` and the update (with the EMA) runs eagerly after the exchange -- ~15 launches, still no per-layer host work.
+    `transform` (a `data.transforms.TrainingInput`, or any `utils.vision.Augment`): `example_x` and every later `x` are RAW batches
+    (uint8 or float32 at source size); the transform's two launches are captured at the head of the first segment and write the
+    model's input, which is also the `x` that `loss_fn` sees.  Each replay draws fresh decisions on the device
+    (`transform.last_params` is the table of the last step); the generator's {seed, offset} is in `transform.state_dict()`.
     `max_grad_norm` clips the averaged gradient by its global norm in front of the update (the reference's step does,
     mcquic/train/trainer.py:280; torch.nn.utils.clip_grad_norm_'s arithmetic over the flat buffer, on the device); the norm before
     clipping is `step.grad_norm` (a 0-dim device tensor, valid after each call).
@@ -260,12 +264,18 @@ class GraphedTrainStep:
 
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
-                 broadcast: bool = True, max_grad_norm: float | None = None):
+                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None):
         if not example_x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
         self.model, self.optimizer, self.group = model, optimizer, group
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.x = example_x.detach().clone()
+        self.transform, self.raw = transform, None
+        if transform is not None:                             # the static input holds RAW images; the transform's two launches write self.x
+            self.raw = self.x
+            self.transform = transform.to(self.raw.device)    # (its generator state and gain table: on the device before any capture)
+            with torch.no_grad():
+                self.x = self.transform(self.raw).detach()
         self.kwargs = dict(forward_kwargs or {})
         staged = all(hasattr(model, a) for a in ("_encoder", "_quantizer", "_decoder", "_repackStale")) and set(self.kwargs) <= {"uniforms"}
         if segments is None:
@@ -499,6 +509,7 @@ class GraphedTrainStep:
         if k == 0:
             for p in self.params:
                 p.grad = None
+            self._input()
             m._repackStale()
             y = m._trainEncode(self.x) if hasattr(m, "_trainEncode") else m._encoder(self.x)     # (no padding in the training forward, compressor.py:39)
             yl = y.detach().requires_grad_()
@@ -531,9 +542,16 @@ class GraphedTrainStep:
             run_backward([y], [yl.grad])                      # encoder parameters
             self._carry = None
 
+    def _input(self):
+        """With a transform: the draw and the apply launch, from the static raw batch into the model's static input."""
+        if self.transform is not None:
+            with torch.no_grad():
+                self.transform(self.raw, out=self.x)
+
     def _forward_backward(self):
         for p in self.params:
             p.grad = None
+        self._input()
         out = self.model(self.x, **self.kwargs)
         loss = self.loss_fn(out, self.x)
         _backward(loss)
@@ -566,9 +584,12 @@ class GraphedTrainStep:
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         if self.closed:
             raise RuntimeError("GraphedTrainStep: the step was closed (its count sinks are gone); build a new one")
-        if tuple(x.shape) != tuple(self.x.shape):             # (`copy_` would BROADCAST a smaller batch into the static input silently)
-            raise RuntimeError(f"GraphedTrainStep was captured for shards of shape {tuple(self.x.shape)}, got {tuple(x.shape)}")
-        self.x.copy_(x, non_blocking=True)
+        static = self.x if self.raw is None else self.raw
+        if tuple(x.shape) != tuple(static.shape):             # (`copy_` would BROADCAST a smaller batch into the static input silently)
+            raise RuntimeError(f"GraphedTrainStep was captured for shards of shape {tuple(static.shape)}, got {tuple(x.shape)}")
+        if self.raw is not None and x.dtype != static.dtype:  # (`copy_` would convert a uint8 batch to float without the / 255)
+            raise RuntimeError(f"GraphedTrainStep was captured for {static.dtype} shards, got {x.dtype}")
+        static.copy_(x, non_blocking=True)
         works = []
         for k, g in enumerate(self.graphs):
             g.replay()
