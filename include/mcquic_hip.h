@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   10
+#define MCQ_ABI_VERSION   11
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -213,6 +213,35 @@ int mcq_vq_assign_ws_f32(const float* x, const float* cb_packed, int64_t* codes,
 int mcq_vq_gather_f32(const int64_t* codes, const float* codebook, float* out, float* out_silu /* or NULL */,
                       int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k,
                       void* stream);
+
+/* ---- k-means on the device: the accumulate / update / reseed half of a Lloyd iteration (csrc/vq_kmeans.hip) ------------- */
+/* Layouts are mcq_vq_assign_f32's: x [N, m*d, h, w] (channel = g*d + j), codes int64 [N, m, h, w], codebook the plain [m, k, d]
+ * parameter (not the packed stream); V = N*h*w latent vectors per group.  Accumulators: sums double [m, k, d], sqsums double
+ * [m, k], counts int64 [m, k].  Every entry returns MCQ_EINVAL before any launch for a NULL pointer or a non-positive size;
+ * any d, k, m, V >= 1 is taken (V and m*k below 2^31). */
+
+/* sums = 0, sqsums = 0, counts = 0 (a kernel: safe inside a captured graph, like every other zeroing here). */
+int mcq_vq_kmeans_zero(double* sums, double* sqsums, int64_t* counts, int32_t m, int32_t k, int32_t d, void* stream);
+
+/* Adds one batch: sums[g, c, :] += sum of the x_v with codes == c, sqsums[g, c] += sum of |x_v|^2, counts[g, c] += their number.
+ * Each codeword is owned by one workgroup: no atomics, and every sum runs over ascending vector index (n, y, x) inside up to 16
+ * contiguous segments that are folded in segment order; the segment count follows from (m, k, V) alone, so two calls on the
+ * same inputs give identical bits.  A vector whose code lies outside [0, k) is skipped. */
+int mcq_vq_kmeans_accumulate_f32(const float* x, const int64_t* codes, double* sums, double* sqsums, int64_t* counts,
+                                 int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, void* stream);
+
+/* In place on the codebook: where counts[g, c] > 0, codebook[g, c, :] = float32(sums / counts); other codewords stay as they are
+ * and empty[g] (int64 [m]) counts them.  inertia[g] (double [m]) = sum over c ascending of
+ * sqsums - 2 <c_old, sums> + counts |c_old|^2: the within-cluster sum of squares against the codewords the codes were made with. */
+int mcq_vq_kmeans_update_f32(float* codebook, const double* sums, const double* sqsums, const int64_t* counts, double* inertia,
+                             int64_t* empty, int32_t m, int32_t k, int32_t d, void* stream);
+
+/* codebook[g, c, :] = latent vector number min(V - 1, floor(u V)) of group g, u = the generator's draw for stream 2, element
+ * g*k + c under rng_state = {seed, offset} in device memory (what mcq_hash_uniform_f32(rng_state, 2, ...) returns there; the
+ * product is taken in double, where it is exact) -- for every (g, c) when counts is NULL (Forgy seeding), otherwise for those
+ * with counts[g, c] == 0 (reseeding empty clusters).  The caller advances the offset between calls, on the device. */
+int mcq_vq_kmeans_seed_f32(const float* x, float* codebook, const int64_t* counts_or_null, const uint64_t* rng_state,
+                           int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, void* stream);
 
 /* ---- training-mode quantizer forward (BASELINE config #5, forward half) ------------------------------ */
 

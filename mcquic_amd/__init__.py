@@ -18,6 +18,7 @@ _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 
 from .modules.compressor import BaseCompressor, Compressor, Neon  # noqa: E402
 from . import loss  # noqa: E402,F401  (training losses: MsSSIM, PSNR, step_loss)
+from . import kmeans  # noqa: E402,F401  (fit_codebooks: data-dependent codebooks by k-means on the device)
 
-__all__ = ["BaseCompressor", "Compressor", "Neon", "loss"]
+__all__ = ["BaseCompressor", "Compressor", "Neon", "loss", "kmeans"]
 __version__ = "0.1.0"

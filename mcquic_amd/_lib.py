@@ -74,6 +74,10 @@ SYMBOLS = {
     "mcq_vq_assign_ws_f32": (c_int32, [c_void_p, c_void_p, c_void_p] + [c_int32] * 6 + [c_void_p, c_void_p]),
     "mcq_vq_gather_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_int32, c_void_p]),
+    "mcq_vq_kmeans_zero": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "mcq_vq_kmeans_accumulate_f32": (c_int32, [c_void_p] * 5 + [c_int32] * 6 + [c_void_p]),
+    "mcq_vq_kmeans_update_f32": (c_int32, [c_void_p] * 6 + [c_int32] * 3 + [c_void_p]),
+    "mcq_vq_kmeans_seed_f32": (c_int32, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p]),
     "mcq_vq_logits_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_int32, c_void_p]),
     "mcq_vq_gumbel_sample_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -168,7 +172,7 @@ SYMBOLS = {
     "mcq_abi_version": (c_int32, []),
 }
 
-ABI_VERSION = 10         # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
+ABI_VERSION = 11         # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
 
 _lib = None
 

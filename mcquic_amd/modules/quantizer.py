@@ -198,26 +198,34 @@ class _quantizerEncoder(nn.Module):
         return self._quantizer.reAssignCodebook(freq)
 
     def encode(self, x: torch.Tensor):
+        residual, code, _ = self._encode(x)
+        return residual, code
+
+    def _encode(self, x: torch.Tensor):
+        """(residual for the next level or None, code, the tensor `_quantizer.encode` received)."""
         from ..nn import blocks
         z = self._latentStageEncoder(x)
         head = self._latentHead
         if head is None:
-            return None, self._quantizer.encode(self._quantizationHead(z))
+            qin = self._quantizationHead(z)
+            return None, self._quantizer.encode(qin), qin
         if blocks.lockstep_ok([self._quantizationHead, head], [z, z]):
             # latentHead(z) does not depend on the codes until its closing conv: everything before that runs in lockstep with
             # quantizationHead (same layer shapes on the same z: one multi-problem launch per layer, four problems in the
             # AttentionBlocks)
             last = len(head) - 1
             q, t = blocks.lockstep_infer([self._quantizationHead, head], [z, z], layers=last)
-            code = self._quantizer.encode(self._quantizationHead[last](q))
+            qin = self._quantizationHead[last](q)
+            code = self._quantizer.encode(qin)
         else:
-            code = self._quantizer.encode(self._quantizationHead(z))
+            qin = self._quantizationHead(z)
+            code = self._quantizer.encode(qin)
             t = z
             for i in range(len(head) - 1):
                 t = head[i](t)
         deq = self._dequantizer.decode(code)
         # z' - dequant(code): the subtraction is the epilogue of latentHead's closing conv3x3 (:318)
-        return head[len(head) - 1](t, res=deq, res_scale=-1.0, dual_silu=True), code
+        return head[len(head) - 1](t, res=deq, res_scale=-1.0, dual_silu=True), code, qin
 
 
     def _forward(self, x: torch.Tensor, freqEMA: torch.Tensor, uniforms=None, step=None):
@@ -358,6 +366,16 @@ class UMGMQuantizer(BaseQuantizer):
             x, code = encoder.encode(x)
             codes.append(code)
         return codes
+
+    def quantizerInputs(self, y: torch.Tensor) -> List[torch.Tensor]:
+        """What each level's `_quantizer.encode` receives on the inference path under the current codebooks: `encode`'s cascade
+        (the very same launches, lockstep paths included) with the quantization heads' outputs kept -- the data a level's codebook
+        is fitted to (mcquic_amd.kmeans)."""
+        inputs = []
+        for encoder in self._encoders:
+            y, _, qin = encoder._encode(y)
+            inputs.append(qin)
+        return inputs
 
     def compress(self, x: torch.Tensor):
         """`encode` + the entropy coder (mcquic/modules/entropyCoder.py:108-126) with the coder taken level by level: a level's codes

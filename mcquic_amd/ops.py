@@ -908,6 +908,91 @@ def hash_uniform(rng: torch.Tensor, stream_id: int, shape) -> torch.Tensor:
     return out
 
 
+# ---- k-means on the device (csrc/vq_kmeans.hip): what turns ops.vq_assign's codes into new codewords -------------------------------
+class KMeansAcc:
+    """The running accumulators of one level's Lloyd iteration: `sums` float64 [m, k, d], `sqsums` float64 [m, k] and `counts`
+    int64 [m, k], one allocation each, zeroed at construction and by `zero_()` (mcq_vq_kmeans_zero: a kernel, not a memset)."""
+
+    __slots__ = ("sums", "sqsums", "counts", "m", "k", "d")
+
+    def __init__(self, m: int, k: int, d: int, device):
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError(f"mcquic_amd: KMeansAcc must live on a HIP device (got {device}); the HIP kernels have no CPU fallback")
+        self.m, self.k, self.d = int(m), int(k), int(d)
+        self.sums = torch.empty((self.m, self.k, self.d), dtype=torch.float64, device=device)
+        self.sqsums = torch.empty((self.m, self.k), dtype=torch.float64, device=device)
+        self.counts = torch.empty((self.m, self.k), dtype=torch.int64, device=device)
+        self.zero_()
+
+    def zero_(self) -> "KMeansAcc":
+        with _guard(self.sums.device):
+            check(_lib.load().mcq_vq_kmeans_zero(_ptr(self.sums), _ptr(self.sqsums), _ptr(self.counts), self.m, self.k, self.d, _stream()),
+                  "mcq_vq_kmeans_zero")
+        return self
+
+
+def _kmeans_latent(x: torch.Tensor, m: int, d: int) -> torch.Tensor:
+    x = _dev(x, "x")
+    if x.dim() != 4 or x.shape[1] != m * d:
+        raise ValueError(f"latent must be [n, {m}*{d}, h, w], got {tuple(x.shape)}")
+    return x
+
+
+def _kmeans_codebook(codebook: torch.Tensor) -> torch.Tensor:
+    cb = _dev(codebook, "codebook")
+    if cb.dim() != 3 or cb.data_ptr() != codebook.data_ptr():
+        raise ValueError("codebook must be a contiguous [m, k, d] tensor (it is written in place)")
+    return cb
+
+
+def vq_kmeans_accumulate(x: torch.Tensor, codes: torch.Tensor, acc: KMeansAcc) -> None:
+    """Adds one batch onto `acc`: per codeword the sum of the latent vectors `x` [n, m*d, h, w] whose code (`codes` int64
+    [n, m, h, w], ops.vq_assign's layout) it is, the sum of their squared norms and their number; codes outside [0, k) are skipped.
+    No atomics, one fixed order per sum: bit-reproducible (mcq_vq_kmeans_accumulate_f32)."""
+    x = _kmeans_latent(x, acc.m, acc.d)
+    codes = _dev(codes, "codes", torch.int64)
+    n, _, h, w = x.shape
+    if tuple(codes.shape) != (n, acc.m, h, w):
+        raise ValueError(f"codes must be [{n}, {acc.m}, {h}, {w}], got {tuple(codes.shape)}")
+    with _guard(x.device):
+        check(_lib.load().mcq_vq_kmeans_accumulate_f32(_ptr(x), _ptr(codes), _ptr(acc.sums), _ptr(acc.sqsums), _ptr(acc.counts), n, acc.m,
+                                                       acc.d, h, w, acc.k, _stream()), "mcq_vq_kmeans_accumulate_f32")
+
+
+def vq_kmeans_update(codebook: torch.Tensor, acc: KMeansAcc):
+    """In place on `codebook` [m, k, d]: the mean of every codeword that was assigned a vector; the others stay as they are.
+    Returns (inertia float64 [m] against the old codewords, empty int64 [m] = codewords left untouched), both on the device
+    (mcq_vq_kmeans_update_f32).  The caller tells whoever caches the codebook (`_multiCodebookQuantization._store`)."""
+    cb = _kmeans_codebook(codebook)
+    if tuple(cb.shape) != (acc.m, acc.k, acc.d):
+        raise ValueError(f"codebook must be [{acc.m}, {acc.k}, {acc.d}], got {tuple(cb.shape)}")
+    inertia = torch.empty(acc.m, dtype=torch.float64, device=cb.device)
+    empty = torch.empty(acc.m, dtype=torch.int64, device=cb.device)
+    with _guard(cb.device):
+        check(_lib.load().mcq_vq_kmeans_update_f32(_ptr(cb), _ptr(acc.sums), _ptr(acc.sqsums), _ptr(acc.counts), _ptr(inertia), _ptr(empty),
+                                                   acc.m, acc.k, acc.d, _stream()), "mcq_vq_kmeans_update_f32")
+    return inertia, empty
+
+
+def vq_kmeans_seed(x: torch.Tensor, codebook: torch.Tensor, rng: torch.Tensor, counts: Optional[torch.Tensor] = None) -> None:
+    """In place on `codebook` [m, k, d]: codeword (g, c) becomes latent vector min(V - 1, floor(u V)) of group g of `x`, u =
+    hash_uniform(rng, 2, (m, k))[g, c] -- every codeword (`counts` None), or those with counts[g, c] == 0.  `rng` is a {seed, offset}
+    int64[2] device tensor; the caller moves its offset on between calls (mcq_vq_kmeans_seed_f32)."""
+    cb = _kmeans_codebook(codebook)
+    m, k, d = cb.shape
+    x = _kmeans_latent(x, m, d)
+    rng = _dev(rng, "rng", torch.int64)
+    if counts is not None:
+        counts = _dev(counts, "counts", torch.int64)
+        if counts.numel() != m * k:
+            raise ValueError("vq_kmeans_seed: `counts` must hold m * k entries")
+    n, _, h, w = x.shape
+    with _guard(x.device):
+        check(_lib.load().mcq_vq_kmeans_seed_f32(_ptr(x), _ptr(cb), _ptr(counts), _ptr(rng), n, m, d, h, w, k, _stream()),
+              "mcq_vq_kmeans_seed_f32")
+
+
 def vq_gumbel_sample(logits: torch.Tensor, u_drop: Optional[torch.Tensor], u_gumbel: Optional[torch.Tensor], freq_ema: torch.Tensor,
                      drop_exponent: torch.Tensor, rng: Optional[torch.Tensor] = None, counts: Optional[torch.Tensor] = None):
     """In place on `logits`: random drop; returns (codes, sample_index, sample_hot), each [n, m, h, w].  A draw that is None is
