@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   11
+#define MCQ_ABI_VERSION   12
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -470,6 +470,26 @@ int mcq_lamb_step_f32(const void* ptr_tables, int32_t ntensors, const int64_t* n
                       float* step, const float* lr_dev /* or NULL */, double lr, double beta1, double beta2, double eps, double weight_decay,
                       int32_t bias_correction, int32_t adam_w_mode, int32_t grad_averaging, int32_t use_nvlamb, double max_grad_norm,
                       float* grad_norm, float* ratios, void* workspace, void* scalars, void* stream);
+
+/* SGD over a whole model in one launch (the `self._optimizer.step()` of mcquic/train/trainer.py:283 with the reference's `"SGD"`
+ * registry entry, mcquic/train/ddp.py:53-69; torch.optim.SGD's arithmetic per element in float32: g = maximize ? -grad : grad;
+ * g += weight_decay p; with momentum buf = g on the update where `step` was 0, else buf = momentum buf + (1 - dampening) g, and
+ * g = nesterov ? g + momentum buf : buf; p -= lr g).  Tables, `step`, `lr_dev` / `lr` and `scalars` as for mcq_adam_step_f32; row 2 of
+ * ptr_tables holds the momentum buffers (read only when momentum != 0), row 3 is not read.  Two launches: a scalar kernel and one pass
+ * over 12 bytes per element (20 with momentum), 16 bytes per lane where all of a tensor's addresses are 16-byte aligned.
+ * With `grad_partials` (n_grad_partials doubles from mcq_lamb_grad_partials_f32, every parameter group's in one array: a third
+ * launch, in front) the scalar kernel sums them in a fixed order -> G, written to grad_norm[0], and
+ *   max_grad_norm (device float, or NULL)  grad is multiplied by min(1, max_grad_norm / (G + 1e-6)) before everything else
+ *                                          (torch.nn.utils.clip_grad_norm_'s arithmetic; the gradients themselves are only read);
+ *   skip_nonfinite                         when G is not finite the call changes no parameter, no buffer and not `step`, and adds 1 to
+ *                                          skipped[0] (device int64, or NULL: a caller with several parameter groups counts a call
+ *                                          once); every workgroup reads the flag on the device.
+ * Without grad_partials all three must be 0 / NULL.  No atomics: equal inputs give equal bits.  Nothing is read by the host. */
+int mcq_sgd_step_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                     int32_t nblocks, float* step, const float* lr_dev /* or NULL */, double lr, double momentum, double dampening,
+                     double weight_decay, int32_t nesterov, int32_t maximize, const double* grad_partials /* or NULL */,
+                     int32_t n_grad_partials, const float* max_grad_norm /* or NULL */, float* grad_norm /* or NULL without grad_partials */,
+                     int32_t skip_nonfinite, int64_t* skipped /* or NULL */, void* scalars, void* stream);
 
 /* u8 = trunc(clamp(((x + 1) / 2) * 255.999, 0, 255))   (mcquic/utils/vision.py:143-146 DeTransform). */
 int mcq_detransform_u8(const float* x, uint8_t* out, int64_t n, void* stream);

@@ -11,7 +11,12 @@ call (a scheduler fills it; a captured step needs no re-capture), and nothing is
 `parallel.GraphedTrainStep` captures it like any capturable optimizer.  float32 parameters on a HIP device only: there is no CPU path.
 
 `Lamb` (alias `FusedLAMB`) is the reference's third optimizer (mcquic/train/ddp.py:53-69, apex FusedLAMB's arithmetic) on the same tables
-and flat moment buffers: csrc/lamb.hip, five launches; `REGISTRY` maps the reference's `optim.key` names to these classes."""
+and flat moment buffers: csrc/lamb.hip, five launches; `REGISTRY` maps the reference's `optim.key` names to these classes.
+
+`SGD` is torch.optim.SGD's arithmetic and checkpoint layout on the same tables with one flat momentum buffer (none without momentum):
+csrc/sgd.hip, the scalar kernel plus one pass; `max_grad_norm=` (clip_grad_norm_'s arithmetic) and `skip_nonfinite=` (a call whose
+gradient norm is inf or NaN changes nothing and is counted in `skipped`) add one pass over the gradients.  `REGISTRY["SGD"]` stays
+torch.optim.SGD, as the reference's registry has it: opt in by building `mcquic_amd.optim.SGD(model.parameters(), ...)` yourself."""
 from __future__ import annotations
 
 import torch
@@ -19,43 +24,52 @@ import torch
 from . import _lib
 from .ops import check, _guard, _stream
 
-__all__ = ["Adam", "AdamW", "Lamb", "FusedLAMB", "REGISTRY"]
+__all__ = ["Adam", "AdamW", "Lamb", "FusedLAMB", "SGD", "REGISTRY"]
 
 
 class _Planned(torch.optim.Optimizer):
-    """What the optimizers of this module share: both moments in two flat buffers the object owns, and the device tables (pointers,
-    sizes, chunks) the kernels walk, built once per parameter group and refilled only when an address changes."""
+    """What the optimizers of this module share: the per-parameter state (`_state_names`: both moments, or SGD's momentum buffer, or
+    nothing) in flat buffers the object owns, one per name, and the device tables (pointers, sizes, chunks) the kernels walk, built once
+    per parameter group and refilled only when an address changes."""
     _NAME = "?"
+
+    def _state_names(self, group) -> tuple:
+        """The per-parameter state tensors of `group`, by their names in `state_dict()`: one flat buffer each (at most two)."""
+        return ("exp_avg", "exp_avg_sq")
 
     def __init__(self, params, defaults):
         super().__init__(params, defaults)
         self._plans = {}                                      # group index -> _Plan
+        self._norm = None                                     # (see `_planned`)
 
     # ---- state in flat buffers -------------------------------------------------------------------------------------------------
     class _Plan:
         __slots__ = ("key", "tables", "numel", "blk_tensor", "blk_first", "nblocks", "flat_m", "flat_v", "views", "step", "scalars", "ntensors",
-                     "sizes", "ids", "adopted")
+                     "sizes", "ids", "adopted", "names")
 
     def _flat_state(self, gi: int, params):
-        """(flat_m, flat_v, [(m_view, v_view)], step) of group `gi` for `params`; state found in `self.state` that does not live in
-        the flat buffers (loaded from a checkpoint, or set by hand) is copied in and replaced by views."""
+        """The plan of group `gi` for `params`: `flat_m` / `flat_v` (the flat buffers of the group's first / second state name, None where
+        there is none), `views` [one tuple of views per parameter], `step`; state found in `self.state` that does not live in the flat
+        buffers (loaded from a checkpoint, or set by hand) is copied in and replaced by views."""
         plan = self._plans.get(gi)
         ids = [id(p) for p in params]
-        if plan is not None and plan.ids == ids and plan.adopted and plan.flat_m.device == params[0].device:
+        names = tuple(self._state_names(self.param_groups[gi]))
+        same = plan is not None and plan.ids == ids and plan.names == names and plan.step.device == params[0].device
+        if same and plan.adopted:
             return plan
         sizes = [p.numel() for p in params]
-        if plan is None or plan.ids != ids or plan.flat_m.device != params[0].device:
+        if not same:
             # (also when the set of parameters that carry a gradient changed: fresh buffers, the old state is copied over below)
             plan = self._plans[gi] = type(self)._Plan()
             dev = params[0].device
-            plan.sizes, plan.ids = sizes, ids
+            plan.sizes, plan.ids, plan.names = sizes, ids, names
             offs, at = [], 0
             for n in sizes:
                 offs.append(at)
                 at += (n + 3) // 4 * 4                        # 16-byte aligned slices
-            plan.flat_m = torch.zeros(at, dtype=torch.float32, device=dev)
-            plan.flat_v = torch.zeros(at, dtype=torch.float32, device=dev)
-            plan.views = [(plan.flat_m[o: o + n].view_as(p), plan.flat_v[o: o + n].view_as(p)) for o, n, p in zip(offs, sizes, params)]
+            flats = [torch.zeros(at, dtype=torch.float32, device=dev) for _ in names]
+            plan.flat_m, plan.flat_v = (flats + [None, None])[:2]
+            plan.views = [tuple(f[o: o + n].view_as(p) for f in flats) for o, n, p in zip(offs, sizes, params)]
             plan.step = torch.zeros((), dtype=torch.float32, device=dev)
             plan.scalars = torch.zeros(4, dtype=torch.float32, device=dev)
             plan.ntensors, plan.key = len(params), None
@@ -73,16 +87,17 @@ class _Planned(torch.optim.Optimizer):
             plan.nblocks = len(blk_t)
             plan.tables = torch.zeros(4 * len(params), dtype=torch.int64, device=dev)
             self._extend_plan(plan, blk_t, dev)
-        for p, (mv, vv) in zip(params, plan.views):
+        for p, views in zip(params, plan.views):
             st = self.state[p]
-            old_m, old_v, old_s = st.get("exp_avg"), st.get("exp_avg_sq"), st.get("step")
-            if old_m is not None and old_m.data_ptr() != mv.data_ptr():
-                mv.copy_(old_m.to(mv.device, torch.float32))
-            if old_v is not None and old_v.data_ptr() != vv.data_ptr():
-                vv.copy_(old_v.to(vv.device, torch.float32))
+            for name, view in zip(names, views):
+                old = st.get(name)
+                if old is not None and old.data_ptr() != view.data_ptr():
+                    view.copy_(old.to(view.device, torch.float32))
+                st[name] = view
+            old_s = st.get("step")
             if old_s is not None and old_s is not plan.step:  # (torch keeps one count per parameter; they move together)
                 plan.step.copy_(torch.as_tensor(old_s, dtype=torch.float32).to(plan.step.device))
-            st["exp_avg"], st["exp_avg_sq"], st["step"] = mv, vv, plan.step
+            st["step"] = plan.step
         plan.adopted = True
         return plan
 
@@ -96,8 +111,9 @@ class _Planned(torch.optim.Optimizer):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError(f"mcquic_amd.optim.{self._NAME}: parameter / gradient addresses changed since the last step; call `prepare()` "
                                "before capturing (a host-to-device copy of the pointer table cannot be part of a graph)")
-        ptrs = [p.data_ptr() for p in params] + [p.grad.data_ptr() for p in params] + [m.data_ptr() for m, _ in plan.views] + \
-               [v.data_ptr() for _, v in plan.views]
+        ptrs = [p.data_ptr() for p in params] + [p.grad.data_ptr() for p in params]
+        for k in range(2):                                    # (rows of a state the group does not have stay 0: no kernel reads them)
+            ptrs += [views[k].data_ptr() if k < len(views) else 0 for views in plan.views]
         plan.tables.copy_(torch.tensor(ptrs, dtype=torch.int64))          # (stream-ordered behind the launches that read the old one)
         plan.key = key
 
@@ -115,12 +131,34 @@ class _Planned(torch.optim.Optimizer):
 
     @torch.no_grad()
     def prepare(self) -> None:
-        """Build the moment buffers and the device tables for the gradients the parameters hold NOW, without updating anything: what
+        """Build the state buffers and the device tables for the gradients the parameters hold NOW, without updating anything: what
         `parallel.GraphedTrainStep` calls before it captures `step()` (table uploads are host-to-device copies)."""
+        self._planned()
+
+    def _wants_norm(self) -> bool:
+        return False
+
+    def _planned(self):
+        """[(group, plan)] of the groups that hold gradients, tables current, and -- for an optimizer that `_wants_norm()` -- the buffers
+        of the gradient norm they share: `self._norm` = (key, double partials of sum g^2 for all groups, G)."""
+        live = []
         for gi, group in enumerate(self.param_groups):
             params = self._checked(group)
             if params:
-                self._tables(self._flat_state(gi, params), params)
+                if live and self._wants_norm() and params[0].device != live[0][2][0].device:
+                    raise RuntimeError(f"mcquic_amd.optim.{self._NAME}: all param groups must live on one device (the gradient norm spans them)")
+                live.append((gi, group, params))
+        out = []
+        for gi, group, params in live:
+            plan = self._flat_state(gi, params)
+            self._tables(plan, params)
+            out.append((group, plan))
+        key = tuple((id(plan), plan.nblocks) for _, plan in out)
+        if out and self._wants_norm() and (self._norm is None or self._norm[0] != key):
+            dev = out[0][1].step.device
+            gnorm = self._norm[2] if self._norm is not None and self._norm[2].device == dev else torch.zeros((), dtype=torch.float32, device=dev)
+            self._norm = (key, torch.zeros(max(sum(plan.nblocks for _, plan in out), 1), dtype=torch.float64, device=dev), gnorm)
+        return out
 
     def _rate(self, group):
         """(device tensor or None, host value) of a group's learning rate."""
@@ -246,10 +284,12 @@ class Lamb(_Planned):
                                       grad_averaging=bool(grad_averaging), max_grad_norm=max_grad_norm, adam_w_mode=bool(adam_w_mode),
                                       use_nvlamb=bool(use_nvlamb), capturable=True))
         self.set_grad_none = bool(set_grad_none)
-        self._norm = None                                     # (key, double partials of sum g^2 for all groups, G)
 
     def zero_grad(self, set_to_none=None):
         super().zero_grad(self.set_grad_none if set_to_none is None else set_to_none)
+
+    def _wants_norm(self) -> bool:
+        return True
 
     def _extend_plan(self, plan, blk_t, dev) -> None:
         first, at = [0], 0
@@ -261,32 +301,6 @@ class Lamb(_Planned):
         nbytes = _lib.load().mcq_lamb_workspace_bytes(plan.ntensors, max(plan.nblocks, 1))
         plan.workspace = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         plan.ratios = torch.zeros(plan.ntensors, dtype=torch.float32, device=dev)
-
-    def _planned(self):
-        """[(group, plan)] of the groups that hold gradients, tables current, and the buffers of the gradient norm they share."""
-        live = []
-        for gi, group in enumerate(self.param_groups):
-            params = self._checked(group)
-            if params:
-                if live and params[0].device != live[0][2][0].device:
-                    raise RuntimeError("mcquic_amd.optim.Lamb: all param groups must live on one device (the gradient norm spans them)")
-                live.append((gi, group, params))
-        out = []
-        for gi, group, params in live:
-            plan = self._flat_state(gi, params)
-            self._tables(plan, params)
-            out.append((group, plan))
-        key = tuple((id(plan), plan.nblocks) for _, plan in out)
-        if out and (self._norm is None or self._norm[0] != key):
-            dev = out[0][1].flat_m.device
-            gnorm = self._norm[2] if self._norm is not None and self._norm[2].device == dev else torch.zeros((), dtype=torch.float32, device=dev)
-            self._norm = (key, torch.zeros(max(sum(plan.nblocks for _, plan in out), 1), dtype=torch.float64, device=dev), gnorm)
-        return out
-
-    @torch.no_grad()
-    def prepare(self) -> None:
-        """As `Adam.prepare`, for every group at once (the norm's buffers depend on all of them)."""
-        self._planned()
 
     @property
     def grad_norm(self) -> torch.Tensor:
@@ -357,6 +371,138 @@ class Lamb(_Planned):
             for k in ("bias_correction", "grad_averaging", "max_grad_norm", "adam_w_mode", "use_nvlamb"):
                 group.setdefault(k, self.defaults[k])         # (apex keeps adam_w_mode / use_nvlamb on the object, not in the groups)
             group["capturable"] = True
+        for plan in self._plans.values():
+            plan.adopted = False
+
+
+class SGD(_Planned):
+    """torch.optim.SGD(params, lr, momentum, dampening, weight_decay, nesterov, maximize=...) without `foreach` / `fused` /
+    `differentiable`: csrc/sgd.hip, the whole parameter group in one launch behind a one-thread kernel.  Per element, in float32:
+
+      g = -grad if maximize else grad;  g += weight_decay p;
+      with momentum: buf = g on the first update, else buf = momentum buf + (1 - dampening) g;  g = g + momentum buf if nesterov else buf;
+      p -= lr g.
+
+    The momentum buffers are views of ONE flat buffer (none is allocated without momentum).  Two options add one pass over the gradients,
+    the per-chunk sums of g^2 over every parameter that has a gradient, in EVERY group, summed on the device to the norm G:
+      max_grad_norm   every gradient enters as grad * min(1, max_grad_norm / (G + 1e-6)): torch.nn.utils.clip_grad_norm_ in front of the
+                      step, without touching the gradients;
+      skip_nonfinite  a call whose G is inf or NaN changes no parameter, no buffer and no step count; `skipped` counts such calls.
+    Nothing is read by the host: `grad_norm()` and `skipped` are device tensors.  `state_dict()` / `load_state_dict()` exchange checkpoints
+    with torch.optim.SGD (`momentum_buffer` per parameter, nothing without momentum).  torch keeps no step count: a loaded buffer means
+    "not the first update"; a group loaded without any buffer starts with one (parameters that lack a buffer while others of their
+    group have one start from zeros)."""
+    _NAME = "SGD"
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, *, maximize: bool = False,
+                 max_grad_norm=None, skip_nonfinite: bool = False):
+        if torch.is_tensor(lr) and lr.numel() != 1:
+            raise ValueError("Tensor lr must be 1-element")
+        if not torch.is_tensor(lr) and not lr >= 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not momentum >= 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if not weight_decay >= 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        if max_grad_norm is not None and not max_grad_norm > 0.0:
+            raise ValueError(f"Invalid max_grad_norm: {max_grad_norm} (positive, or None: no clipping)")
+        # (the keys torch.optim.SGD's step reads from a loaded group travel with ours)
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
+                                      maximize=bool(maximize), foreach=None, differentiable=False, fused=None))
+        self.max_grad_norm, self.skip_nonfinite = max_grad_norm, bool(skip_nonfinite)
+        self._bound = self._skipped = None                    # device tensors: the clip bound, the count of skipped calls
+
+    def _state_names(self, group) -> tuple:
+        return ("momentum_buffer",) if group["momentum"] != 0 else ()
+
+    def _wants_norm(self) -> bool:
+        return self.max_grad_norm is not None or self.skip_nonfinite
+
+    def _planned(self):
+        out = super()._planned()
+        if out:                                               # (created here, outside any capture: `prepare()` comes through)
+            dev = out[0][1].step.device
+            if self.max_grad_norm is not None and (self._bound is None or self._bound.device != dev):
+                self._bound = torch.tensor(float(self.max_grad_norm), dtype=torch.float32).to(dev)
+            if self._skipped is None or self._skipped.device != dev:
+                self._skipped = torch.zeros((), dtype=torch.int64, device=dev) if self._skipped is None else self._skipped.to(dev)
+        return out
+
+    def grad_norm(self) -> torch.Tensor:
+        """G of the last call, skipped or not: the norm of all gradients before clipping (0-dim float32 on the device)."""
+        if not self._wants_norm():
+            raise RuntimeError("mcquic_amd.optim.SGD: the gradient norm is computed only with `max_grad_norm` or `skip_nonfinite`")
+        if self._norm is None:
+            raise RuntimeError("mcquic_amd.optim.SGD: no step has run yet")
+        return self._norm[2]
+
+    @property
+    def skipped(self) -> torch.Tensor:
+        """How many calls the non-finite guard has skipped (0-dim int64 on the device; stays 0 without `skip_nonfinite`)."""
+        if self._skipped is None:
+            dev = next((p.device for g in self.param_groups for p in g["params"]), None)
+            self._skipped = torch.zeros((), dtype=torch.int64, device=dev)
+        return self._skipped
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if closure is not None:
+            raise NotImplementedError("mcquic_amd.optim.SGD: closures are not supported (the reference's trainer passes none)")
+        lib = _lib.load()
+        todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
+        if not todo:
+            return None
+        partials = gnorm = None
+        total = 0
+        if self._wants_norm():                                # the norm of ALL gradients first, every group's chunks into one array
+            _, partials, gnorm = self._norm
+            with _guard(gnorm.device):
+                for _, plan in todo:
+                    check(lib.mcq_lamb_grad_partials_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
+                                                         plan.blk_first.data_ptr(), plan.nblocks, partials.data_ptr() + 8 * total, _stream()),
+                          "mcq_lamb_grad_partials_f32")
+                    total += plan.nblocks
+        for i, (group, plan) in enumerate(todo):              # (every group derives the same factor and flag; the first one counts a skip)
+            lr_dev, lr_host = self._rate(group)
+            with _guard(plan.step.device):
+                check(lib.mcq_sgd_step_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
+                                           plan.blk_first.data_ptr(), plan.nblocks, plan.step.data_ptr(),
+                                           None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(group["momentum"]),
+                                           float(group["dampening"]), float(group["weight_decay"]), 1 if group["nesterov"] else 0,
+                                           1 if group["maximize"] else 0, None if partials is None else partials.data_ptr(), total,
+                                           None if self.max_grad_norm is None else self._bound.data_ptr(),
+                                           None if gnorm is None else gnorm.data_ptr(), 1 if self.skip_nonfinite else 0,
+                                           self._skipped.data_ptr() if self.skip_nonfinite and i == 0 else None, plan.scalars.data_ptr(), _stream()),
+                      "mcq_sgd_step_f32")
+        return None
+
+    def state_dict(self):
+        """torch.optim.SGD's layout: `momentum_buffer` per parameter and nothing else (the step count every plan keeps is ours)."""
+        sd = super().state_dict()
+        state = {k: {n: v for n, v in st.items() if n != "step"} for k, st in sd["state"].items()}
+        sd["state"] = {k: st for k, st in state.items() if st}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """torch.optim.SGD checkpoints load as they are; the buffers move into the flat buffer on the next `step()`, at the same
+        addresses.  A group that comes with a buffer continues (its next update is not a first one); one without starts over."""
+        super().load_state_dict(state_dict)
+        for group in self.param_groups:
+            for k in ("foreach", "fused", "differentiable"):
+                if group.get(k):
+                    raise NotImplementedError(f"mcquic_amd.optim.SGD: `{k}` checkpoints are not supported")
+            group.update(foreach=None, differentiable=False, fused=None)
+            for k in ("nesterov", "maximize"):
+                group.setdefault(k, False)
+            held = [p for p in group["params"] if p in self.state]
+            for p in held:
+                if self.state[p].get("momentum_buffer", 0) is None:
+                    del self.state[p]["momentum_buffer"]
+            count = 1.0 if any("momentum_buffer" in self.state[p] for p in held) else 0.0
+            for p in group["params"]:
+                self.state[p]["step"] = torch.tensor(count, dtype=torch.float32)
         for plan in self._plans.values():
             plan.adopted = False
 

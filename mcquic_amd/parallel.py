@@ -259,7 +259,8 @@ class GraphedTrainStep:
     (`transform.last_params` is the table of the last step); the generator's {seed, offset} is in `transform.state_dict()`.
     `max_grad_norm` clips the averaged gradient by its global norm in front of the update (the reference's step does,
     mcquic/train/trainer.py:280; torch.nn.utils.clip_grad_norm_'s arithmetic over the flat buffer, on the device); the norm before
-    clipping is `step.grad_norm` (a 0-dim device tensor, valid after each call).
+    clipping is `step.grad_norm` (a 0-dim device tensor, valid after each call).  An optimizer that clips by itself
+    (`mcquic_amd.optim.SGD(max_grad_norm=...)`: its `grad_norm()`) goes with `max_grad_norm=None` here; setting both is refused.
     """
 
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
@@ -287,6 +288,8 @@ class GraphedTrainStep:
         self.segments = segments
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError("max_grad_norm must be positive (or None: no clipping)")
+        if max_grad_norm is not None and getattr(optimizer, "max_grad_norm", None) is not None:
+            raise ValueError("both the step and the optimizer clip (`max_grad_norm`): the gradient would be scaled twice; set one of them")
         self.max_grad_norm = max_grad_norm
         self.grad_norm = None                                 # 0-dim device tensor: the global gradient norm of the last step, before clipping
         if loss_fn is not None and not memset_nodes_replay_correctly(example_x.device):
@@ -381,7 +384,7 @@ class GraphedTrainStep:
             p.grad = self.flat[off: off + p.numel()].view_as(p)
             off += p.numel()
         self.post = None
-        if hasattr(self.optimizer, "prepare"):                # (mcquic_amd.optim.Adam: device tables for the flat gradient views, built
+        if hasattr(self.optimizer, "prepare"):                # (mcquic_amd.optim.Adam / Lamb / SGD: device tables for the flat gradient views, built
             self.optimizer.prepare()                          #  outside the capture)
         if capture_post:
             before = self._snapshot_optimizer_state()

@@ -56,6 +56,9 @@ def main():
     ap.add_argument("--own-adam", action="store_true", help="mcquic_amd.optim.Adam: the whole model in one launch")
     ap.add_argument("--lamb", action="store_true", help="mcquic_amd.optim.Lamb(max_grad_norm=4.0): the reference's FusedLAMB entry; the optimizer clips, "
                                                         "so the step itself does not")
+    ap.add_argument("--own-sgd", action="store_true", help="mcquic_amd.optim.SGD(momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True): one launch behind "
+                                                           "the gradient norm's pass; the optimizer clips, so the step itself does not")
+    ap.add_argument("--sgd", action="store_true", help="torch.optim.SGD(momentum=0.9, lr as a float) under the step's own clipping: what --own-sgd is measured against")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from mcquic_amd import Compressor, parallel
@@ -72,10 +75,17 @@ def main():
     elif args.own_adam:
         from mcquic_amd import optim
         opt = optim.Adam(model.parameters(), lr=lr)
+    elif args.own_sgd:
+        from mcquic_amd import optim
+        opt = optim.SGD(model.parameters(), lr=lr, momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True)
+    elif args.sgd:
+        if args.warmup:
+            ap.error("--sgd takes no --warmup: torch.optim.SGD reads a tensor rate on the host, so its captured update bakes the rate in")
+        opt = torch.optim.SGD(model.parameters(), lr=args.lr, momentum=0.9)
     else:
         opt = torch.optim.Adam(model.parameters(), lr=lr, capturable=True, **({"fused": True} if args.fused else {}))
     x = images(args.batch, args.crop, gen, dev)
-    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if args.lamb else 4.0)
+    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if (args.lamb or args.own_sgd) else 4.0)
     trace = {"loss": [], "grad_norm": [], "psnr": [], "reassigned": [], "non_finite": 0}
     model.eval()
     step.invalidate()
@@ -95,7 +105,7 @@ def main():
         lv = loss.item()                                           # (what a logger does every step)
         if i % max(10, args.steps // 200) == 0 or i == 1 or os.environ.get("REHEARSAL_TRACE_ALL"):
             trace["loss"].append((i, round(lv, 6)))
-            trace["grad_norm"].append((i, round(float(opt.grad_norm if args.lamb else step.grad_norm), 5)))
+            trace["grad_norm"].append((i, round(float(opt.grad_norm if args.lamb else opt.grad_norm() if args.own_sgd else step.grad_norm), 5)))
         if lv != lv:
             trace["non_finite"] += 1
         if i == args.every:
@@ -116,9 +126,10 @@ def main():
     last = sum(v for _, v in trace["loss"][-3:]) / 3
     out = {"what": "GraphedTrainStep(Adam, lr in a device tensor, max_grad_norm=4.0) on fresh synthetic batches; loss.item() every step; every "
                    f"{args.every} steps: finiteness of all parameters, eager encode/decode PSNR on 4 held-out images, codebook re-assignment every {2 * args.every}",
-           "model": f"Compressor({args.channel}, {args.m}, {ks})", "lr": args.lr, "lr_warmup_steps": args.warmup, "optimizer": "mcquic_amd.optim.Lamb(max_grad_norm=4.0), no clipping in the step" if args.lamb else "mcquic_amd.optim.Adam" if args.own_adam else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "crop": args.crop, "steps": args.steps,
+           "model": f"Compressor({args.channel}, {args.m}, {ks})", "lr": args.lr, "lr_warmup_steps": args.warmup, "optimizer": "mcquic_amd.optim.Lamb(max_grad_norm=4.0), no clipping in the step" if args.lamb else "mcquic_amd.optim.Adam" if args.own_adam else "mcquic_amd.optim.SGD(momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True), no clipping in the step" if args.own_sgd else "torch SGD(momentum=0.9) foreach" if args.sgd else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "crop": args.crop, "steps": args.steps,
            "ms_per_step": round(t_steps / args.steps * 1e3, 3), "loss_first": round(first, 6), "loss_last": round(last, 6),
-           "psnr_first": trace["psnr"][0][1], "psnr_last": trace["psnr"][-1][1], "memset_nodes_ok": parallel.memset_nodes_replay_correctly(dev), "memory": mem, **trace}
+           "psnr_first": trace["psnr"][0][1], "psnr_last": trace["psnr"][-1][1], "memset_nodes_ok": parallel.memset_nodes_replay_correctly(dev), "memory": mem,
+           **({"skipped": int(opt.skipped)} if args.own_sgd else {}), **trace}
     line = json.dumps(out)
     print(line)
     if args.out:
