@@ -563,27 +563,28 @@ def conv2d(x: torch.Tensor, w: PackedConv, stride: int = 1, **fused) -> torch.Te
     return y
 
 
-def conv2d_gdn_bwd(x: torch.Tensor, w: PackedConv, dy: torch.Tensor, inverse: bool):
+def conv2d_gdn_bwd(x: torch.Tensor, w: PackedConv, dy: torch.Tensor, inverse: bool, tile: int = 0):
     """(dy f(s), dy x f'(s)) with s = beta + gamma @ x^2 recomputed by THIS launch (`w` = the layer's folded 1x1 operand stream):
     the element-wise part of the GDN / IGDN backward as the epilogue of the s-convolution (MCQ_CONV_GDN_BWD / _IGDN_BWD) instead of
-    a launch of its own behind a stored s -- one launch and 2 x the tensor less HBM traffic per layer."""
+    a launch of its own behind a stored s -- one launch and 2 x the tensor less HBM traffic per layer.  `tile` forces the tile height
+    (the launcher keeps one pixel block per wave and no split for this epilogue)."""
     x, dy = _dev(x, "x"), _dev(dy, "dy")
     if w.ksize != 1 or x.shape != dy.shape or x.shape[1] != w.cin or w.cout != w.cin:
         raise ValueError("conv2d_gdn_bwd: a square 1x1 layer and dy of x's shape")
     n, c, h, wd = x.shape
     dxd, ds = torch.empty_like(x), torch.empty_like(x)
     d = ConvDesc(_ptr(x), _ptr(w.wp), _ptr(w.bias), _ptr(dxd), _ptr(ds), _ptr(dy), _ptr(x), None,
-                 n, c, h, wd, w.cout, 1, 1, CONV_SQUARE_IN | (CONV_IGDN_BWD if inverse else CONV_GDN_BWD), 1.0, 0)
+                 n, c, h, wd, w.cout, 1, 1, CONV_SQUARE_IN | (CONV_IGDN_BWD if inverse else CONV_GDN_BWD), 1.0, tile)
     with _guard(x.device):
         check(_lib.load().mcq_conv2d_f32(ctypes.byref(d), _stream()), "mcq_conv2d_f32")
     return dxd, ds
 
 
-def conv2d_gate_bwd(bs, ws, as_, douts):
+def conv2d_gate_bwd(bs, ws, as_, douts, tile: int = 0):
     """[(d a_i, d s_i)] of out_i = a_i * sigmoid(s_i) + x_i with s_i = conv1x1(b_i) RECOMPUTED by this launch (`ws[i]` = the gate's
     1x1 operand stream): d a = dout sigmoid(s), d s = dout a sigmoid(s) (1 - sigmoid(s)) leave from the epilogue
     (MCQ_CONV_GATE_BWD), so the forward stores no s and runs the gate as its 1x1 launch's epilogue (mcquic/nn/blocks.py:281-288).
-    Several gates of one geometry (the paired heads' AttentionBlocks) share the launch."""
+    Several gates of one geometry (the paired heads' AttentionBlocks) share the launch.  `tile`: as for conv2d_gdn_bwd."""
     built = []
     for b, w, a, dout in zip(bs, ws, as_, douts):
         b, a, dout = _dev(b, "b"), _dev(a, "a"), _dev(dout, "dout")
@@ -592,7 +593,7 @@ def conv2d_gate_bwd(bs, ws, as_, douts):
         n, c, h, wd = b.shape
         da, ds = torch.empty_like(a), torch.empty_like(a)
         d = ConvDesc(_ptr(b), _ptr(w.wp), _ptr(w.bias), _ptr(da), _ptr(ds), _ptr(dout), _ptr(a), None,
-                     n, c, h, wd, w.cout, 1, 1, CONV_GATE_BWD, 1.0, 0)
+                     n, c, h, wd, w.cout, 1, 1, CONV_GATE_BWD, 1.0, tile)
         built.append((d, da, ds, (b, a, dout)))
     lib = _lib.load()
     cap = lib.mcq_conv2d_max_multi() if _MULTI else 1

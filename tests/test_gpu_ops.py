@@ -806,7 +806,7 @@ def test_conv_random_shapes_and_epilogues(dev):
             opts["silu_in"] = True                             #  and the library refuses it -- checked at the end)
             xin = F.silu(xin)
         want = F.conv2d(xin, wt.double(), None if b is None else b.double(), stride=stride, padding=ks // 2)
-        if stride == 1 and rng.random() < 0.4:
+        if rng.random() < 0.4:
             res = _rand(tuple(want.shape), 4000 + it)
             scale = rng.choice([1.0, 1.0, 0.5])
             opts["res"] = res.to(dev)
