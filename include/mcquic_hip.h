@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   12
+#define MCQ_ABI_VERSION   13
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -242,6 +242,23 @@ int mcq_vq_kmeans_update_f32(float* codebook, const double* sums, const double* 
  * with counts[g, c] == 0 (reseeding empty clusters).  The caller advances the offset between calls, on the device. */
 int mcq_vq_kmeans_seed_f32(const float* x, float* codebook, const int64_t* counts_or_null, const uint64_t* rng_state,
                            int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, void* stream);
+
+/* ---- codebook cosine regulariser (ABI 13; csrc/codebook_cos.hip) ------------------------------------------------------------
+ * The reference's BasicRate._cosineLoss (mcquic/loss/__init__.py:27-44) over one level's codebook [m, k, d] without the [k, k]
+ * Gram matrix: with p = c c^T per group, n_i = sum_t c_it^2 and cos_ij = p_ij / sqrt(n_i n_j),
+ *   mcq_codebook_cos_f32      loss[0] = sum over groups and pairs i < j of clamp(cos_ij, 0, 2)  (three launches);
+ *   mcq_codebook_cos_bwd_f32  dcodebook[g, i, :] = gamma dout[0] sum_{j != i, 0 <= cos_ij <= 2} (c_j / s_ij - cos_ij c_i / n_i),
+ *                             s_ij = sqrt(n_i n_j): the gradient of gamma * loss under clamp's inclusive mask, WRITTEN, not
+ *                             accumulated (two launches); `dout` is a device scalar, `gamma` a host one.
+ * A zero codeword makes the loss non-finite (0 / 0, as in the reference); the gradient's values for such a row are unspecified.
+ * k == 1 gives loss 0 and gradient 0.  1 <= d <= 256 and m, k >= 1, else MCQ_EINVAL before any launch (as for a NULL pointer).
+ * `workspace`: mcq_codebook_cos_workspace(m, k, d) bytes (0 for refused arguments), 8-byte aligned: per-workgroup double partials
+ * and two floats per codeword, O(m k).  No atomics, no memset, every sum in a fixed order: equal inputs give equal bits, and both
+ * calls are safe inside a captured hipGraph.  (The size query enqueues nothing and therefore takes no stream.) */
+size_t mcq_codebook_cos_workspace(int32_t m, int32_t k, int32_t d);
+int mcq_codebook_cos_f32(const float* codebook, float* loss, void* workspace, int32_t m, int32_t k, int32_t d, void* stream);
+int mcq_codebook_cos_bwd_f32(const float* codebook, const float* dout, float gamma, float* dcodebook, void* workspace, int32_t m,
+                             int32_t k, int32_t d, void* stream);
 
 /* ---- training-mode quantizer forward (BASELINE config #5, forward half) ------------------------------ */
 

@@ -78,6 +78,9 @@ SYMBOLS = {
     "mcq_vq_kmeans_accumulate_f32": (c_int32, [c_void_p] * 5 + [c_int32] * 6 + [c_void_p]),
     "mcq_vq_kmeans_update_f32": (c_int32, [c_void_p] * 6 + [c_int32] * 3 + [c_void_p]),
     "mcq_vq_kmeans_seed_f32": (c_int32, [c_void_p] * 4 + [c_int32] * 6 + [c_void_p]),
+    "mcq_codebook_cos_workspace": (c_size_t, [c_int32, c_int32, c_int32]),
+    "mcq_codebook_cos_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
+    "mcq_codebook_cos_bwd_f32": (c_int32, [c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p]),
     "mcq_vq_logits_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_int32, c_void_p]),
     "mcq_vq_gumbel_sample_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
@@ -174,7 +177,7 @@ SYMBOLS = {
     "mcq_abi_version": (c_int32, []),
 }
 
-ABI_VERSION = 12         # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
+ABI_VERSION = 13       # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
 
 _lib = None
 

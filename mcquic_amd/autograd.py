@@ -221,6 +221,24 @@ class MsSsimFn(torch.autograd.Function):
         return (da if ctx.needs_input_grad[0] else None), db, None, None
 
 
+class CodebookCosineFn(torch.autograd.Function):
+    """gamma-free sum of the clamped pairwise cosines of one level's codebook [m, k, d] (mcquic/loss/__init__.py:32-41) from this
+    library's kernels (mcq_codebook_cos_f32 / _bwd_f32).  Saves only the codebook: the backward recomputes the tiles."""
+
+    @staticmethod
+    def forward(ctx, codebook):
+        codebook = codebook.contiguous()
+        ctx.save_for_backward(codebook)
+        return ops.codebook_cosine(codebook)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (codebook,) = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None
+        return ops.codebook_cosine_bwd(codebook, dout.contiguous().float(), 1.0)
+
+
 _ONES = {}
 
 

@@ -1097,6 +1097,43 @@ def sumsq(x: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _cosine_codebook(codebook: torch.Tensor):
+    codebook = _dev(codebook, "codebook")
+    if codebook.dim() != 3 or codebook.numel() == 0:
+        raise ValueError(f"expected a non-empty [m, k, d] codebook, got {tuple(codebook.shape)}")
+    m, k, d = codebook.shape
+    nbytes = _lib.load().mcq_codebook_cos_workspace(m, k, d)
+    if nbytes == 0:
+        raise ValueError(f"codebook_cosine: [m, k, d] = {(m, k, d)} is not taken (1 <= d <= 256, m * k below 2^31)")
+    return codebook, torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=codebook.device)
+
+
+def codebook_cosine(codebook: torch.Tensor) -> torch.Tensor:
+    """Sum over the groups of a [m, k, d] codebook and the pairs i < j of clamp(cos(c_i, c_j), 0, 2) as a 0-dim float32 tensor
+    (mcquic/loss/__init__.py:32-41 without the [k, k] plane; mcq_codebook_cos_f32: fixed summation order, no memset)."""
+    codebook, ws = _cosine_codebook(codebook)
+    m, k, d = codebook.shape
+    out = torch.empty((), dtype=torch.float32, device=codebook.device)
+    with _guard(codebook.device):
+        check(_lib.load().mcq_codebook_cos_f32(_ptr(codebook), _ptr(out), _ptr(ws), m, k, d, _stream()), "mcq_codebook_cos_f32")
+    return out
+
+
+def codebook_cosine_bwd(codebook: torch.Tensor, dout: torch.Tensor, gamma: float) -> torch.Tensor:
+    """Gradient [m, k, d] of `gamma * codebook_cosine(codebook)` times the device scalar `dout` (mcq_codebook_cos_bwd_f32: the
+    tiles are recomputed, every element has one writer)."""
+    codebook, ws = _cosine_codebook(codebook)
+    dout = _dev(dout, "dout")
+    if dout.numel() != 1:
+        raise ValueError("codebook_cosine_bwd: `dout` must hold one element")
+    m, k, d = codebook.shape
+    out = torch.empty_like(codebook)
+    with _guard(codebook.device):
+        check(_lib.load().mcq_codebook_cos_bwd_f32(_ptr(codebook), _ptr(dout), float(gamma), _ptr(out), _ptr(ws), m, k, d, _stream()),
+              "mcq_codebook_cos_bwd_f32")
+    return out
+
+
 def clip_by_norm_(x: torch.Tensor, max_norm: float, eps: float = 1e-6) -> torch.Tensor:
     """In place: x *= max_norm / (||x|| + eps) where that is < 1 (torch.nn.utils.clip_grad_norm_ over one flat buffer; the reference's
     trainer.py:280).  Returns ||x|| BEFORE clipping as a 0-dim device tensor; no host read, so it can be captured."""

@@ -285,6 +285,9 @@ class GraphedTrainStep:
             raise ValueError("segments must be 1 (one graph, one all-reduce) or 3 (decoder / quantizer / encoder backward)")
         if segments == 3 and not staged:
             raise ValueError("segments=3 needs a model with _encoder / _quantizer / _decoder stages and no forward_kwargs but `uniforms`")
+        if segments == 3 and getattr(loss_fn, "single_segment", False):
+            raise ValueError("this loss_fn reaches parameters from outside the model's output (loss.step_loss(rate=...) reads the codebooks): "
+                             "their gradients would come from two segments; use segments=1")
         self.segments = segments
         if max_grad_norm is not None and not max_grad_norm > 0:
             raise ValueError("max_grad_norm must be positive (or None: no clipping)")

@@ -28,6 +28,8 @@ def main():
     ap.add_argument("--graph-streams", action="store_true", help="with --graph: keep the branch streams on during capture (experiment)")
     ap.add_argument("--loss", choices=("mse", "msssim"), default="mse",
                     help="msssim: mcquic_amd.loss.step_loss(), the reference trainer's 0.5 MS-SSIM + 0.5 MSE (without LPIPS)")
+    ap.add_argument("--rate", type=float, default=None, metavar="GAMMA",
+                    help="with --loss msssim: add mcquic_amd.loss.BasicRate(GAMMA) over the model's codebooks to the objective (one graph segment)")
     ap.add_argument("--graphed", action="store_true",
                     help="parallel.GraphedTrainStep: main hipGraph (forward + backward, flat gradient buffer) + one gradient all-reduce "
                          "over the ranks + post hipGraph (SGD update, frequency EMA) -- the data-parallel step without DDP's hooks")
@@ -59,6 +61,8 @@ def main():
             finally:
                 ops.conv2d = conv
         ops.conv2d, ops.conv2d_multi = conv, multi
+    if args.rate is not None and args.loss != "msssim":
+        raise SystemExit("bench_train.py: --rate goes with --loss msssim")
     if args.graph and not args.graph_streams:
         # capturing the nested stream forks of the training graph crashes hipGraph capture (ROCm 7.2): one stream there
         os.environ["MCQUIC_AMD_BRANCH_STREAMS"] = "0"
@@ -84,7 +88,11 @@ def main():
     opt = torch.optim.SGD(model.parameters(), lr=1e-6) if args.optimizer_step else None
     if args.loss == "msssim":
         from mcquic_amd.loss import step_loss
-        _msssim = step_loss()
+        if args.rate is not None:
+            from mcquic_amd.loss import BasicRate
+            _msssim = step_loss(rate=BasicRate(args.rate), model=model)
+        else:
+            _msssim = step_loss()
 
         def mse_loss(xHat, x):                             # noqa: F811  (the objective the steps below take)
             return _msssim((xHat,), x)
@@ -103,7 +111,8 @@ def main():
         from mcquic_amd import parallel
         args.optimizer_step = True
         gstep = parallel.GraphedTrainStep(model, torch.optim.SGD(model.parameters(), lr=1e-6), x,
-                                          loss_fn=(lambda out, xx: mse_loss(out[0], xx)) if args.loss != "mse" else None)
+                                          loss_fn=(lambda out, xx: mse_loss(out[0], xx)) if args.loss != "mse" else None,
+                                          segments=1 if args.rate is not None else None)
 
         def step():                                        # noqa: F811
             return gstep(x)
@@ -140,6 +149,8 @@ def main():
     if rank == 0:
         gn = float(torch.sqrt(sum((p.grad.double() ** 2).sum() for p in model.parameters() if p.grad is not None)))
         extra = {"loss_fn": args.loss} if args.loss != "mse" else {}
+        if args.rate is not None:
+            extra["rate_gamma"] = args.rate
         print(json.dumps({"metric": "training step (forward + backward), 256x256 crops, qp=2 model", "n_gpus": world,
                           "images_per_gpu": args.batch, "ms_per_step": round(dt / args.steps * 1e3, 2),
                           "images_per_s": round(world * args.batch * args.steps / dt, 2), "loss": float(loss), "grad_norm": gn,
