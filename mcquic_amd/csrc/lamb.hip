@@ -1,9 +1,8 @@
 // LAMB over MANY tensors with per-tensor trust ratios (the reference's `FusedLAMB` registry entry, mcquic/train/ddp.py:53-69; the
 // arithmetic is apex FusedLAMB's published algorithm, written out in mcquic_amd/optim.py) for gfx950.
 //
-// The tensor lists are Adam's device tables (train_ops.hip: pointer tables [4][ntensors], numel, one (tensor, first element) entry
-// per ADAM_CHUNK-element chunk) plus tensor_first_blk[ntensors + 1], so a tensor's chunks are a contiguous range.  A step is five
-// launches whatever the number of tensors:
+// The tensor lists are the device tables of tensor_list.h (pointer rows: param, grad, exp_avg, exp_avg_sq) plus
+// tensor_first_blk[ntensors + 1], so a tensor's chunks are a contiguous range.  A step is five launches whatever the number of tensors:
 //   (a) lamb_gradsq_kernel    one double partial of sum g^2 per chunk                                   4 B / element
 //   (b) lamb_prepare_kernel   ONE workgroup: the partials of every group in a fixed order -> G, the clip divisor, the step count
 //                             and the bias corrections (double, rounded once), the learning rate
@@ -14,23 +13,12 @@
 // are only read (apex overwrites them with u).  Loads are one dword per lane, consecutive lanes consecutive elements, as in
 // adam_update_kernel: the slices of a flat gradient buffer are 4-byte aligned only.
 #include "mcq_common.h"
+#include "tensor_list.h"
 #include "../../include/mcquic_hip.h"
 
 namespace {
 
-constexpr int LAMB_CHUNK = 4096;                             // == mcq_adam_chunk(): the chunk tables are shared with Adam
 struct LambScalars { float clip; float bc1; float bc2; float lr; };
-
-// sum over the workgroup's 256 lanes in a fixed tree; the result is valid in lane 0
-__device__ __forceinline__ double lamb_block_sum(double s, double* red) {
-    red[threadIdx.x] = s;
-    __syncthreads();
-    for (int off = 128; off > 0; off >>= 1) {
-        if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-        __syncthreads();
-    }
-    return red[0];
-}
 
 // the update direction; stage 1 (norm) and stage 2 (apply) both call this on the same floats, so they see the same bits
 __device__ __forceinline__ float lamb_direction(float m, float v, float p, const LambScalars& sc, float eps, float weight_decay, int adam_w) {
@@ -38,22 +26,17 @@ __device__ __forceinline__ float lamb_direction(float m, float v, float p, const
     return adam_w ? u + weight_decay * p : u;
 }
 
-__global__ __launch_bounds__(256) void lamb_gradsq_kernel(const unsigned long long* __restrict__ ptrs, int ntensors, const long long* __restrict__ numel,
-                                                          const int* __restrict__ blk_tensor, const long long* __restrict__ blk_first,
-                                                          double* __restrict__ part) {
+__global__ __launch_bounds__(256) void lamb_gradsq_kernel(McqTensorList list, double* __restrict__ part) {
     __shared__ double red[256];
-    const int t = blk_tensor[blockIdx.x];
-    const long long first = blk_first[blockIdx.x];
-    const float* __restrict__ g = (const float*)ptrs[(size_t)ntensors + t];
-    const long long n = numel[t];
-    const long long end = first + LAMB_CHUNK < n ? first + LAMB_CHUNK : n;
+    const McqChunk c = list.chunk();
+    const float* __restrict__ g = list.row(1, c.t);
     double s = 0.0;
 #pragma unroll 4
-    for (long long i = first + threadIdx.x; i < end; i += 256) {
+    for (long long i = c.first + threadIdx.x; i < c.end; i += 256) {
         const double gi = (double)g[i];
         s += gi * gi;
     }
-    s = lamb_block_sum(s, red);
+    s = mcq_block_sum256(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 
@@ -64,7 +47,7 @@ __global__ __launch_bounds__(256) void lamb_prepare_kernel(const double* __restr
     __shared__ double red[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
-    s = lamb_block_sum(s, red);
+    s = mcq_block_sum256(s, red);
     if (threadIdx.x) return;
     const float G = (float)sqrt(s);
     grad_norm[0] = G;
@@ -76,23 +59,18 @@ __global__ __launch_bounds__(256) void lamb_prepare_kernel(const double* __restr
     sc->lr = lr_dev ? lr_dev[0] : (float)lr_host;
 }
 
-__global__ __launch_bounds__(256) void lamb_stage1_kernel(const unsigned long long* __restrict__ ptrs, int ntensors, const long long* __restrict__ numel,
-                                                          const int* __restrict__ blk_tensor, const long long* __restrict__ blk_first,
-                                                          const LambScalars* __restrict__ scp, float beta1, float beta3, float beta2, float omb2,
-                                                          float eps, float weight_decay, int adam_w, double* __restrict__ part_pu) {
+__global__ __launch_bounds__(256) void lamb_stage1_kernel(McqTensorList list, const LambScalars* __restrict__ scp, float beta1, float beta3, float beta2,
+                                                          float omb2, float eps, float weight_decay, int adam_w, double* __restrict__ part_pu) {
     __shared__ double red[256];
-    const int t = blk_tensor[blockIdx.x];
-    const long long first = blk_first[blockIdx.x];
-    const float* __restrict__ p = (const float*)ptrs[t];
-    const float* __restrict__ g = (const float*)ptrs[(size_t)ntensors + t];
-    float* __restrict__ m = (float*)ptrs[2 * (size_t)ntensors + t];
-    float* __restrict__ v = (float*)ptrs[3 * (size_t)ntensors + t];
-    const long long n = numel[t];
-    const long long end = first + LAMB_CHUNK < n ? first + LAMB_CHUNK : n;
+    const McqChunk c = list.chunk();
+    const float* __restrict__ p = list.row(0, c.t);
+    const float* __restrict__ g = list.row(1, c.t);
+    float* __restrict__ m = list.row(2, c.t);
+    float* __restrict__ v = list.row(3, c.t);
     const LambScalars sc = *scp;
     double sp = 0.0, su = 0.0;
 #pragma unroll 4
-    for (long long i = first + threadIdx.x; i < end; i += 256) {
+    for (long long i = c.first + threadIdx.x; i < c.end; i += 256) {
         const float pi = p[i];
         float gi = g[i] / sc.clip;
         if (!adam_w) gi = gi + weight_decay * pi;                    // L2: the decay joins the gradient
@@ -104,9 +82,9 @@ __global__ __launch_bounds__(256) void lamb_stage1_kernel(const unsigned long lo
         sp += (double)pi * (double)pi;
         su += ui * ui;
     }
-    sp = lamb_block_sum(sp, red);
+    sp = mcq_block_sum256(sp, red);
     __syncthreads();                                                 // (lane 0 has read red[0] before it is overwritten)
-    su = lamb_block_sum(su, red);
+    su = mcq_block_sum256(su, red);
     if (threadIdx.x == 0) {
         part_pu[2 * (size_t)blockIdx.x] = sp;
         part_pu[2 * (size_t)blockIdx.x + 1] = su;
@@ -143,21 +121,16 @@ __global__ __launch_bounds__(64) void lamb_ratio_kernel(const double* __restrict
     rate[t] = (scaled && pn != 0.0 && un != 0.0) ? lr * q : lr;
 }
 
-__global__ __launch_bounds__(256) void lamb_stage2_kernel(const unsigned long long* __restrict__ ptrs, int ntensors, const long long* __restrict__ numel,
-                                                          const int* __restrict__ blk_tensor, const long long* __restrict__ blk_first,
-                                                          const LambScalars* __restrict__ scp, const float* __restrict__ rate, float eps,
+__global__ __launch_bounds__(256) void lamb_stage2_kernel(McqTensorList list, const LambScalars* __restrict__ scp, const float* __restrict__ rate, float eps,
                                                           float weight_decay, int adam_w) {
-    const int t = blk_tensor[blockIdx.x];
-    const long long first = blk_first[blockIdx.x];
-    float* __restrict__ p = (float*)ptrs[t];
-    const float* __restrict__ m = (const float*)ptrs[2 * (size_t)ntensors + t];
-    const float* __restrict__ v = (const float*)ptrs[3 * (size_t)ntensors + t];
-    const long long n = numel[t];
-    const long long end = first + LAMB_CHUNK < n ? first + LAMB_CHUNK : n;
+    const McqChunk c = list.chunk();
+    float* __restrict__ p = list.row(0, c.t);
+    const float* __restrict__ m = list.row(2, c.t);
+    const float* __restrict__ v = list.row(3, c.t);
     const LambScalars sc = *scp;
-    const float r = rate[t];
+    const float r = rate[c.t];
 #pragma unroll 4
-    for (long long i = first + threadIdx.x; i < end; i += 256) {
+    for (long long i = c.first + threadIdx.x; i < c.end; i += 256) {
         const float pi = p[i];
         p[i] = pi - r * lamb_direction(m[i], v[i], pi, sc, eps, weight_decay, adam_w);
     }
@@ -174,9 +147,9 @@ extern "C" size_t mcq_lamb_workspace_bytes(int32_t ntensors, int32_t nblocks) {
 
 extern "C" int mcq_lamb_grad_partials_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor,
                                           const int64_t* blk_first, int32_t nblocks, double* partials, void* stream) {
-    if (!ptr_tables || !numel || !blk_tensor || !blk_first || !partials || ntensors <= 0 || nblocks <= 0) return MCQ_EINVAL;
-    hipLaunchKernelGGL(lamb_gradsq_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)ptr_tables,
-                       (int)ntensors, (const long long*)numel, (const int*)blk_tensor, (const long long*)blk_first, partials);
+    McqTensorList list;
+    if (!mcq_tensor_list(&list, ptr_tables, ntensors, numel, blk_tensor, blk_first, nblocks) || !partials) return MCQ_EINVAL;
+    hipLaunchKernelGGL(lamb_gradsq_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, list, partials);
     return mcq_check_launch();
 }
 
@@ -185,14 +158,14 @@ extern "C" int mcq_lamb_step_f32(const void* ptr_tables, int32_t ntensors, const
                                  float* step, const float* lr_dev, double lr, double beta1, double beta2, double eps, double weight_decay,
                                  int32_t bias_correction, int32_t adam_w_mode, int32_t grad_averaging, int32_t use_nvlamb, double max_grad_norm,
                                  float* grad_norm, float* ratios, void* workspace, void* scalars, void* stream) {
-    if (!ptr_tables || !numel || !blk_tensor || !blk_first || !tensor_first_blk || !grad_partials || !step || !grad_norm || !ratios || !workspace ||
-        !scalars || ntensors <= 0 || nblocks <= 0 || n_grad_partials <= 0)
+    McqTensorList list;
+    if (!mcq_tensor_list(&list, ptr_tables, ntensors, numel, blk_tensor, blk_first, nblocks) || !tensor_first_blk || !grad_partials || !step ||
+        !grad_norm || !ratios || !workspace || !scalars || n_grad_partials <= 0)
         return MCQ_EINVAL;
     if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0) || !(max_grad_norm >= 0.0))
         return MCQ_EINVAL;
     if (!lr_dev && !(lr >= 0.0)) return MCQ_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const unsigned long long* ptrs = (const unsigned long long*)ptr_tables;
     const LambScalars* sc = (const LambScalars*)scalars;
     double* part_pu = (double*)workspace;
     float* rate = (float*)((char*)workspace + lamb_rate_offset(nblocks));
@@ -201,12 +174,10 @@ extern "C" int mcq_lamb_step_f32(const void* ptr_tables, int32_t ntensors, const
     hipLaunchKernelGGL(lamb_prepare_kernel, dim3(1), dim3(256), 0, s, grad_partials, (int)n_grad_partials, step, lr_dev, lr, beta1, beta2,
                        (int)bias_correction, (float)max_grad_norm, grad_norm, (LambScalars*)scalars);
     // (1 - beta rounded from double, as in mcq_adam_step_f32)
-    hipLaunchKernelGGL(lamb_stage1_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, ptrs, (int)ntensors, (const long long*)numel, (const int*)blk_tensor,
-                       (const long long*)blk_first, sc, (float)beta1, grad_averaging ? (float)(1.0 - beta1) : 1.0f, (float)beta2, (float)(1.0 - beta2),
-                       epsf, wd, adam_w, part_pu);
+    hipLaunchKernelGGL(lamb_stage1_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, list, sc, (float)beta1, grad_averaging ? (float)(1.0 - beta1) : 1.0f,
+                       (float)beta2, (float)(1.0 - beta2), epsf, wd, adam_w, part_pu);
     hipLaunchKernelGGL(lamb_ratio_kernel, dim3((unsigned)ntensors), dim3(64), 0, s, (const double*)part_pu, (const int*)tensor_first_blk, sc,
                        (use_nvlamb || weight_decay != 0.0) ? 1 : 0, rate, ratios);
-    hipLaunchKernelGGL(lamb_stage2_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, ptrs, (int)ntensors, (const long long*)numel, (const int*)blk_tensor,
-                       (const long long*)blk_first, sc, (const float*)rate, epsf, wd, adam_w);
+    hipLaunchKernelGGL(lamb_stage2_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, list, sc, (const float*)rate, epsf, wd, adam_w);
     return mcq_check_launch();
 }

@@ -1,8 +1,7 @@
 // SGD over MANY tensors in one launch (torch.optim.SGD's arithmetic: momentum, dampening, Nesterov, L2 decay, maximize) for gfx950,
 // with two things torch's update does not have: clipping by the global gradient norm and a guard against a non-finite gradient.
 //
-// The tensor lists are Adam's device tables (train_ops.hip: pointer tables [4][ntensors] = param, grad, momentum buffer, unused; numel;
-// one (tensor, first element) entry per chunk of mcq_adam_chunk() elements).  A call is
+// The tensor lists are the device tables of tensor_list.h (pointer rows: param, grad, momentum buffer, unused).  A call is
 //   (a) sgd_prepare_kernel   ONE workgroup: the step count, the learning rate; with gradient partials (mcq_lamb_grad_partials_f32, one
 //                            double per chunk) their sum in a fixed tree -> G, the clip factor and the skip flag
 //   (b) sgd_update_kernel    one workgroup per chunk: 12 B / element without momentum, 20 B with it
@@ -12,11 +11,11 @@
 // equal inputs give equal bits.  Gradients are only read.  A skipped call writes nothing but the `skipped` counter: every workgroup of
 // (b) reads the flag (a) wrote and leaves.
 #include "mcq_common.h"
+#include "tensor_list.h"
 #include "../../include/mcquic_hip.h"
 
 namespace {
 
-constexpr int SGD_CHUNK = 4096;                              // == mcq_adam_chunk(): the chunk tables are shared with Adam
 struct SgdScalars { float lr; float clip; int first; int skip; };
 static_assert(sizeof(SgdScalars) == 16, "`scalars` is 16 bytes");
 struct SgdCoef { float momentum; float omd; float weight_decay; int nesterov; int maximize; };
@@ -29,13 +28,7 @@ __global__ __launch_bounds__(256) void sgd_prepare_kernel(const double* __restri
     double s = 0.0;
     if (part) {                                              // (the same for every lane: launched with 256 lanes then, with 64 otherwise)
         for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
-        red[threadIdx.x] = s;
-        __syncthreads();
-        for (int off = 128; off > 0; off >>= 1) {
-            if ((int)threadIdx.x < off) red[threadIdx.x] += red[threadIdx.x + off];
-            __syncthreads();
-        }
-        s = red[0];
+        s = mcq_block_sum256(s, red);
     }
     if (threadIdx.x) return;
     float clip = 1.0f;
@@ -74,21 +67,16 @@ __device__ __forceinline__ void sgd_element(float& p, float g, float& buf, const
 }
 
 template <bool MOMENTUM>
-__global__ __launch_bounds__(256) void sgd_update_kernel(const unsigned long long* __restrict__ ptrs, int ntensors, const long long* __restrict__ numel,
-                                                         const int* __restrict__ blk_tensor, const long long* __restrict__ blk_first,
-                                                         const SgdScalars* __restrict__ scp, SgdCoef k) {
+__global__ __launch_bounds__(256) void sgd_update_kernel(McqTensorList list, const SgdScalars* __restrict__ scp, SgdCoef k) {
     const SgdScalars sc = *scp;
     if (sc.skip) return;
-    const int t = blk_tensor[blockIdx.x];
-    const long long first = blk_first[blockIdx.x];
-    const long long n = numel[t];
-    const long long end = first + SGD_CHUNK < n ? first + SGD_CHUNK : n;
-    const unsigned long long pa = ptrs[t], ga = ptrs[(size_t)ntensors + t], ma = MOMENTUM ? ptrs[2 * (size_t)ntensors + t] : 0ull;
-    float* __restrict__ p = (float*)pa;
-    const float* __restrict__ g = (const float*)ga;
-    float* __restrict__ m = (float*)ma;
+    const McqChunk c = list.chunk();
+    const long long first = c.first, end = c.end;
+    float* __restrict__ p = list.row(0, c.t);
+    const float* __restrict__ g = list.row(1, c.t);
+    float* __restrict__ m = MOMENTUM ? list.row(2, c.t) : nullptr;
     long long done = first;
-    if (((pa | ga | ma) & 15ull) == 0) {                     // every stream of this tensor is 16-byte aligned (first % 4 == 0)
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m) & 15) == 0) {   // every stream of this tensor is 16-byte aligned (first % 4 == 0)
         const long long nvec = (end - first) >> 2;           // <= 1024 float4: at most four per lane
         float4* __restrict__ p4 = (float4*)(p + first);
         const float4* __restrict__ g4 = (const float4*)(g + first);
@@ -122,7 +110,8 @@ extern "C" int mcq_sgd_step_f32(const void* ptr_tables, int32_t ntensors, const 
                                 double weight_decay, int32_t nesterov, int32_t maximize, const double* grad_partials, int32_t n_grad_partials,
                                 const float* max_grad_norm, float* grad_norm, int32_t skip_nonfinite, int64_t* skipped, void* scalars,
                                 void* stream) {
-    if (!ptr_tables || !numel || !blk_tensor || !blk_first || !step || !scalars || ntensors <= 0 || nblocks <= 0) return MCQ_EINVAL;
+    McqTensorList list;
+    if (!mcq_tensor_list(&list, ptr_tables, ntensors, numel, blk_tensor, blk_first, nblocks) || !step || !scalars) return MCQ_EINVAL;
     if (!(momentum >= 0.0) || !(weight_decay >= 0.0) || !(dampening == dampening)) return MCQ_EINVAL;
     if (nesterov && (!(momentum > 0.0) || dampening != 0.0)) return MCQ_EINVAL;
     if (!lr_dev && !(lr >= 0.0)) return MCQ_EINVAL;
@@ -132,11 +121,7 @@ extern "C" int mcq_sgd_step_f32(const void* ptr_tables, int32_t ntensors, const 
                        max_grad_norm, grad_norm, skip_nonfinite ? 1 : 0, (long long*)skipped, (SgdScalars*)scalars);
     // (1 - dampening rounded from double, as torch passes `alpha = 1 - dampening` to _foreach_add_)
     const SgdCoef k = {(float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov ? 1 : 0, maximize ? 1 : 0};
-    if (momentum != 0.0)
-        hipLaunchKernelGGL(sgd_update_kernel<true>, dim3((unsigned)nblocks), dim3(256), 0, s, (const unsigned long long*)ptr_tables, (int)ntensors,
-                           (const long long*)numel, (const int*)blk_tensor, (const long long*)blk_first, (const SgdScalars*)scalars, k);
-    else
-        hipLaunchKernelGGL(sgd_update_kernel<false>, dim3((unsigned)nblocks), dim3(256), 0, s, (const unsigned long long*)ptr_tables, (int)ntensors,
-                           (const long long*)numel, (const int*)blk_tensor, (const long long*)blk_first, (const SgdScalars*)scalars, k);
+    hipLaunchKernelGGL(momentum != 0.0 ? sgd_update_kernel<true> : sgd_update_kernel<false>, dim3((unsigned)nblocks), dim3(256), 0, s, list,
+                       (const SgdScalars*)scalars, k);
     return mcq_check_launch();
 }

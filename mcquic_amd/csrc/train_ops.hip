@@ -14,6 +14,7 @@
 #include <type_traits>
 
 #include "mcq_common.h"
+#include "tensor_list.h"
 #include "../../include/mcquic_hip.h"
 
 namespace {
@@ -418,58 +419,6 @@ __global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ 
     }
 }
 
-// ---- Adam / AdamW over MANY tensors in one launch (the update of mcquic/train/trainer.py:283; torch.optim.Adam's arithmetic) ----------
-// torch's fused Adam passes its tensor lists through kernel arguments (4 KB): 19 launches of ~91 us for this model's 666 tensors =
-// 1.7 ms per step at 0.8 TB/s.  Here the lists live in device memory -- pointer tables [4][ntensors] (param, grad, exp_avg, exp_avg_sq),
-// a block table (tensor, first element) of ADAM_CHUNK-element chunks -- so the whole model is ONE launch of ~13 k workgroups that moves
-// 28 bytes per element once.  A one-thread kernel in front advances the step counter and derives the bias corrections on the device
-// (double precision), so learning rate and step may be device scalars a captured graph re-reads on every replay.
-constexpr int ADAM_CHUNK = 4096;
-struct AdamScalars { float step_size; float inv_sqrt_bc2; float lr; float pad; };
-
-__global__ void adam_prepare_kernel(float* __restrict__ step, const float* __restrict__ lr_dev, double lr_host, double beta1, double beta2,
-                                    AdamScalars* __restrict__ sc) {
-    if (blockIdx.x || threadIdx.x) return;
-    const float t = step[0] + 1.0f;
-    step[0] = t;
-    const double lr = lr_dev ? (double)lr_dev[0] : lr_host;
-    const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
-    sc->step_size = (float)(lr / bc1);
-    sc->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
-    sc->lr = (float)lr;
-    sc->pad = 0.0f;
-}
-
-__global__ __launch_bounds__(256) void adam_update_kernel(const unsigned long long* __restrict__ ptrs, int ntensors, const long long* __restrict__ numel,
-                                                          const int* __restrict__ blk_tensor, const long long* __restrict__ blk_first,
-                                                          const AdamScalars* __restrict__ sc, float omb1, float beta2, float omb2, float eps,
-                                                          float weight_decay, int decoupled, int maximize) {
-    const int t = blk_tensor[blockIdx.x];
-    const long long first = blk_first[blockIdx.x];
-    float* __restrict__ p = (float*)ptrs[t];
-    const float* __restrict__ g = (const float*)ptrs[(size_t)ntensors + t];
-    float* __restrict__ m = (float*)ptrs[2 * (size_t)ntensors + t];
-    float* __restrict__ v = (float*)ptrs[3 * (size_t)ntensors + t];
-    const long long n = numel[t];
-    const long long end = first + ADAM_CHUNK < n ? first + ADAM_CHUNK : n;
-    const float step_size = sc->step_size, inv_sqrt_bc2 = sc->inv_sqrt_bc2, lr = sc->lr;
-    for (long long i = first + threadIdx.x; i < end; i += 256) {
-        float gi = g[i], pi = p[i];
-        if (maximize) gi = -gi;
-        if (weight_decay != 0.0f) {
-            if (decoupled) pi = pi * (1.0f - lr * weight_decay);     // AdamW: param.mul_(1 - lr * wd)
-            else gi = gi + weight_decay * pi;                        // Adam: grad.add(param, alpha = wd)
-        }
-        float mi = m[i], vi = v[i];
-        mi = mi + (gi - mi) * omb1;                                  // exp_avg.lerp_(grad, 1 - beta1)
-        vi = vi * beta2 + omb2 * gi * gi;                            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value = 1 - beta2)
-        const float denom = sqrtf(vi) * inv_sqrt_bc2 + eps;
-        m[i] = mi;
-        v[i] = vi;
-        p[i] = pi - step_size * (mi / denom);
-    }
-}
-
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 __global__ void silu_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int64_t n) {
@@ -708,41 +657,20 @@ extern "C" int mcq_mse_bwd_f32(const float* a, const float* b, const float* dlos
 }
 
 // many tensors -> their slices of one flat buffer in ONE launch: workgroup b copies chunk blk_first[b] of tensor blk_tensor[b]
-// (device tables like the optimizer's: the tensor list does not travel as kernel arguments, 4 KB at a time)
+// (the optimizers' chunk tables, tensor_list.h, with one row of source pointers: the tensor list does not travel as kernel arguments)
 __global__ __launch_bounds__(256) void gather_flat_kernel(const unsigned long long* __restrict__ src_ptrs, float* __restrict__ flat,
-                                                          const long long* __restrict__ dst_off, const long long* __restrict__ numel,
-                                                          const int* __restrict__ blk_tensor, const long long* __restrict__ blk_first) {
-    const int t = blk_tensor[blockIdx.x];
-    const long long first = blk_first[blockIdx.x];
-    const float* __restrict__ src = (const float*)src_ptrs[t];
-    float* __restrict__ dst = flat + dst_off[t];
-    const long long n = numel[t];
-    const long long end = first + ADAM_CHUNK < n ? first + ADAM_CHUNK : n;
-    for (long long i = first + threadIdx.x; i < end; i += 256) dst[i] = src[i];
+                                                          const long long* __restrict__ dst_off, McqChunkTable chunks) {
+    const McqChunk c = chunks.chunk();
+    const float* __restrict__ src = (const float*)src_ptrs[c.t];
+    float* __restrict__ dst = flat + dst_off[c.t];
+    for (long long i = c.first + threadIdx.x; i < c.end; i += 256) dst[i] = src[i];
 }
 
 extern "C" int mcq_gather_flat_f32(const void* src_ptrs, float* flat, const int64_t* dst_offsets, const int64_t* numel, const int32_t* blk_tensor,
                                    const int64_t* blk_first, int32_t nblocks, void* stream) {
     if (!src_ptrs || !flat || !dst_offsets || !numel || !blk_tensor || !blk_first || nblocks <= 0) return MCQ_EINVAL;
     hipLaunchKernelGGL(gather_flat_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)src_ptrs, flat,
-                       (const long long*)dst_offsets, (const long long*)numel, (const int*)blk_tensor, (const long long*)blk_first);
-    return mcq_check_launch();
-}
-
-extern "C" int32_t mcq_adam_chunk(void) { return ADAM_CHUNK; }
-
-extern "C" int mcq_adam_step_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
-                                 int32_t nblocks, float* step, const float* lr_dev, double lr, double beta1, double beta2, double eps,
-                                 double weight_decay, int32_t decoupled, int32_t maximize, void* scalars, void* stream) {
-    if (!ptr_tables || !numel || !blk_tensor || !blk_first || !step || !scalars || ntensors <= 0 || nblocks <= 0) return MCQ_EINVAL;
-    if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0) || !(eps >= 0.0) || !(weight_decay >= 0.0)) return MCQ_EINVAL;
-    if (!lr_dev && !(lr >= 0.0)) return MCQ_EINVAL;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(1), dim3(64), 0, s, step, lr_dev, lr, beta1, beta2, (AdamScalars*)scalars);
-    hipLaunchKernelGGL(adam_update_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, (const unsigned long long*)ptr_tables, (int)ntensors,
-                       (const long long*)numel, (const int*)blk_tensor, (const long long*)blk_first, (const AdamScalars*)scalars,
-                       (float)(1.0 - beta1), (float)beta2, (float)(1.0 - beta2), (float)eps, (float)weight_decay, (int)decoupled, (int)maximize);
-    // (1 - beta rounded from double, as torch passes `1 - beta2` to addcmul_: 1 - 0.999f would be 1.3e-5 off)
+                       (const long long*)dst_offsets, McqChunkTable{(const long long*)numel, (const int*)blk_tensor, (const long long*)blk_first});
     return mcq_check_launch();
 }
 

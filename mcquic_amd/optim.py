@@ -1,5 +1,5 @@
 """The optimizer update of the training step (mcquic/train/trainer.py:283 `self._optimizer.step()`; the reference trains with
-`Adam`, lr 1e-4, configs/a800_8.yaml:20-25) as ONE launch over the whole model: `mcq_adam_step_f32` (csrc/train_ops.hip).
+`Adam`, lr 1e-4, configs/a800_8.yaml:20-25) as ONE launch over the whole model: `mcq_adam_step_f32` (csrc/adam.hip; the device tables: csrc/tensor_list.h).
 
 torch.optim.Adam(fused=True) hands its tensor lists to the GPU through kernel arguments, 4 KB at a time: 19 launches of ~91 us for
 the qp=2 model's 666 tensors, 1.7 ms per step at 0.8 TB/s (docs/experiments.md section 9.11).  Here the lists are device arrays
@@ -27,6 +27,21 @@ from .ops import check, _guard, _stream
 __all__ = ["Adam", "AdamW", "Lamb", "FusedLAMB", "SGD", "REGISTRY"]
 
 
+def chunk_tables(sizes):
+    """The host side of the chunk tables the whole-model kernels walk (csrc/tensor_list.h), for tensors of `sizes` elements:
+    (blk_tensor, blk_first, tensor_first_blk) -- one (tensor, first element) entry per chunk of mcq_adam_chunk() elements, in tensor
+    order, and [len(sizes) + 1] chunk offsets: tensor i owns the chunks [tensor_first_blk[i], tensor_first_blk[i + 1]); a tensor
+    without elements owns none."""
+    chunk = _lib.load().mcq_adam_chunk()
+    blk_tensor, blk_first, tensor_first_blk = [], [], [0]
+    for i, n in enumerate(sizes):
+        for first in range(0, n, chunk):
+            blk_tensor.append(i)
+            blk_first.append(first)
+        tensor_first_blk.append(len(blk_tensor))
+    return blk_tensor, blk_first, tensor_first_blk
+
+
 class _Planned(torch.optim.Optimizer):
     """What the optimizers of this module share: the per-parameter state (`_state_names`: both moments, or SGD's momentum buffer, or
     nothing) in flat buffers the object owns, one per name, and the device tables (pointers, sizes, chunks) the kernels walk, built once
@@ -46,6 +61,11 @@ class _Planned(torch.optim.Optimizer):
     class _Plan:
         __slots__ = ("key", "tables", "numel", "blk_tensor", "blk_first", "nblocks", "flat_m", "flat_v", "views", "step", "scalars", "ntensors",
                      "sizes", "ids", "adopted", "names")
+
+        def table_args(self) -> tuple:
+            """The leading arguments of every entry point that walks the tables."""
+            return (self.tables.data_ptr(), self.ntensors, self.numel.data_ptr(), self.blk_tensor.data_ptr(), self.blk_first.data_ptr(),
+                    self.nblocks)
 
     def _flat_state(self, gi: int, params):
         """The plan of group `gi` for `params`: `flat_m` / `flat_v` (the flat buffers of the group's first / second state name, None where
@@ -75,18 +95,13 @@ class _Planned(torch.optim.Optimizer):
             plan.ntensors, plan.key = len(params), None
             # the chunk table depends on the sizes only; the pointer table is ONE device buffer for the plan's lifetime, refilled in
             # place when an address changes (a captured graph that reads it keeps a valid address and sees the current pointers)
-            chunk = _lib.load().mcq_adam_chunk()
-            blk_t, blk_f = [], []
-            for i, n in enumerate(sizes):
-                for first in range(0, n, chunk):
-                    blk_t.append(i)
-                    blk_f.append(first)
+            blk_t, blk_f, _ = chunk_tables(sizes)
             plan.numel = torch.tensor(sizes, dtype=torch.int64).to(dev)
             plan.blk_tensor = torch.tensor(blk_t, dtype=torch.int32).to(dev)
             plan.blk_first = torch.tensor(blk_f, dtype=torch.int64).to(dev)
             plan.nblocks = len(blk_t)
             plan.tables = torch.zeros(4 * len(params), dtype=torch.int64, device=dev)
-            self._extend_plan(plan, blk_t, dev)
+            self._extend_plan(plan, dev)
         for p, views in zip(params, plan.views):
             st = self.state[p]
             for name, view in zip(names, views):
@@ -101,8 +116,8 @@ class _Planned(torch.optim.Optimizer):
         plan.adopted = True
         return plan
 
-    def _extend_plan(self, plan, blk_t, dev) -> None:
-        """What a subclass adds to a new plan (`blk_t`: the tensor of every chunk, on the host)."""
+    def _extend_plan(self, plan, dev) -> None:
+        """What a subclass adds to a new plan."""
 
     def _tables(self, plan, params):
         key = tuple((p.data_ptr(), p.grad.data_ptr()) for p in params)
@@ -160,6 +175,22 @@ class _Planned(torch.optim.Optimizer):
             self._norm = (key, torch.zeros(max(sum(plan.nblocks for _, plan in out), 1), dtype=torch.float64, device=dev), gnorm)
         return out
 
+    @staticmethod
+    def _check_adam_args(lr, betas, eps, weight_decay) -> None:
+        if not torch.is_tensor(lr) and not lr >= 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
+            raise ValueError(f"Invalid betas: {betas}")
+        if not eps >= 0.0 or not weight_decay >= 0.0:
+            raise ValueError("eps and weight_decay must be non-negative")
+
+    def state_dict(self):
+        """Every parameter gets a `step` tensor of ITS OWN (here a group shares one): torch's optimizers increment each entry they are
+        handed, so a shared one would be advanced once per parameter after loading there."""
+        sd = super().state_dict()
+        sd["state"] = {k: {n: (v.clone() if n == "step" and torch.is_tensor(v) else v) for n, v in st.items()} for k, st in sd["state"].items()}
+        return sd
+
     def _rate(self, group):
         """(device tensor or None, host value) of a group's learning rate."""
         lr = group["lr"]
@@ -178,12 +209,7 @@ class Adam(_Planned):
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, *, decoupled: bool = False,
                  maximize: bool = False):
-        if not torch.is_tensor(lr) and not lr >= 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid betas: {betas}")
-        if not eps >= 0.0 or not weight_decay >= 0.0:
-            raise ValueError("eps and weight_decay must be non-negative")
+        self._check_adam_args(lr, betas, eps, weight_decay)
         # (capturable=True is what torch's load_state_dict looks at to keep `step` a float32 device tensor)
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, decoupled=bool(decoupled),
                                       maximize=bool(maximize), capturable=True))
@@ -193,28 +219,19 @@ class Adam(_Planned):
         if closure is not None:
             raise NotImplementedError("mcquic_amd.optim.Adam: closures are not supported (the reference's trainer passes none)")
         lib = _lib.load()
-        for gi, group in enumerate(self.param_groups):
-            params = self._checked(group)
-            if not params:
-                continue
-            plan = self._flat_state(gi, params)
-            self._tables(plan, params)
+        for group, plan in self._planned():
             lr_dev, lr_host = self._rate(group)
             b1, b2 = group["betas"]
-            with _guard(params[0].device):
-                check(lib.mcq_adam_step_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
-                                            plan.blk_first.data_ptr(), plan.nblocks, plan.step.data_ptr(),
-                                            None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(b1), float(b2),
-                                            float(group["eps"]), float(group["weight_decay"]),
+            with _guard(plan.step.device):
+                check(lib.mcq_adam_step_f32(*plan.table_args(), plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(),
+                                            float(lr_host), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
                                             1 if group["decoupled"] else 0, 1 if group["maximize"] else 0, plan.scalars.data_ptr(), _stream()),
                       "mcq_adam_step_f32")
         return None
 
     def state_dict(self):
-        """torch.optim.Adam's layout.  Every parameter gets a `step` tensor of ITS OWN (here they all share one): torch's optimizers
-        increment each entry they are handed, so a shared one would be advanced once per parameter after loading there."""
+        """torch.optim.Adam's layout."""
         sd = super().state_dict()
-        sd["state"] = {k: {n: (v.clone() if n == "step" and torch.is_tensor(v) else v) for n, v in st.items()} for k, st in sd["state"].items()}
         # torch spells the decoupled decay `decoupled_weight_decay` (torch.optim.AdamW sets it): both names travel
         sd["param_groups"] = [dict(g, decoupled_weight_decay=bool(g.get("decoupled", False))) for g in sd["param_groups"]]
         return sd
@@ -272,12 +289,7 @@ class Lamb(_Planned):
                  adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0, use_nvlamb=False):
         if amsgrad:
             raise RuntimeError("mcquic_amd.optim.Lamb does not support the AMSGrad variant.")
-        if not torch.is_tensor(lr) and not lr >= 0.0:
-            raise ValueError(f"Invalid learning rate: {lr}")
-        if not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
-            raise ValueError(f"Invalid betas: {betas}")
-        if not eps >= 0.0 or not weight_decay >= 0.0:
-            raise ValueError("eps and weight_decay must be non-negative")
+        self._check_adam_args(lr, betas, eps, weight_decay)
         if not max_grad_norm >= 0.0:
             raise ValueError(f"Invalid max_grad_norm: {max_grad_norm}")
         super().__init__(params, dict(lr=lr, bias_correction=bool(bias_correction), betas=tuple(betas), eps=eps, weight_decay=weight_decay,
@@ -291,13 +303,8 @@ class Lamb(_Planned):
     def _wants_norm(self) -> bool:
         return True
 
-    def _extend_plan(self, plan, blk_t, dev) -> None:
-        first, at = [0], 0
-        for i in range(plan.ntensors):
-            while at < len(blk_t) and blk_t[at] == i:
-                at += 1
-            first.append(at)
-        plan.tensor_first_blk = torch.tensor(first, dtype=torch.int32).to(dev)
+    def _extend_plan(self, plan, dev) -> None:
+        plan.tensor_first_blk = torch.tensor(chunk_tables(plan.sizes)[2], dtype=torch.int32).to(dev)
         nbytes = _lib.load().mcq_lamb_workspace_bytes(plan.ntensors, max(plan.nblocks, 1))
         plan.workspace = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         plan.ratios = torch.zeros(plan.ntensors, dtype=torch.float32, device=dev)
@@ -330,15 +337,14 @@ class Lamb(_Planned):
         with _guard(gnorm.device):
             at = 0
             for _, plan in todo:                              # the norm of ALL gradients first ...
-                check(lib.mcq_lamb_grad_partials_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
-                                                     plan.blk_first.data_ptr(), plan.nblocks, partials.data_ptr() + 8 * at, _stream()),
+                check(lib.mcq_lamb_grad_partials_f32(*plan.table_args(), partials.data_ptr() + 8 * at, _stream()),
                       "mcq_lamb_grad_partials_f32")
                 at += plan.nblocks
             for group, plan in todo:                          # ... then every group's update reads the same partials
                 lr_dev, lr_host = self._rate(group)
                 b1, b2 = group["betas"]
-                check(lib.mcq_lamb_step_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
-                                            plan.blk_first.data_ptr(), plan.tensor_first_blk.data_ptr(), plan.nblocks, partials.data_ptr(), total,
+                # (this entry point takes tensor_first_blk in front of nblocks)
+                check(lib.mcq_lamb_step_f32(*plan.table_args()[:-1], plan.tensor_first_blk.data_ptr(), plan.nblocks, partials.data_ptr(), total,
                                             plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(b1),
                                             float(b2), float(group["eps"]), float(group["weight_decay"]), 1 if group["bias_correction"] else 0,
                                             1 if group["adam_w_mode"] else 0, 1 if group["grad_averaging"] else 0,
@@ -346,12 +352,6 @@ class Lamb(_Planned):
                                             plan.ratios.data_ptr(), plan.workspace.data_ptr(), plan.scalars.data_ptr(), _stream()),
                       "mcq_lamb_step_f32")
         return None
-
-    def state_dict(self):
-        """Adam's layout; every parameter gets a `step` tensor of its own (here a group shares one)."""
-        sd = super().state_dict()
-        sd["state"] = {k: {n: (v.clone() if n == "step" and torch.is_tensor(v) else v) for n, v in st.items()} for k, st in sd["state"].items()}
-        return sd
 
     def load_state_dict(self, state_dict):
         """Our own checkpoints, and apex FusedLAMB's: there the count is an integer `step` of the param group and the per-parameter
@@ -460,15 +460,13 @@ class SGD(_Planned):
             _, partials, gnorm = self._norm
             with _guard(gnorm.device):
                 for _, plan in todo:
-                    check(lib.mcq_lamb_grad_partials_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
-                                                         plan.blk_first.data_ptr(), plan.nblocks, partials.data_ptr() + 8 * total, _stream()),
+                    check(lib.mcq_lamb_grad_partials_f32(*plan.table_args(), partials.data_ptr() + 8 * total, _stream()),
                           "mcq_lamb_grad_partials_f32")
                     total += plan.nblocks
         for i, (group, plan) in enumerate(todo):              # (every group derives the same factor and flag; the first one counts a skip)
             lr_dev, lr_host = self._rate(group)
             with _guard(plan.step.device):
-                check(lib.mcq_sgd_step_f32(plan.tables.data_ptr(), plan.ntensors, plan.numel.data_ptr(), plan.blk_tensor.data_ptr(),
-                                           plan.blk_first.data_ptr(), plan.nblocks, plan.step.data_ptr(),
+                check(lib.mcq_sgd_step_f32(*plan.table_args(), plan.step.data_ptr(),
                                            None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(group["momentum"]),
                                            float(group["dampening"]), float(group["weight_decay"]), 1 if group["nesterov"] else 0,
                                            1 if group["maximize"] else 0, None if partials is None else partials.data_ptr(), total,

@@ -422,8 +422,7 @@ class GraphedTrainStep:
     def _gather_tables(self):
         """The static side of `_gather` (sizes, offsets, chunk tables, the pinned pointer buffer), built OUTSIDE the captures: host-to-device
         copies from pageable memory invalidate a capture."""
-        from . import _lib
-        chunk = _lib.load().mcq_adam_chunk()
+        from .optim import chunk_tables
         dev = self.flat.device
         self._gatherTables = {}
         for k, params in enumerate(self.live_groups):
@@ -434,11 +433,7 @@ class GraphedTrainStep:
             for n in sizes:
                 offs.append(at)
                 at += n
-            blk_t, blk_f = [], []
-            for i, n in enumerate(sizes):
-                for first in range(0, n, chunk):
-                    blk_t.append(i)
-                    blk_f.append(first)
+            blk_t, blk_f, _ = chunk_tables(sizes)
             self._gatherTables[k] = dict(
                 host=torch.empty(len(params), dtype=torch.int64, pin_memory=True), ptrs=torch.empty(len(params), dtype=torch.int64, device=dev),
                 offs=torch.tensor(offs, dtype=torch.int64).to(dev), numel=torch.tensor(sizes, dtype=torch.int64).to(dev),

@@ -13,16 +13,24 @@ from _record import record
 
 pytestmark = pytest.mark.gpu
 # one element; no multiple of 4; around the 4096-element chunk; several chunks and a ragged tail; 36 full chunks; two full chunks; odd
-# sizes; [9] starts as all zeros (||p|| = 0); [10] has a zero gradient at every step (||u|| = 0 without decay)
-SHAPES = [(1,), (3,), (4095,), (4096,), (4097,), (3 * 4096 + 5,), (128, 128, 3, 3), (2, 64, 64), (5, 7, 11), (300,), (257,)]
-ZERO_PARAM, ZERO_GRAD = 9, 10
+# sizes; [9] starts as all zeros (||p|| = 0); [10] has a zero gradient at every step (||u|| = 0 without decay); [11] is, on the device, a
+# view starting 4 bytes past a 16-byte boundary
+SHAPES = [(1,), (3,), (4095,), (4096,), (4097,), (3 * 4096 + 5,), (128, 128, 3, 3), (2, 64, 64), (5, 7, 11), (300,), (257,), (1029,)]
+ZERO_PARAM, ZERO_GRAD, VIEW = 9, 10, 11
 
 
 def _params(dev, seed, dtype=torch.float32):
     g = torch.Generator().manual_seed(seed)
     vals = [torch.randn(s, generator=g) for s in SHAPES]
     vals[ZERO_PARAM].zero_()
-    return [torch.nn.Parameter(v.to(dev, dtype)) for v in vals]
+    out = [torch.nn.Parameter(v.to(dev, dtype)) for v in vals]
+    if dtype == torch.float32 and out[VIEW].is_cuda:
+        base = torch.zeros(vals[VIEW].numel() + 8, device=dev)
+        t = base[1: 1 + vals[VIEW].numel()]
+        t.copy_(vals[VIEW])
+        assert t.data_ptr() % 16 == 4 and t.is_contiguous()
+        out[VIEW] = torch.nn.Parameter(t)
+    return out
 
 
 def _fresh_grads(seed):

@@ -1,4 +1,4 @@
-"""mcquic_amd.optim.Adam / AdamW (one launch over the whole model, csrc/train_ops.hip: mcq_adam_step_f32) against torch.optim.Adam /
+"""mcquic_amd.optim.Adam / AdamW (one launch over the whole model, csrc/adam.hip: mcq_adam_step_f32) against torch.optim.Adam /
 AdamW: same parameters after several updates, checkpoints exchanged in both directions, a device learning rate, and the update
 captured inside parallel.GraphedTrainStep (the reference's step: mcquic/train/trainer.py:283 with `Adam`, configs/a800_8.yaml:20-25)."""
 import copy
@@ -7,12 +7,26 @@ import pytest
 import torch
 
 pytestmark = pytest.mark.gpu
-SHAPES = [(1,), (2, 1, 1, 1), (3,), (128,), (4097,), (128, 128, 3, 3), (2, 8192, 64), (5, 7, 11), (12288,), (128, 3, 3, 3)]
+# (the last three: both sides of the 4096-element chunk edge, and a parameter that is a view starting 4 bytes past a 16-byte boundary)
+SHAPES = [(1,), (2, 1, 1, 1), (3,), (128,), (4097,), (128, 128, 3, 3), (2, 8192, 64), (5, 7, 11), (12288,), (128, 3, 3, 3), (4095,), (4096,),
+          (1029,)]
+VIEW = 12                                                     # index of the misaligned view
 
 
 def _params(dev, seed):
     g = torch.Generator().manual_seed(seed)
-    return [torch.nn.Parameter(torch.randn(s, generator=g).to(dev)) for s in SHAPES]
+    out = []
+    for i, s in enumerate(SHAPES):
+        v = torch.randn(s, generator=g)
+        if i == VIEW:
+            base = torch.zeros(v.numel() + 8, device=dev)
+            t = base[1: 1 + v.numel()]
+            t.copy_(v)
+            assert t.data_ptr() % 16 == 4 and t.is_contiguous()
+            out.append(torch.nn.Parameter(t))
+        else:
+            out.append(torch.nn.Parameter(v.to(dev)))
+    return out
 
 
 def _grads(params, seed):
