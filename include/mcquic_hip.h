@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   13
+#define MCQ_ABI_VERSION   14
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -507,6 +507,25 @@ int mcq_sgd_step_f32(const void* ptr_tables, int32_t ntensors, const int64_t* nu
                      double weight_decay, int32_t nesterov, int32_t maximize, const double* grad_partials /* or NULL */,
                      int32_t n_grad_partials, const float* max_grad_norm /* or NULL */, float* grad_norm /* or NULL without grad_partials */,
                      int32_t skip_nonfinite, int64_t* skipped /* or NULL */, void* scalars, void* stream);
+
+/* Exponential moving average of a whole model's weights in one launch, and the in-place exchange of the live and the averaged
+ * weights (csrc/ema.hip; host mirror mcquic_amd.optim.EMA).  Tables as for mcq_adam_step_f32: row 0 of ptr_tables holds the live
+ * parameters (only read by the update), row 1 the averages, rows 2 and 3 are not read.
+ *   mcq_ema_update_f32  two launches.  A scalar kernel reads n = num_updates[0] (device int64), takes d = decay, or decay_dev[0]
+ *                       (device float) when non-NULL, with `warmup` d = min(d, (1 + n) / (10 + n)) in double, writes the weight
+ *                       w = float(1 - d) to `scalars` (16 bytes of device scratch) and stores n + 1; then one pass over 12 bytes
+ *                       per element, avg = lerp(avg, p, w) in float32 with torch's lerp (what torch.optim.swa_utils'
+ *                       get_ema_multi_avg_fn runs): avg + w (p - avg) where w < 0.5, p - (p - avg) (1 - w) otherwise, so decay 0
+ *                       leaves avg == p bit for bit.  `decay` must lie in [0, 1] (pass 0 with decay_dev).
+ *   mcq_ema_swap_f32    one launch, 16 bytes per element: rows 0 and 1 exchanged as raw 32-bit words (NaN payloads and the sign of
+ *                       -0.0 survive; two swaps are the identity on bits).
+ * 16 bytes per lane where both rows of a tensor are 16-byte aligned, dwords otherwise.  No atomics: equal inputs give equal bits.
+ * Nothing is read by the host, so both are captured like the optimizers' updates. */
+int mcq_ema_update_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                       int32_t nblocks, int64_t* num_updates, const float* decay_dev /* or NULL */, double decay, int32_t warmup,
+                       void* scalars, void* stream);
+int mcq_ema_swap_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                     int32_t nblocks, void* stream);
 
 /* u8 = trunc(clamp(((x + 1) / 2) * 255.999, 0, 255))   (mcquic/utils/vision.py:143-146 DeTransform). */
 int mcq_detransform_u8(const float* x, uint8_t* out, int64_t n, void* stream);

@@ -16,7 +16,11 @@ and flat moment buffers: csrc/lamb.hip, five launches; `REGISTRY` maps the refer
 `SGD` is torch.optim.SGD's arithmetic and checkpoint layout on the same tables with one flat momentum buffer (none without momentum):
 csrc/sgd.hip, the scalar kernel plus one pass; `max_grad_norm=` (clip_grad_norm_'s arithmetic) and `skip_nonfinite=` (a call whose
 gradient norm is inf or NaN changes nothing and is counted in `skipped`) add one pass over the gradients.  `REGISTRY["SGD"]` stays
-torch.optim.SGD, as the reference's registry has it: opt in by building `mcquic_amd.optim.SGD(model.parameters(), ...)` yourself."""
+torch.optim.SGD, as the reference's registry has it: opt in by building `mcquic_amd.optim.SGD(model.parameters(), ...)` yourself.
+
+`EMA` is not an optimizer: the exponential moving average of the weights on the same tables (row 1: the averages, one flat buffer),
+csrc/ema.hip, the scalar kernel plus one pass, and a second kernel that exchanges live and averaged weights in place to evaluate the
+average.  The reference has no such entry, so `REGISTRY` has none."""
 from __future__ import annotations
 
 import torch
@@ -24,7 +28,7 @@ import torch
 from . import _lib
 from .ops import check, _guard, _stream
 
-__all__ = ["Adam", "AdamW", "Lamb", "FusedLAMB", "SGD", "REGISTRY"]
+__all__ = ["Adam", "AdamW", "Lamb", "FusedLAMB", "SGD", "EMA", "REGISTRY"]
 
 
 def chunk_tables(sizes):
@@ -503,6 +507,195 @@ class SGD(_Planned):
                 self.state[p]["step"] = torch.tensor(count, dtype=torch.float32)
         for plan in self._plans.values():
             plan.adopted = False
+
+
+class EMA:
+    """Exponential moving average of a model's weights, the whole model in one launch (csrc/ema.hip), and the model evaluated under
+    its average without a second module or a third copy of the weights:
+
+        ema = EMA(model, decay=0.9999, warmup=True)      # model: an nn.Module, or an iterable of parameters
+        ema.update()                                     # after optimizer.step(): one scalar kernel + one pass; capturable after prepare()
+        with ema.applied(): model.eval(); ...            # the model runs under the averaged weights; the live ones come back on exit
+        ema.averaged_state_dict()                        # the model's state_dict with the averaged parameters in place of the live ones
+
+    Averaged are the floating-point parameters with `requires_grad` (float32 on a HIP device: there is no CPU path); every other entry
+    of the model's `state_dict` -- frozen parameters, buffers such as the frequency EMA -- is the live model's.  Built from an iterable
+    of parameters, exactly those are averaged.  The averages are views of ONE flat float32 buffer, initialised as a copy of the
+    parameters.  Per element, in float32, avg = lerp(avg, p, 1 - d_t) with torch's lerp (what `torch.optim.swa_utils.AveragedModel`
+    runs with `get_ema_multi_avg_fn(decay)`): avg + (1 - d_t) (p - avg), in the form p - (p - avg) d_t once 1 - d_t >= 0.5, so decay 0
+    tracks the parameters bit for bit.  d_t = decay, with `warmup` min(decay, (1 + n) / (10 + n)) after n updates: 1/10, 2/11, 3/12, ...
+    `decay` may be a 0-dim float32 device tensor, read by the kernel on every call (a schedule under capture).  The update count lives
+    on the device and is advanced there, so captured replays count; `num_updates` reads it back.
+
+    `swap()` exchanges the live and the averaged weights in place, as raw words (one launch; two swaps are the identity on bits), and
+    bumps the version counter of every swapped parameter, so eager code re-packs its operand streams and `enableGraphs` captures are
+    dropped by the weight stamp.  (`GraphedTrainStep.invalidate()`'s `_foreach_add_(params, 0.0)` would do that too but turns -0.0
+    into +0.0; the bump alone changes no value.)  While swapped, `update()` raises."""
+
+    def __init__(self, model, decay=0.9999, warmup: bool = True):
+        if isinstance(model, torch.nn.Module):
+            self.model = model
+            named = [(n, p) for n, p in model.named_parameters() if p.requires_grad and p.is_floating_point()]
+        else:
+            self.model = None
+            named = [(str(i), p) for i, p in enumerate(model)]
+        if torch.is_tensor(decay):
+            if decay.numel() != 1:
+                raise ValueError("Tensor decay must be 1-element")
+        elif not 0.0 <= decay <= 1.0:
+            raise ValueError(f"Invalid decay: {decay}")
+        if not named or not any(p.numel() for _, p in named):
+            raise ValueError("mcquic_amd.optim.EMA: nothing to average")
+        for n, p in named:
+            if p.dtype != torch.float32:
+                raise RuntimeError(f"mcquic_amd.optim.EMA: float32 parameters only ({n} is {p.dtype})")
+            if p.device != named[0][1].device:
+                raise RuntimeError("mcquic_amd.optim.EMA: the parameters must live on one device (one launch)")
+        self.decay, self.warmup = decay, bool(warmup)
+        self.names, self.params = [n for n, _ in named], [p for _, p in named]
+        self.sizes = [p.numel() for p in self.params]
+        self._offs, at = [], 0
+        for n in self.sizes:
+            self._offs.append(at)
+            at += (n + 3) // 4 * 4                            # 16-byte aligned slices, as `_Planned._flat_state` lays out optimizer state
+        dev = self.params[0].device
+        self._layout(torch.zeros(at, dtype=torch.float32, device=dev))
+        with torch.no_grad():
+            for v, p in zip(self.averages, self.params):
+                v.copy_(p)
+        self._count = torch.zeros((), dtype=torch.int64, device=dev)
+        self._scalars = torch.zeros(4, dtype=torch.float32, device=dev)
+        self.swapped = False
+
+    def _layout(self, flat) -> None:
+        self._flat = flat
+        self.averages = [flat[o: o + n].view(p.shape) for o, n, p in zip(self._offs, self.sizes, self.params)]
+        self._tables = self._key = None                       # (the tables hold the views' addresses)
+
+    # ---- device tables ---------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prepare(self) -> None:
+        """Build the device tables for the addresses the parameters have NOW, without updating anything: what
+        `parallel.GraphedTrainStep` calls before it captures `update()` (table uploads are host-to-device copies).  Rebuilt when a
+        parameter's storage address changes."""
+        dev = self.params[0].device
+        for p in self.params:
+            if not (p.is_cuda and p.is_contiguous() and p.device == dev):
+                raise RuntimeError("mcquic_amd.optim.EMA: contiguous float32 parameters on one HIP device only (there is no CPU path)")
+        key = tuple(p.data_ptr() for p in self.params)
+        if key == self._key:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("mcquic_amd.optim.EMA: parameter addresses changed since the last call; call `prepare()` before capturing "
+                               "(a host-to-device copy of the pointer table cannot be part of a graph)")
+        if self._flat.device != dev:                          # (the model moved since construction)
+            self._count, self._scalars = self._count.to(dev), self._scalars.to(dev)
+            self._layout(self._flat.to(dev))
+        if self._tables is None:
+            blk_t, blk_f, _ = chunk_tables(self.sizes)
+            self._numel = torch.tensor(self.sizes, dtype=torch.int64).to(dev)
+            self._blk_tensor = torch.tensor(blk_t, dtype=torch.int32).to(dev)
+            self._blk_first = torch.tensor(blk_f, dtype=torch.int64).to(dev)
+            self._nblocks = len(blk_t)
+            self._tables = torch.zeros(4 * len(self.params), dtype=torch.int64, device=dev)    # (rows 2 and 3 stay 0: no kernel reads them)
+        ptrs = list(key) + [v.data_ptr() for v in self.averages] + [0] * (2 * len(self.params))
+        self._tables.copy_(torch.tensor(ptrs, dtype=torch.int64))         # (stream-ordered behind the launches that read the old one)
+        self._key = key
+
+    def _table_args(self) -> tuple:
+        return (self._tables.data_ptr(), len(self.params), self._numel.data_ptr(), self._blk_tensor.data_ptr(), self._blk_first.data_ptr(),
+                self._nblocks)
+
+    # ---- the average -----------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def update(self) -> None:
+        if self.swapped:
+            raise RuntimeError("mcquic_amd.optim.EMA: the averaged weights are swapped in (`swap()` / `applied()`): the model holds the average, "
+                               "not the iterate; swap back before `update()`")
+        self.prepare()
+        decay = self.decay
+        if torch.is_tensor(decay) and (not decay.is_cuda or decay.dtype != torch.float32 or decay.numel() != 1):
+            raise TypeError("mcquic_amd.optim.EMA: a tensor decay must be one float32 on the device")
+        dev = torch.is_tensor(decay)
+        with _guard(self._flat.device):
+            check(_lib.load().mcq_ema_update_f32(*self._table_args(), self._count.data_ptr(), decay.data_ptr() if dev else None,
+                                                 0.0 if dev else float(decay), 1 if self.warmup else 0, self._scalars.data_ptr(), _stream()),
+                  "mcq_ema_update_f32")
+
+    @torch.no_grad()
+    def warm(self) -> None:
+        """One throw-away update, so that the kernels' first launch happens outside any capture; averages and count keep their bits."""
+        flat, count = self._flat.clone(), self._count.clone()
+        self.update()
+        self._flat.copy_(flat)
+        self._count.copy_(count)
+
+    @property
+    def num_updates(self) -> int:
+        """How many updates have run, captured replays included (reads the device counter: a host synchronisation)."""
+        return int(self._count)
+
+    # ---- evaluating under the average ------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def swap(self) -> None:
+        """Exchange the live and the averaged weights in place (one launch) and mark every swapped parameter changed."""
+        self.prepare()
+        with _guard(self._flat.device):
+            check(_lib.load().mcq_ema_swap_f32(*self._table_args(), _stream()), "mcq_ema_swap_f32")
+        self.swapped = not self.swapped
+        for p in self.params:
+            torch.autograd.graph.increment_version(p)
+
+    def applied(self):
+        """Context manager: swap, run the body under the averaged weights, swap back (the same bits as before)."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def ctx():
+            self.swap()
+            try:
+                yield self
+            finally:
+                self.swap()
+        return ctx()
+
+    def _averaged(self):
+        """The averaged values, wherever they are right now."""
+        return [p.detach() for p in self.params] if self.swapped else self.averages
+
+    def averaged_state_dict(self) -> dict:
+        """The model's `state_dict()` with the averaged parameters in place of the live ones (references, as `state_dict()` returns
+        them; every other entry is the live model's): what `Compressor.load_state_dict` takes."""
+        if self.model is None:
+            raise RuntimeError("mcquic_amd.optim.EMA: built from an iterable of parameters: there is no model whose state_dict to fill")
+        sd = self.model.state_dict()
+        for n, v in zip(self.names, self._averaged()):
+            sd[n] = v
+        return sd
+
+    def state_dict(self) -> dict:
+        return {"averages": {n: v.clone() for n, v in zip(self.names, self._averaged())}, "num_updates": self.num_updates,
+                "decay": float(self.decay), "warmup": self.warmup}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd) -> None:
+        """Averages (by name, into the flat buffer: the same addresses, which a captured update may hold), update count, decay (a
+        tensor decay is refilled) and warmup."""
+        if self.swapped:
+            raise RuntimeError("mcquic_amd.optim.EMA: swap back before loading")
+        if set(sd["averages"]) != set(self.names):
+            raise KeyError("mcquic_amd.optim.EMA: the checkpoint averages other parameters than this object")
+        for n, v in zip(self.names, self.averages):
+            src = sd["averages"][n]
+            if tuple(src.shape) != tuple(v.shape):
+                raise RuntimeError(f"mcquic_amd.optim.EMA: {n} has shape {tuple(v.shape)}, the checkpoint {tuple(src.shape)}")
+            v.copy_(src.to(v.device, torch.float32))
+        self._count.fill_(int(sd["num_updates"]))
+        if torch.is_tensor(self.decay):
+            self.decay.fill_(float(sd["decay"]))
+        else:
+            self.decay = float(sd["decay"])
+        self.warmup = bool(sd["warmup"])
 
 
 FusedLAMB = Lamb

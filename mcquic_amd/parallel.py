@@ -261,14 +261,19 @@ class GraphedTrainStep:
     mcquic/train/trainer.py:280; torch.nn.utils.clip_grad_norm_'s arithmetic over the flat buffer, on the device); the norm before
     clipping is `step.grad_norm` (a 0-dim device tensor, valid after each call).  An optimizer that clips by itself
     (`mcquic_amd.optim.SGD(max_grad_norm=...)`: its `grad_norm()`) goes with `max_grad_norm=None` here; setting both is refused.
+    `ema` (a `mcquic_amd.optim.EMA` of this model): `ema.update()` follows the optimizer's update, inside the post graph when that
+    is captured (two more launches; the update count and the decay's warm-up advance on the device with every replay).  The
+    constructor leaves the averages and the count bit for bit as they were, as it leaves optimizer state.  To evaluate under the
+    average between steps: `with ema.applied(): model.eval(); ...` -- the swap marks the parameters changed by itself, and a call
+    of the step while the average is swapped in raises.
     """
 
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
-                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None):
+                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None):
         if not example_x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
-        self.model, self.optimizer, self.group = model, optimizer, group
+        self.model, self.optimizer, self.group, self.ema = model, optimizer, group, ema
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.x = example_x.detach().clone()
         self.transform, self.raw = transform, None
@@ -389,6 +394,9 @@ class GraphedTrainStep:
         self.post = None
         if hasattr(self.optimizer, "prepare"):                # (mcquic_amd.optim.Adam / Lamb / SGD: device tables for the flat gradient views, built
             self.optimizer.prepare()                          #  outside the capture)
+        if self.ema is not None:                              # (its tables, and its kernels' first launch, outside the capture: a throw-away
+            self.ema.prepare()                                #  update after which averages and count have their bits back)
+            self.ema.warm()
         if capture_post:
             before = self._snapshot_optimizer_state()
             try:
@@ -565,6 +573,8 @@ class GraphedTrainStep:
             from . import ops                                 # two launches over the flat buffer, nothing read by the host
             self.grad_norm = ops.clip_by_norm_(self.flat, self.max_grad_norm)
         self.optimizer.step()
+        if self.ema is not None:
+            self.ema.update()
         off = 0
         for c in self.coders:
             n = c.countSink().numel()
@@ -585,6 +595,9 @@ class GraphedTrainStep:
     def __call__(self, x: torch.Tensor) -> torch.Tensor:
         if self.closed:
             raise RuntimeError("GraphedTrainStep: the step was closed (its count sinks are gone); build a new one")
+        if self.ema is not None and self.ema.swapped:
+            raise RuntimeError("GraphedTrainStep: the EMA's averaged weights are swapped in (`ema.applied()` / `ema.swap()`); training would "
+                               "update the average as if it were the iterate -- swap back first")
         static = self.x if self.raw is None else self.raw
         if tuple(x.shape) != tuple(static.shape):             # (`copy_` would BROADCAST a smaller batch into the static input silently)
             raise RuntimeError(f"GraphedTrainStep was captured for shards of shape {tuple(static.shape)}, got {tuple(x.shape)}")

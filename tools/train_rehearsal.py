@@ -59,6 +59,8 @@ def main():
     ap.add_argument("--own-sgd", action="store_true", help="mcquic_amd.optim.SGD(momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True): one launch behind "
                                                            "the gradient norm's pass; the optimizer clips, so the step itself does not")
     ap.add_argument("--sgd", action="store_true", help="torch.optim.SGD(momentum=0.9, lr as a float) under the step's own clipping: what --own-sgd is measured against")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="mcquic_amd.optim.EMA(model, decay=DECAY, warmup=True) inside the step's post graph; "
+                                                                               "every evaluation also reports the PSNR under `ema.applied()`")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from mcquic_amd import Compressor, parallel
@@ -85,12 +87,24 @@ def main():
     else:
         opt = torch.optim.Adam(model.parameters(), lr=lr, capturable=True, **({"fused": True} if args.fused else {}))
     x = images(args.batch, args.crop, gen, dev)
-    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if (args.lamb or args.own_sgd) else 4.0)
+    ema = None
+    if args.ema is not None:
+        from mcquic_amd import optim
+        ema = optim.EMA(model, decay=args.ema, warmup=True)
+    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if (args.lamb or args.own_sgd) else 4.0, ema=ema)
     trace = {"loss": [], "grad_norm": [], "psnr": [], "reassigned": [], "non_finite": 0}
-    model.eval()
-    step.invalidate()
-    trace["psnr"].append((0, round(psnr(model, val), 3)))
-    model.train()
+    if ema is not None:
+        trace["psnr_ema"] = []
+
+    def evaluate(i):
+        step.invalidate()
+        model.eval()
+        trace["psnr"].append((i, round(psnr(model, val), 3)))
+        if ema is not None:
+            with ema.applied():                                # (the swap marks the weights changed, in and out)
+                trace["psnr_ema"].append((i, round(psnr(model, val), 3)))
+        model.train()
+    evaluate(0)
     torch.cuda.synchronize()
     t_steps = 0.0
     for i in range(1, args.steps + 1):
@@ -112,10 +126,7 @@ def main():
             trace["_mem_first"] = round(torch.cuda.memory_allocated(dev) / 2 ** 20, 1)
         if i % args.every == 0:
             trace["non_finite"] += sum(int(not torch.isfinite(p).all()) for p in model.parameters())
-            step.invalidate()
-            model.eval()
-            trace["psnr"].append((i, round(psnr(model, val), 3)))
-            model.train()
+            evaluate(i)
             if i % (2 * args.every) == 0 and i < args.steps:
                 trace["reassigned"].append((i, round(float(model.reAssignCodebook()), 4)))
     mem = {"allocated_mb_after_first_period": None, "allocated_mb_at_end": round(torch.cuda.memory_allocated(dev) / 2 ** 20, 1),
@@ -129,7 +140,8 @@ def main():
            "model": f"Compressor({args.channel}, {args.m}, {ks})", "lr": args.lr, "lr_warmup_steps": args.warmup, "optimizer": "mcquic_amd.optim.Lamb(max_grad_norm=4.0), no clipping in the step" if args.lamb else "mcquic_amd.optim.Adam" if args.own_adam else "mcquic_amd.optim.SGD(momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True), no clipping in the step" if args.own_sgd else "torch SGD(momentum=0.9) foreach" if args.sgd else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "crop": args.crop, "steps": args.steps,
            "ms_per_step": round(t_steps / args.steps * 1e3, 3), "loss_first": round(first, 6), "loss_last": round(last, 6),
            "psnr_first": trace["psnr"][0][1], "psnr_last": trace["psnr"][-1][1], "memset_nodes_ok": parallel.memset_nodes_replay_correctly(dev), "memory": mem,
-           **({"skipped": int(opt.skipped)} if args.own_sgd else {}), **trace}
+           **({"skipped": int(opt.skipped)} if args.own_sgd else {}),
+           **({"ema": {"decay": args.ema, "warmup": True, "num_updates": ema.num_updates}} if ema is not None else {}), **trace}
     line = json.dumps(out)
     print(line)
     if args.out:
