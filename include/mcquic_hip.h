@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   14
+#define MCQ_ABI_VERSION   15
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -401,6 +401,18 @@ int mcq_conv2d_wgrad_s2_nchw_f32(const float* x, const float* dy, float* dw, flo
 size_t mcq_conv2d_wgrad1x1_nchw_workspace_floats(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout);
 int mcq_conv2d_wgrad1x1_nchw_f32(const float* x, const float* dy, float* dw, float* dbias, float* workspace, int32_t N, int32_t Cin,
                                  int32_t H, int32_t W, int32_t Cout, int32_t square_x, void* stream);
+
+/* Read-only: the plan the strip walk of the three entry points above would run for X [N,Cin,H,W] -- `taps` 9 or 1, `stride2` the
+ * 3x3 stride-2 form (H, W: the input map, as its entry point takes them), `nconv` the convolutions sharing the launch (only
+ * mcq_conv2d_wgrad_nchw_group_f32 launches more than one; for the other forms the plan is what the planner would hand such a
+ * launch).  out[9] = {F, strips, row_chunks, rpc, units, splits, ups, groups, gmax}: floats a lane reads per row, strips per row,
+ * row ranges per (image, strip), rows per range, walks = N strips row_chunks, waves per tile, walks per wave, workgroups per tile
+ * and convolution = ceil(splits / 4), and the groups the workspace query sizes by -- after the fall-back of a grouped plan that
+ * would need more groups than that to the one-by-one plan.  The launch writes nconv * groups * (taps Cout Cin + 4 Cout) floats
+ * of `workspace`.  Host code only; the planner the launchers call.  Returns 1, or 0 (out untouched) for a shape the strip walk
+ * does not take: the one-pass 16 x 16-tile kernel's, the small-map kernel's, or one for the NHWC entry point. */
+int32_t mcq_conv2d_wgrad_nchw_plan(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t taps, int32_t stride2,
+                                   int32_t nconv, int32_t* out);
 
 /* out[c] = sum_{n,p} x[n][c][p]   (bias / beta gradients); optional workspace of min(N, 16) * C floats. */
 int mcq_channel_sum_f32(const float* x, float* out, float* workspace, int32_t N, int32_t C, int32_t HW, void* stream);

@@ -113,6 +113,7 @@ SYMBOLS = {
     "mcq_conv2d_wgrad1x1_nchw_workspace_floats": (c_size_t, [c_int32] * 5),
     "mcq_conv2d_wgrad1x1_nchw_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                                c_int32, c_int32, c_void_p]),
+    "mcq_conv2d_wgrad_nchw_plan": (c_int32, [c_int32] * 8 + [c_void_p]),
     "mcq_wgrad_defer": (None, [c_int32]),
     "mcq_wgrad_pending": (c_int32, []),
     "mcq_wgrad_flush": (c_int32, [c_int32, c_void_p]),
@@ -180,7 +181,7 @@ SYMBOLS = {
     "mcq_abi_version": (c_int32, []),
 }
 
-ABI_VERSION = 14      # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
+ABI_VERSION = 15     # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
 
 _lib = None
 

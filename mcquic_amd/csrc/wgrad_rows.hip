@@ -814,6 +814,18 @@ inline unsigned rows_fill(WgRowsK& p, WgRowsReduceK& q, const RowsPlan& r, const
 
 // a single problem's one-element pointer tables
 struct OneConv { const float* x[1]; const float* dy[1]; float* dw[1]; float* dbias[1]; };
+
+// The plan a launch of `nconv` convolutions runs (H, W: the map the walk runs over).  The workspace query sizes by the one-by-one
+// plan's gmax: a grouped plan that would need more groups than that (the shared-splits path rounds upwards) falls back to the
+// one-by-one plan instead of overrunning the workspace.
+inline bool rows_launch_plan(int N, int Cin, int H, int W, int Cout, RowsPlan& r, int taps, bool stride2, int nconv) {
+    if (!rows_plan(N, Cin, H, W, Cout, r, taps, stride2, nconv)) return false;
+    if (nconv > 1) {
+        RowsPlan one;
+        if (rows_plan(N, Cin, H, W, Cout, one, taps, stride2) && r.groups > one.gmax) r = one;
+    }
+    return true;
+}
 }  // namespace
 
 extern "C" int32_t mcq_conv2d_wgrad_nchw_max_group(void) { return ROWS_MAX_CONVS; }
@@ -840,14 +852,7 @@ extern "C" int mcq_conv2d_wgrad_nchw_group_f32(const float* const* x, const floa
         return mcq_check_launch();
     }
     RowsPlan r;
-    bool planned = rows_plan(N, Cin, H, W, Cout, r, 9, false, nconv);
-    if (planned && nconv > 1) {
-        // the workspace query sizes by the one-by-one plan's gmax: a grouped plan that would need more groups than that (the
-        // shared-splits path rounds upwards) falls back to the one-by-one plan instead of overrunning the workspace
-        RowsPlan one;
-        if (rows_plan(N, Cin, H, W, Cout, one) && r.groups > one.gmax) r = one;
-    }
-    if (!planned) {      // (never more groups than the nconv = 1 plan the workspace query assumes)
+    if (!rows_launch_plan(N, Cin, H, W, Cout, r, 9, false, nconv)) {      // (planned: never more groups than the nconv = 1 plan the workspace query assumes)
         if (!tiny_shape(N, Cin, H, W, Cout)) return MCQ_EINVAL;
         WgTinyK t;
         fill_slots(t.x, x, nconv); fill_slots(t.dy, dy, nconv); fill_slots(t.dw, dw, nconv); fill_slots(t.dbias, dbias, nconv);
@@ -934,6 +939,18 @@ extern "C" int mcq_conv2d_wgrad_s2_nchw_f32(const float* x, const float* dy, flo
     else hipLaunchKernelGGL(conv_wgrad_rows_s2_kernel<false>, grid, dim3(256), 0, s, p);
     reduce_pass(q, gx, s);
     return mcq_check_launch();
+}
+
+extern "C" int32_t mcq_conv2d_wgrad_nchw_plan(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t taps, int32_t stride2,
+                                              int32_t nconv, int32_t* out) {
+    if (!out || (taps != 9 && taps != 1) || (taps == 1 && stride2) || nconv < 1 || nconv > ROWS_MAX_CONVS) return 0;
+    if (stride2 ? ((H & 1) || (W & 1)) : wgt16_shape(N, Cin, H, W, Cout)) return 0;          // (few pixels: the one-pass kernel of wgrad_t16.h)
+    if (taps == 1 && (H & 1)) return 0;
+    RowsPlan r;
+    if (!rows_launch_plan(N, Cin, stride2 ? H / 2 : H, stride2 ? W / 2 : W, Cout, r, taps, stride2 != 0, nconv)) return 0;
+    const int32_t plan[9] = {r.F, r.strips, r.row_chunks, r.rpc, r.units, r.splits, r.ups, r.groups, r.gmax};
+    for (int i = 0; i < 9; ++i) out[i] = plan[i];
+    return 1;
 }
 
 extern "C" void mcq_wgrad_defer(int32_t on) {
