@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   15
+#define MCQ_ABI_VERSION   16
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -538,6 +538,35 @@ int mcq_ema_update_f32(const void* ptr_tables, int32_t ntensors, const int64_t* 
                        void* scalars, void* stream);
 int mcq_ema_swap_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
                      int32_t nblocks, void* stream);
+
+/* Per-step training telemetry kept on the device (csrc/step_meter.hip; host mirror mcquic_amd.monitor.StepMeter): what the
+ * reference's trainer reports after an update (mcquic/train/trainer.py:423-441, 463-491) as one float32 row per step in a ring
+ * buffer, written by two launches that read every per-step value through a device pointer.  Level tables as for
+ * mcq_freq_ema_update_f32 (host arrays of `levels` <= MCQ_VQ_MAX_LEVELS entries); `counts` = this step's global [m_l, k_l] code
+ * histograms back to back (int64).
+ *   launch 1  one workgroup per (level, group) row; into `workspace` (mcq_step_meter_workspace_bytes(m, k, levels) bytes, 8-byte
+ *             aligned: total int64 [rows], used int32 [rows], hit int32 [rows], ema_entropy float [rows], step_bits float [rows]):
+ *               used         entries with f / sum f > 1e-6 (strict; the sum and the quotient in double)
+ *               ema_entropy  -sum p log2 p of the normalised frequency row (a zero entry contributes 0)
+ *               hit          entries with a non-zero count
+ *               total        the sum of the row's counts, exact
+ *               step_bits    total * (-sum q log2 q), q = count / total; 0 when total == 0, never NaN
+ *   launch 2  one wave.  db = -10 log10(loss / upper_bound^2); the shadow (state[2], a float32 in the low word) is set to db while
+ *             it is NaN and afterwards shadow -= (1 - momentum) (shadow - db), float32 op by op (validate/utils.py:6-28);
+ *             state[1] (first_bad_step, -1 = none) is set to the step number the first time loss or grad_norm is inf / NaN, or the
+ *             shadow is NaN or < `floor` (NaN: that test is off); the row goes to ring[count % capacity], count to
+ *             steps[count % capacity], and state[0] (count) is advanced.  Row, mcq_step_meter_columns(levels) = 8 + 4 levels floats:
+ *               0 loss  1 db  2 shadow  3 grad_norm (NaN if NULL)  4 lr (lr_dev[0], or `lr` by value if NULL: pass NaN for none)
+ *               5 skipped (0 if NULL)  6 sum used / sum m_l k_l  7 sum step_bits / pixels
+ *               8 + 4 l ..: used_l / (m_l k_l), mean_g ema_entropy, hit_l / (m_l k_l), sum_g step_bits / sum_g total (0 if that is 0)
+ * No atomics: equal inputs give equal bits.  Nothing is read by the host. */
+size_t mcq_step_meter_workspace_bytes(const int32_t* m, const int32_t* k, int32_t levels);      /* 0 for an invalid table */
+int32_t mcq_step_meter_columns(int32_t levels);                                                 /* 0 for levels out of range */
+int mcq_step_meter_update_f32(const float* const* freq_ema /* [levels] device pointers */, const int32_t* m, const int32_t* k,
+                              int32_t levels, const int64_t* counts, void* workspace, const float* loss, const float* grad_norm /* or NULL */,
+                              const float* lr_dev /* or NULL */, double lr, const int64_t* skipped /* or NULL */, double upper_bound,
+                              double momentum, double floor, double pixels, int64_t* state /* device [4] */, int64_t* steps /* [capacity] */,
+                              float* ring /* [capacity][columns] */, int64_t capacity, void* stream);
 
 /* u8 = trunc(clamp(((x + 1) / 2) * 255.999, 0, 255))   (mcquic/utils/vision.py:143-146 DeTransform). */
 int mcq_detransform_u8(const float* x, uint8_t* out, int64_t n, void* stream);

@@ -146,6 +146,10 @@ SYMBOLS = {
     "mcq_ema_update_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_double, c_int32, c_void_p,
                                      c_void_p]),
     "mcq_ema_swap_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "mcq_step_meter_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int32]),
+    "mcq_step_meter_columns": (c_int32, [c_int32]),
+    "mcq_step_meter_update_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
+                                            c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mcq_sumsq_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mcq_clip_by_norm_f32": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_int64, c_void_p]),
     "mcq_detransform_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),
@@ -181,7 +185,7 @@ SYMBOLS = {
     "mcq_abi_version": (c_int32, []),
 }
 
-ABI_VERSION = 15     # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
+ABI_VERSION = 16     # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
 
 _lib = None
 

@@ -1,0 +1,205 @@
+"""Training telemetry that stays on the device: what the reference's trainer reports after every update
+(mcquic/train/trainer.py:423-441 `_stepFinishHook`: the distortion in dB, its `EMATracker((), 0.99)` shadow, gradient norm, learning
+rate, the `Loss becomes NAN. Train crashed.` guard; trainer.py:463-491 `log`: `CodeUsage` and the per-level code statistics), recorded as
+one float32 row per step in a ring buffer by two HIP launches (csrc/step_meter.hip) that read every value through a device pointer.
+The host copies the buffer back when it likes, with one copy; nothing else here synchronises, so the launches sit in the captured
+post graph of `parallel.GraphedTrainStep(..., meter=...)` and a replay stays free of host reads.
+"""
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .ops import _guard, _stream, check
+
+HEAD = ("loss", "db", "db_ema", "grad_norm", "lr", "skipped", "code_usage", "bpp")
+PER_LEVEL = ("usage", "ema_entropy", "hit", "step_entropy")
+_STATE = 4                                                    # int64 words in front of `steps`: count, first_bad_step, shadow, reserved
+
+
+class StepMeter:
+    """One row per training step, kept on the device:
+
+        meter = StepMeter(model, capacity=1024, pixels=n * H * W, upper_bound=1.0, momentum=0.99, floor=0.1)
+        step = parallel.GraphedTrainStep(model, opt, example_x, ..., meter=meter)       # or, by hand: meter.update(loss, counts, ...)
+        rows = meter.read()          # ONE device-to-host copy: the rows recorded since the last read(), as numpy arrays
+        meter.check()                # raises `Loss becomes NAN. Train crashed.` once the watchdog has tripped (reads one word)
+
+    `model`: anything whose modules include the entropy coder(s) (`EntropyCoder` / `VariousMCoder`: what has `deferCounts`); their
+    frequency EMAs give the levels (m_l, k_l).  Columns of a row (`read()` keys; the per-level ones are [rows, levels] arrays):
+
+        loss, db, db_ema     the loss given to `update`, -10 log10(loss / upper_bound^2) (`Decibel`: upper_bound 1.0 for MsSSIM, 2.0 for
+                             PSNR) and its EMATracker shadow with `momentum`, float32 op by op as the reference computes them
+        grad_norm, lr        as given (NaN when not given);  skipped: the optimizer's skip count (0 when not given)
+        code_usage           the reference's `CodeUsage` of the frequency EMA: entries with f / sum f > 1e-6 over all entries of all levels
+        bpp                  `validate.ideal_bpp` of THIS step's code histograms over `pixels` (the image pixels behind `counts`: all ranks')
+        usage, ema_entropy   per level: used entries / all entries; entropy of the normalised EMA rows in bits per code, mean over groups
+        hit, step_entropy    per level: codewords this step used / all entries; entropy of this step's codes in bits per code
+
+    `first_bad_step` (0-dim int64 device tensor, -1 = none) is set, and stays set, the first time the loss or the gradient norm is inf / NaN
+    or the shadow is NaN or below `floor` (the reference's 0.1; None switches that test off).  The ring holds the last `capacity` rows;
+    `read()` reports how many were overwritten unread as `dropped`.  HIP device and float32 only: there is no CPU path."""
+
+    def __init__(self, model, capacity: int = 1024, pixels: int = 1, upper_bound: float = 1.0, momentum: float = 0.99,
+                 floor: Optional[float] = 0.1):
+        coders = [m for m in model.modules() if hasattr(m, "deferCounts")]
+        if not coders:
+            raise ValueError("mcquic_amd.monitor.StepMeter: the model has no entropy coder (no module with `deferCounts`)")
+        self.freqs = [f for c in coders for f in c._freqEMA]
+        for f in self.freqs:
+            if not f.is_cuda:
+                raise RuntimeError(f"mcquic_amd: the model's frequency tables must live on a HIP device (got {f.device}); "
+                                   "the HIP kernels have no CPU fallback")
+            if f.dtype != torch.float32:
+                raise TypeError(f"mcquic_amd: the model's frequency tables must be torch.float32 (got {f.dtype})")
+            if f.device != self.freqs[0].device:
+                raise RuntimeError("mcquic_amd.monitor.StepMeter: the coders must live on one device")
+        if capacity < 1 or not pixels > 0 or not upper_bound > 0 or not 0.0 <= momentum <= 1.0:
+            raise ValueError("mcquic_amd.monitor.StepMeter: capacity >= 1, pixels > 0, upper_bound > 0 and 0 <= momentum <= 1 are required")
+        self.ms, self.ks = [int(f.shape[0]) for f in self.freqs], [int(f.shape[1]) for f in self.freqs]
+        self.levels = len(self.freqs)
+        lib = _lib.load()
+        if self.levels > int(lib.mcq_vq_max_levels()):
+            raise ValueError(f"mcquic_amd.monitor.StepMeter: {self.levels} levels, the kernels' tables hold {int(lib.mcq_vq_max_levels())}")
+        self.capacity, self.pixels = int(capacity), float(pixels)
+        self.upper_bound, self.momentum, self.floor = float(upper_bound), float(momentum), floor
+        self.columns = int(lib.mcq_step_meter_columns(self.levels))
+        self.entries = sum(m * k for m, k in zip(self.ms, self.ks))
+        dev = self.freqs[0].device
+        # ONE buffer, so that read() is one copy: [count, first_bad_step, shadow (float32 in the low word), -] [steps] [ring]
+        words = _STATE + self.capacity + (self.capacity * self.columns + 1) // 2
+        self._buf = torch.zeros(words, dtype=torch.int64, device=dev)
+        self._count, self.first_bad_step = self._buf[0], self._buf[1]
+        self._shadow = self._buf[2:3].view(torch.float32)[0]
+        self._steps = self._buf[_STATE: _STATE + self.capacity]
+        self._ring = self._buf[_STATE + self.capacity:].view(torch.float32)[: self.capacity * self.columns].view(self.capacity, self.columns)
+        self.first_bad_step.fill_(-1)
+        self._shadow.fill_(float("nan"))
+        self._last_read = 0
+        self._tables = self._key = self._ws = None
+
+    # ---- launch tables -------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prepare(self) -> None:
+        """The level tables and the workspace for the addresses the frequency tables have NOW; `parallel.GraphedTrainStep` calls it
+        before it captures `update()`.  Rebuilt when a table's storage address changes (not inside a capture)."""
+        key = tuple(f.data_ptr() for f in self.freqs)
+        if key == self._key:
+            return
+        for f in self.freqs:
+            if not (f.is_cuda and f.is_contiguous() and f.device == self._buf.device):
+                raise RuntimeError("mcquic_amd.monitor.StepMeter: contiguous frequency tables on the meter's HIP device only (there is no CPU path)")
+        if torch.cuda.is_current_stream_capturing() and self._ws is None:
+            raise RuntimeError("mcquic_amd.monitor.StepMeter: call `prepare()` before capturing (the workspace cannot be allocated inside a graph)")
+        n = self.levels
+        ms, ks = (ctypes.c_int32 * n)(*self.ms), (ctypes.c_int32 * n)(*self.ks)
+        if self._ws is None:
+            nbytes = int(_lib.load().mcq_step_meter_workspace_bytes(ms, ks, n))
+            if nbytes <= 0:
+                raise ValueError("mcquic_amd.monitor.StepMeter: the level table is not one the kernels take")
+            self._ws = torch.zeros((nbytes + 7) // 8, dtype=torch.int64, device=self._buf.device)
+        self._tables = ((ctypes.c_void_p * n)(*key), ms, ks)
+        self._key = key
+
+    def partials(self) -> dict:
+        """The five per-(level, group) partials of the last `update` (device views of the workspace, rows in level-then-group order)."""
+        rows = sum(self.ms)
+        w32 = self._ws[rows:].view(torch.int32)
+        return {"total": self._ws[:rows], "used": w32[:rows], "hit": w32[rows: 2 * rows],
+                "ema_entropy": w32[2 * rows: 3 * rows].view(torch.float32), "step_bits": w32[3 * rows: 4 * rows].view(torch.float32)}
+
+    # ---- one step ------------------------------------------------------------------------------------------------------------
+    @staticmethod
+    def _scalar(t, name: str, dtype, dev):
+        if t is None:
+            return None
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"mcquic_amd: `{name}` must live on the meter's HIP device; the HIP kernels have no CPU fallback")
+        if t.dtype != dtype or t.numel() != 1:
+            raise TypeError(f"mcquic_amd: `{name}` must be one {dtype} value (got {t.dtype}, {tuple(t.shape)})")
+        return t.data_ptr()
+
+    @torch.no_grad()
+    def update(self, loss: torch.Tensor, counts: torch.Tensor, grad_norm: Optional[torch.Tensor] = None, lr=None,
+               skipped: Optional[torch.Tensor] = None) -> None:
+        """Record one step: two launches on the current stream, capturable after `prepare()`.  `loss`, `grad_norm`: 0-dim float32 device
+        tensors; `counts`: this step's global code histograms, all levels back to back (int64, what `applyCounts` takes); `lr`: a 0-dim
+        float32 device tensor (read on the device at every launch or replay) or a host number (recorded as it is now); `skipped`: 0-dim int64."""
+        self.prepare()
+        dev = self._buf.device
+        if not (torch.is_tensor(counts) and counts.is_cuda and counts.device == dev):
+            raise RuntimeError("mcquic_amd: `counts` must live on the meter's HIP device; the HIP kernels have no CPU fallback")
+        if counts.dtype != torch.int64 or counts.numel() != self.entries or not counts.is_contiguous():
+            raise ValueError(f"mcquic_amd.monitor.StepMeter: `counts` must be {self.entries} contiguous int64 entries (sum of m_l * k_l)")
+        lr_ptr, lr_val = None, float("nan")
+        if torch.is_tensor(lr) and lr.is_cuda:
+            lr_ptr = self._scalar(lr, "lr", torch.float32, dev)
+        elif lr is not None:
+            lr_val = float(lr)
+        ptrs, ms, ks = self._tables
+        with _guard(dev):
+            check(_lib.load().mcq_step_meter_update_f32(
+                ptrs, ms, ks, self.levels, counts.data_ptr(), self._ws.data_ptr(), self._scalar(loss, "loss", torch.float32, dev),
+                self._scalar(grad_norm, "grad_norm", torch.float32, dev), lr_ptr, lr_val, self._scalar(skipped, "skipped", torch.int64, dev),
+                self.upper_bound, self.momentum, float("nan") if self.floor is None else float(self.floor), self.pixels,
+                self._buf.data_ptr(), self._steps.data_ptr(), self._ring.data_ptr(), self.capacity, _stream()), "mcq_step_meter_update_f32")
+
+    @torch.no_grad()
+    def warm(self) -> None:
+        """One throw-away update, so that the kernels' first launch happens outside any capture; count, shadow, watchdog and ring keep
+        their bits."""
+        self.prepare()
+        dev = self._buf.device
+        keep = self._buf.clone()
+        self.update(torch.ones((), dtype=torch.float32, device=dev), torch.zeros(self.entries, dtype=torch.int64, device=dev))
+        self._buf.copy_(keep)
+
+    # ---- the host side ---------------------------------------------------------------------------------------------------------
+    def read(self) -> dict:
+        """The rows recorded since the last `read()` (at most the last `capacity`), in step order: numpy arrays keyed by column name, per-level
+        columns as [rows, levels], plus `steps`; `dropped` rows were overwritten before they were read; `count` and `first_bad_step` as
+        of this copy.  One device-to-host copy of the buffer (a host synchronisation: call it when you want to look, not every step)."""
+        host = self._buf.cpu().numpy()
+        count, bad = int(host[0]), int(host[1])
+        first = max(self._last_read, count - self.capacity)
+        dropped = max(0, first - self._last_read)
+        slots = np.arange(first, max(first, count)) % self.capacity
+        ring = host[_STATE + self.capacity:].view(np.float32)[: self.capacity * self.columns].reshape(self.capacity, self.columns)[slots]
+        out = {"steps": host[_STATE: _STATE + self.capacity][slots].copy(), "dropped": dropped, "count": count, "first_bad_step": bad}
+        for i, name in enumerate(HEAD):
+            out[name] = ring[:, i].copy()
+        per = ring[:, len(HEAD):].reshape(len(slots), self.levels, len(PER_LEVEL))
+        for i, name in enumerate(PER_LEVEL):
+            out[name] = per[:, :, i].copy()
+        self._last_read = max(self._last_read, count)
+        return out
+
+    def check(self) -> None:
+        """Raise as the reference's trainer does (trainer.py:435-437) if the watchdog has tripped (reads `first_bad_step` back)."""
+        bad = int(self.first_bad_step)
+        if bad >= 0:
+            raise RuntimeError(f"Loss becomes NAN. Train crashed. (first bad step: {bad})")
+
+    def state_dict(self) -> dict:
+        """Count, shadow, watchdog, ring and step numbers (device copies: nothing is read back), and the host's read position."""
+        return {"count": self._count.clone(), "shadow": self._shadow.clone(), "first_bad_step": self.first_bad_step.clone(),
+                "ring": self._ring.clone(), "steps": self._steps.clone(), "last_read": self._last_read}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd) -> None:
+        """Into the buffer this meter already has (the addresses a captured `update` holds): a resumed run continues its numbering."""
+        if tuple(sd["ring"].shape) != tuple(self._ring.shape):
+            raise RuntimeError(f"mcquic_amd.monitor.StepMeter: the checkpoint's ring is {tuple(sd['ring'].shape)}, this meter's "
+                               f"{tuple(self._ring.shape)} (capacity, 8 + 4 levels)")
+        dev = self._buf.device
+        self._count.copy_(sd["count"].to(dev, torch.int64))
+        self._shadow.copy_(sd["shadow"].to(dev, torch.float32))
+        self.first_bad_step.copy_(sd["first_bad_step"].to(dev, torch.int64))
+        self._ring.copy_(sd["ring"].to(dev, torch.float32))
+        self._steps.copy_(sd["steps"].to(dev, torch.int64))
+        self._last_read = int(sd.get("last_read", 0))
+

@@ -266,14 +266,21 @@ class GraphedTrainStep:
     constructor leaves the averages and the count bit for bit as they were, as it leaves optimizer state.  To evaluate under the
     average between steps: `with ema.applied(): model.eval(); ...` -- the swap marks the parameters changed by itself, and a call
     of the step while the average is swapped in raises.
+    `meter` (a `mcquic_amd.monitor.StepMeter` of this model): `meter.update(...)` is the LAST thing of the update, after the frequency
+    EMA (its EMA columns describe the table the next `compress` would use), inside the post graph when that is captured (two more
+    launches).  It records `self.loss` -- this rank's LOCAL loss: no collective is added for a global one --, the global code counts,
+    the gradient norm before clipping (the step's, or the optimizer's own where it computes one: `optim.Lamb`, `optim.SGD` with `max_grad_norm` or `skip_nonfinite`), the first parameter group's learning rate (read
+    on the device at every replay when it is a device tensor, as it is now when it is a host number) and the optimizer's `skipped`
+    count where it has one.  The constructor leaves the meter's count, shadow and ring bit for bit as they were.  Without a meter
+    not one launch changes.
     """
 
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
-                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None):
+                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None):
         if not example_x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
-        self.model, self.optimizer, self.group, self.ema = model, optimizer, group, ema
+        self.model, self.optimizer, self.group, self.ema, self.meter = model, optimizer, group, ema, meter
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.x = example_x.detach().clone()
         self.transform, self.raw = transform, None
@@ -397,6 +404,9 @@ class GraphedTrainStep:
         if self.ema is not None:                              # (its tables, and its kernels' first launch, outside the capture: a throw-away
             self.ema.prepare()                                #  update after which averages and count have their bits back)
             self.ema.warm()
+        if self.meter is not None:                            # (the same for the meter: count, shadow and ring keep their bits)
+            self.meter.prepare()
+            self.meter.warm()
         if capture_post:
             before = self._snapshot_optimizer_state()
             try:
@@ -580,6 +590,20 @@ class GraphedTrainStep:
             n = c.countSink().numel()
             c.applyCounts(self.counts[off: off + n])
             off += n
+        if self.meter is not None:
+            self._meter_update()
+
+    def _meter_update(self):
+        """The telemetry row of this step (monitor.StepMeter.update): every value goes by device pointer, nothing is read here."""
+        opt = self.optimizer
+        norm = self.grad_norm
+        wants = getattr(opt, "_wants_norm", None)             # (mcquic_amd.optim: Lamb always; SGD with max_grad_norm or skip_nonfinite)
+        if norm is None and callable(wants) and wants():
+            norm = opt.grad_norm                              # (SGD: a method; Lamb: a property)
+            norm = norm() if callable(norm) else norm
+        skipped = getattr(opt, "skipped", None)
+        self.meter.update(self.loss, self.counts, grad_norm=norm, lr=opt.param_groups[0]["lr"],
+                          skipped=skipped if torch.is_tensor(skipped) else None)
 
     def _start_all_reduce(self, buf: torch.Tensor):
         """Sum `buf` over the ranks without waiting for it: under RCCL an async all-reduce (its stream waits for what the current
