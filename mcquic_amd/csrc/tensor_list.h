@@ -1,9 +1,10 @@
-// MANY tensors in one launch: the device tables that Adam (adam.hip), LAMB (lamb.hip), SGD (sgd.hip) and the gradient gather
-// (train_ops.hip: gather_flat_kernel) walk, and the workgroup sum the optimizers share.  Not for the convolution sources.
+// MANY tensors in one launch: the device tables that Adam (adam.hip), LAMB (lamb.hip), SGD (sgd.hip), the weight average (ema.hip) and
+// the gradient gather (train_ops.hip: gather_flat_kernel) walk, and the workgroup sum the optimizers share.  Not for the convolution
+// sources.  The host builds the tables in mcquic_amd/tensor_list.py, class for struct (ChunkTable, TensorList).
 //
 // torch's fused Adam passes its tensor lists through kernel arguments (4 KB): 19 launches of ~91 us for this model's 666 tensors =
-// 1.7 ms per step at 0.8 TB/s.  Here the lists live in device memory -- pointer tables [4][ntensors] (row k of tensor t at
-// ptrs[k * ntensors + t]; Adam, LAMB: param, grad, exp_avg, exp_avg_sq; SGD: param, grad, momentum buffer, unused), numel[ntensors],
+// 1.7 ms per step at 0.8 TB/s.  Here the lists live in device memory -- pointer tables [rows][ntensors] (row k of tensor t at
+// ptrs[k * ntensors + t]; Adam, LAMB: param, grad, exp_avg, exp_avg_sq; SGD: param, grad, momentum buffer; EMA: param, average), numel[ntensors],
 // and a block table (tensor, first element) with one entry per MCQ_LIST_CHUNK-element chunk, workgroup b taking entry b -- so the
 // whole model is ONE launch of ~13 k workgroups.  A tensor without elements owns no chunk.
 #pragma once

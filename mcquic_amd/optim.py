@@ -27,23 +27,9 @@ import torch
 
 from . import _lib
 from .ops import check, _guard, _stream
+from .tensor_list import TensorList, chunk_tables, flat_layout  # noqa: F401  (`optim.chunk_tables` stays importable)
 
 __all__ = ["Adam", "AdamW", "Lamb", "FusedLAMB", "SGD", "EMA", "REGISTRY"]
-
-
-def chunk_tables(sizes):
-    """The host side of the chunk tables the whole-model kernels walk (csrc/tensor_list.h), for tensors of `sizes` elements:
-    (blk_tensor, blk_first, tensor_first_blk) -- one (tensor, first element) entry per chunk of mcq_adam_chunk() elements, in tensor
-    order, and [len(sizes) + 1] chunk offsets: tensor i owns the chunks [tensor_first_blk[i], tensor_first_blk[i + 1]); a tensor
-    without elements owns none."""
-    chunk = _lib.load().mcq_adam_chunk()
-    blk_tensor, blk_first, tensor_first_blk = [], [], [0]
-    for i, n in enumerate(sizes):
-        for first in range(0, n, chunk):
-            blk_tensor.append(i)
-            blk_first.append(first)
-        tensor_first_blk.append(len(blk_tensor))
-    return blk_tensor, blk_first, tensor_first_blk
 
 
 class _Planned(torch.optim.Optimizer):
@@ -63,13 +49,9 @@ class _Planned(torch.optim.Optimizer):
 
     # ---- state in flat buffers -------------------------------------------------------------------------------------------------
     class _Plan:
-        __slots__ = ("key", "tables", "numel", "blk_tensor", "blk_first", "nblocks", "flat_m", "flat_v", "views", "step", "scalars", "ntensors",
-                     "sizes", "ids", "adopted", "names")
-
-        def table_args(self) -> tuple:
-            """The leading arguments of every entry point that walks the tables."""
-            return (self.tables.data_ptr(), self.ntensors, self.numel.data_ptr(), self.blk_tensor.data_ptr(), self.blk_first.data_ptr(),
-                    self.nblocks)
+        __slots__ = ("table", "flat_m", "flat_v", "views", "step", "scalars", "ids", "adopted", "names")
+        ntensors = property(lambda self: self.table.ntensors)
+        nblocks = property(lambda self: self.table.nblocks)
 
     def _flat_state(self, gi: int, params):
         """The plan of group `gi` for `params`: `flat_m` / `flat_v` (the flat buffers of the group's first / second state name, None where
@@ -86,25 +68,16 @@ class _Planned(torch.optim.Optimizer):
             # (also when the set of parameters that carry a gradient changed: fresh buffers, the old state is copied over below)
             plan = self._plans[gi] = type(self)._Plan()
             dev = params[0].device
-            plan.sizes, plan.ids, plan.names = sizes, ids, names
-            offs, at = [], 0
-            for n in sizes:
-                offs.append(at)
-                at += (n + 3) // 4 * 4                        # 16-byte aligned slices
-            flats = [torch.zeros(at, dtype=torch.float32, device=dev) for _ in names]
+            plan.ids, plan.names = ids, names
+            offs, total = flat_layout(sizes)
+            flats = [torch.zeros(total, dtype=torch.float32, device=dev) for _ in names]
             plan.flat_m, plan.flat_v = (flats + [None, None])[:2]
             plan.views = [tuple(f[o: o + n].view_as(p) for f in flats) for o, n, p in zip(offs, sizes, params)]
             plan.step = torch.zeros((), dtype=torch.float32, device=dev)
             plan.scalars = torch.zeros(4, dtype=torch.float32, device=dev)
-            plan.ntensors, plan.key = len(params), None
-            # the chunk table depends on the sizes only; the pointer table is ONE device buffer for the plan's lifetime, refilled in
-            # place when an address changes (a captured graph that reads it keeps a valid address and sees the current pointers)
-            blk_t, blk_f, _ = chunk_tables(sizes)
-            plan.numel = torch.tensor(sizes, dtype=torch.int64).to(dev)
-            plan.blk_tensor = torch.tensor(blk_t, dtype=torch.int32).to(dev)
-            plan.blk_first = torch.tensor(blk_f, dtype=torch.int64).to(dev)
-            plan.nblocks = len(blk_t)
-            plan.tables = torch.zeros(4 * len(params), dtype=torch.int64, device=dev)
+            plan.table = TensorList(sizes, dev, moved=f"mcquic_amd.optim.{self._NAME}: parameter / gradient addresses changed since the last step")
+            # (rows 2 and 3, the state, are the plan's own and filled once; rows of a state the group does not have stay 0: no kernel reads them)
+            plan.table.fill(params, [p.grad for p in params], *([views[k] for views in plan.views] for k in range(len(names))))
             self._extend_plan(plan, dev)
         for p, views in zip(params, plan.views):
             st = self.state[p]
@@ -122,19 +95,6 @@ class _Planned(torch.optim.Optimizer):
 
     def _extend_plan(self, plan, dev) -> None:
         """What a subclass adds to a new plan."""
-
-    def _tables(self, plan, params):
-        key = tuple((p.data_ptr(), p.grad.data_ptr()) for p in params)
-        if plan.key == key:
-            return
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"mcquic_amd.optim.{self._NAME}: parameter / gradient addresses changed since the last step; call `prepare()` "
-                               "before capturing (a host-to-device copy of the pointer table cannot be part of a graph)")
-        ptrs = [p.data_ptr() for p in params] + [p.grad.data_ptr() for p in params]
-        for k in range(2):                                    # (rows of a state the group does not have stay 0: no kernel reads them)
-            ptrs += [views[k].data_ptr() if k < len(views) else 0 for views in plan.views]
-        plan.tables.copy_(torch.tensor(ptrs, dtype=torch.int64))          # (stream-ordered behind the launches that read the old one)
-        plan.key = key
 
     def _checked(self, group):
         params = [p for p in group["params"] if p.grad is not None]
@@ -170,7 +130,7 @@ class _Planned(torch.optim.Optimizer):
         out = []
         for gi, group, params in live:
             plan = self._flat_state(gi, params)
-            self._tables(plan, params)
+            plan.table.fill(params, [p.grad for p in params])
             out.append((group, plan))
         key = tuple((id(plan), plan.nblocks) for _, plan in out)
         if out and self._wants_norm() and (self._norm is None or self._norm[0] != key):
@@ -178,6 +138,35 @@ class _Planned(torch.optim.Optimizer):
             gnorm = self._norm[2] if self._norm is not None and self._norm[2].device == dev else torch.zeros((), dtype=torch.float32, device=dev)
             self._norm = (key, torch.zeros(max(sum(plan.nblocks for _, plan in out), 1), dtype=torch.float64, device=dev), gnorm)
         return out
+
+    def _grad_partials(self, todo):
+        """(partials, total, G) for an optimizer that `_wants_norm()`, (None, 0, None) otherwise: the per-chunk sums of g^2 of every plan of
+        `todo`, one launch each into one array of `total` doubles, from which every group's update derives the same norm G."""
+        if not self._wants_norm():
+            return None, 0, None
+        _, partials, gnorm = self._norm
+        total = 0
+        with _guard(gnorm.device):
+            for _, plan in todo:
+                check(_lib.load().mcq_lamb_grad_partials_f32(*plan.table.args(), partials.data_ptr() + 8 * total, _stream()),
+                      "mcq_lamb_grad_partials_f32")
+                total += plan.nblocks
+        return partials, total, gnorm
+
+    def _last_grad_norm(self):
+        """The device tensor that holds G of the last step, or None (no step yet, or an optimizer that computes none)."""
+        return self._norm[2] if self._wants_norm() and self._norm is not None else None
+
+    def _no_closure(self, closure) -> None:
+        if closure is not None:
+            raise NotImplementedError(f"mcquic_amd.optim.{self._NAME}: closures are not supported (the reference's trainer passes none)")
+
+    def load_state_dict(self, state_dict):
+        """The loaded tensors are copied INTO the existing flat buffers on the next step (same parameters: same addresses, which a
+        captured update may hold); only a plan whose parameter set changed is rebuilt."""
+        super().load_state_dict(state_dict)
+        for plan in self._plans.values():
+            plan.adopted = False
 
     @staticmethod
     def _check_adam_args(lr, betas, eps, weight_decay) -> None:
@@ -220,14 +209,13 @@ class Adam(_Planned):
 
     @torch.no_grad()
     def step(self, closure=None):
-        if closure is not None:
-            raise NotImplementedError("mcquic_amd.optim.Adam: closures are not supported (the reference's trainer passes none)")
+        self._no_closure(closure)
         lib = _lib.load()
         for group, plan in self._planned():
             lr_dev, lr_host = self._rate(group)
             b1, b2 = group["betas"]
             with _guard(plan.step.device):
-                check(lib.mcq_adam_step_f32(*plan.table_args(), plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(),
+                check(lib.mcq_adam_step_f32(*plan.table.args(), plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(),
                                             float(lr_host), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
                                             1 if group["decoupled"] else 0, 1 if group["maximize"] else 0, plan.scalars.data_ptr(), _stream()),
                       "mcq_adam_step_f32")
@@ -254,10 +242,6 @@ class Adam(_Planned):
             for k in ("amsgrad", "foreach", "fused", "differentiable"):
                 if group.get(k):
                     raise NotImplementedError(f"mcquic_amd.optim.Adam: `{k}` checkpoints are not supported")
-        # the loaded tensors are copied INTO the existing flat buffers on the next step (same parameters: same addresses, which a
-        # captured update may hold); only a plan whose parameter set changed is rebuilt
-        for plan in self._plans.values():
-            plan.adopted = False
 
 
 class AdamW(Adam):
@@ -287,7 +271,7 @@ class Lamb(_Planned):
     _NAME = "Lamb"
 
     class _Plan(_Planned._Plan):
-        __slots__ = ("tensor_first_blk", "workspace", "ratios")
+        __slots__ = ("workspace", "ratios")
 
     def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, amsgrad=False,
                  adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0, use_nvlamb=False):
@@ -308,7 +292,7 @@ class Lamb(_Planned):
         return True
 
     def _extend_plan(self, plan, dev) -> None:
-        plan.tensor_first_blk = torch.tensor(chunk_tables(plan.sizes)[2], dtype=torch.int32).to(dev)
+        plan.table.tensor_first_blk                           # (uploaded now: the first `step()` after `prepare()` may be a captured one)
         nbytes = _lib.load().mcq_lamb_workspace_bytes(plan.ntensors, max(plan.nblocks, 1))
         plan.workspace = torch.zeros((nbytes + 7) // 8, dtype=torch.float64, device=dev)
         plan.ratios = torch.zeros(plan.ntensors, dtype=torch.float32, device=dev)
@@ -330,26 +314,17 @@ class Lamb(_Planned):
 
     @torch.no_grad()
     def step(self, closure=None):
-        if closure is not None:
-            raise NotImplementedError("mcquic_amd.optim.Lamb: closures are not supported (the reference's trainer passes none)")
+        self._no_closure(closure)
         lib = _lib.load()
         todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
         if not todo:
             return None
-        _, partials, gnorm = self._norm
-        total = sum(plan.nblocks for _, plan in todo)
+        partials, total, gnorm = self._grad_partials(todo)    # the norm of ALL gradients first ...
         with _guard(gnorm.device):
-            at = 0
-            for _, plan in todo:                              # the norm of ALL gradients first ...
-                check(lib.mcq_lamb_grad_partials_f32(*plan.table_args(), partials.data_ptr() + 8 * at, _stream()),
-                      "mcq_lamb_grad_partials_f32")
-                at += plan.nblocks
             for group, plan in todo:                          # ... then every group's update reads the same partials
                 lr_dev, lr_host = self._rate(group)
                 b1, b2 = group["betas"]
-                # (this entry point takes tensor_first_blk in front of nblocks)
-                check(lib.mcq_lamb_step_f32(*plan.table_args()[:-1], plan.tensor_first_blk.data_ptr(), plan.nblocks, partials.data_ptr(), total,
-                                            plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(b1),
+                check(lib.mcq_lamb_step_f32(*plan.table.args(first_blk=True), partials.data_ptr(), total, plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(b1),
                                             float(b2), float(group["eps"]), float(group["weight_decay"]), 1 if group["bias_correction"] else 0,
                                             1 if group["adam_w_mode"] else 0, 1 if group["grad_averaging"] else 0,
                                             1 if group["use_nvlamb"] else 0, float(group["max_grad_norm"]), gnorm.data_ptr(),
@@ -375,8 +350,6 @@ class Lamb(_Planned):
             for k in ("bias_correction", "grad_averaging", "max_grad_norm", "adam_w_mode", "use_nvlamb"):
                 group.setdefault(k, self.defaults[k])         # (apex keeps adam_w_mode / use_nvlamb on the object, not in the groups)
             group["capturable"] = True
-        for plan in self._plans.values():
-            plan.adopted = False
 
 
 class SGD(_Planned):
@@ -452,25 +425,16 @@ class SGD(_Planned):
 
     @torch.no_grad()
     def step(self, closure=None):
-        if closure is not None:
-            raise NotImplementedError("mcquic_amd.optim.SGD: closures are not supported (the reference's trainer passes none)")
+        self._no_closure(closure)
         lib = _lib.load()
         todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
         if not todo:
             return None
-        partials = gnorm = None
-        total = 0
-        if self._wants_norm():                                # the norm of ALL gradients first, every group's chunks into one array
-            _, partials, gnorm = self._norm
-            with _guard(gnorm.device):
-                for _, plan in todo:
-                    check(lib.mcq_lamb_grad_partials_f32(*plan.table_args(), partials.data_ptr() + 8 * total, _stream()),
-                          "mcq_lamb_grad_partials_f32")
-                    total += plan.nblocks
+        partials, total, gnorm = self._grad_partials(todo)    # with clipping or the guard: the norm of ALL gradients first
         for i, (group, plan) in enumerate(todo):              # (every group derives the same factor and flag; the first one counts a skip)
             lr_dev, lr_host = self._rate(group)
             with _guard(plan.step.device):
-                check(lib.mcq_sgd_step_f32(*plan.table_args(), plan.step.data_ptr(),
+                check(lib.mcq_sgd_step_f32(*plan.table.args(), plan.step.data_ptr(),
                                            None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(group["momentum"]),
                                            float(group["dampening"]), float(group["weight_decay"]), 1 if group["nesterov"] else 0,
                                            1 if group["maximize"] else 0, None if partials is None else partials.data_ptr(), total,
@@ -505,8 +469,6 @@ class SGD(_Planned):
             count = 1.0 if any("momentum_buffer" in self.state[p] for p in held) else 0.0
             for p in group["params"]:
                 self.state[p]["step"] = torch.tensor(count, dtype=torch.float32)
-        for plan in self._plans.values():
-            plan.adopted = False
 
 
 class EMA:
@@ -554,12 +516,8 @@ class EMA:
         self.decay, self.warmup = decay, bool(warmup)
         self.names, self.params = [n for n, _ in named], [p for _, p in named]
         self.sizes = [p.numel() for p in self.params]
-        self._offs, at = [], 0
-        for n in self.sizes:
-            self._offs.append(at)
-            at += (n + 3) // 4 * 4                            # 16-byte aligned slices, as `_Planned._flat_state` lays out optimizer state
         dev = self.params[0].device
-        self._layout(torch.zeros(at, dtype=torch.float32, device=dev))
+        self._layout(torch.zeros(flat_layout(self.sizes)[1], dtype=torch.float32, device=dev))
         with torch.no_grad():
             for v, p in zip(self.averages, self.params):
                 v.copy_(p)
@@ -569,8 +527,8 @@ class EMA:
 
     def _layout(self, flat) -> None:
         self._flat = flat
-        self.averages = [flat[o: o + n].view(p.shape) for o, n, p in zip(self._offs, self.sizes, self.params)]
-        self._tables = self._key = None                       # (the tables hold the views' addresses)
+        self.averages = [flat[o: o + n].view(p.shape) for o, n, p in zip(flat_layout(self.sizes)[0], self.sizes, self.params)]
+        self._table = None                                    # (a TensorList on the buffer's device; row 1 holds the views' addresses)
 
     # ---- device tables ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -582,29 +540,13 @@ class EMA:
         for p in self.params:
             if not (p.is_cuda and p.is_contiguous() and p.device == dev):
                 raise RuntimeError("mcquic_amd.optim.EMA: contiguous float32 parameters on one HIP device only (there is no CPU path)")
-        key = tuple(p.data_ptr() for p in self.params)
-        if key == self._key:
-            return
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("mcquic_amd.optim.EMA: parameter addresses changed since the last call; call `prepare()` before capturing "
-                               "(a host-to-device copy of the pointer table cannot be part of a graph)")
         if self._flat.device != dev:                          # (the model moved since construction)
             self._count, self._scalars = self._count.to(dev), self._scalars.to(dev)
             self._layout(self._flat.to(dev))
-        if self._tables is None:
-            blk_t, blk_f, _ = chunk_tables(self.sizes)
-            self._numel = torch.tensor(self.sizes, dtype=torch.int64).to(dev)
-            self._blk_tensor = torch.tensor(blk_t, dtype=torch.int32).to(dev)
-            self._blk_first = torch.tensor(blk_f, dtype=torch.int64).to(dev)
-            self._nblocks = len(blk_t)
-            self._tables = torch.zeros(4 * len(self.params), dtype=torch.int64, device=dev)    # (rows 2 and 3 stay 0: no kernel reads them)
-        ptrs = list(key) + [v.data_ptr() for v in self.averages] + [0] * (2 * len(self.params))
-        self._tables.copy_(torch.tensor(ptrs, dtype=torch.int64))         # (stream-ordered behind the launches that read the old one)
-        self._key = key
-
-    def _table_args(self) -> tuple:
-        return (self._tables.data_ptr(), len(self.params), self._numel.data_ptr(), self._blk_tensor.data_ptr(), self._blk_first.data_ptr(),
-                self._nblocks)
+        if self._table is None:                               # (the kernels read rows 0 and 1 only; the averages' row is filled once)
+            self._table = TensorList(self.sizes, dev, rows=2, moved="mcquic_amd.optim.EMA: parameter addresses changed since the last call")
+            self._table.fill(self.params, self.averages)
+        self._table.fill(self.params)
 
     # ---- the average -----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -618,7 +560,7 @@ class EMA:
             raise TypeError("mcquic_amd.optim.EMA: a tensor decay must be one float32 on the device")
         dev = torch.is_tensor(decay)
         with _guard(self._flat.device):
-            check(_lib.load().mcq_ema_update_f32(*self._table_args(), self._count.data_ptr(), decay.data_ptr() if dev else None,
+            check(_lib.load().mcq_ema_update_f32(*self._table.args(), self._count.data_ptr(), decay.data_ptr() if dev else None,
                                                  0.0 if dev else float(decay), 1 if self.warmup else 0, self._scalars.data_ptr(), _stream()),
                   "mcq_ema_update_f32")
 
@@ -641,7 +583,7 @@ class EMA:
         """Exchange the live and the averaged weights in place (one launch) and mark every swapped parameter changed."""
         self.prepare()
         with _guard(self._flat.device):
-            check(_lib.load().mcq_ema_swap_f32(*self._table_args(), _stream()), "mcq_ema_swap_f32")
+            check(_lib.load().mcq_ema_swap_f32(*self._table.args(), _stream()), "mcq_ema_swap_f32")
         self.swapped = not self.swapped
         for p in self.params:
             torch.autograd.graph.increment_version(p)

@@ -428,34 +428,29 @@ class GraphedTrainStep:
         params = self.live_groups[k]
         lib = _lib.load()
         dev = self.flat.device
-        tb = self._gatherTables[k]
+        table, offs, host, ptrs = self._gatherTables[k]
         grads = [p.grad if p.grad.is_contiguous() else p.grad.contiguous() for p in params]
-        tb["grads"] = grads                                   # (alive as long as the tables point at them)
-        tb["host"].copy_(torch.tensor([g.data_ptr() for g in grads], dtype=torch.int64))
-        tb["ptrs"].copy_(tb["host"], non_blocking=True)       # (a copy NODE inside the capture: re-read from the pinned tensor on every replay)
+        self._gatherGrads[k] = grads                          # (alive as long as the tables point at them)
+        host.copy_(torch.tensor([g.data_ptr() for g in grads], dtype=torch.int64))
+        ptrs.copy_(host, non_blocking=True)                   # (a copy NODE inside the capture: re-read from the pinned tensor on every replay)
         with _guard(dev):
-            check(lib.mcq_gather_flat_f32(tb["ptrs"].data_ptr(), self.slices[k].data_ptr(), tb["offs"].data_ptr(), tb["numel"].data_ptr(),
-                                          tb["blk_t"].data_ptr(), tb["blk_f"].data_ptr(), tb["nblocks"], _stream()), "mcq_gather_flat_f32")
+            check(lib.mcq_gather_flat_f32(ptrs.data_ptr(), self.slices[k].data_ptr(), offs.data_ptr(), table.numel.data_ptr(),
+                                          table.blk_tensor.data_ptr(), table.blk_first.data_ptr(), table.nblocks, _stream()), "mcq_gather_flat_f32")
 
     def _gather_tables(self):
-        """The static side of `_gather` (sizes, offsets, chunk tables, the pinned pointer buffer), built OUTSIDE the captures: host-to-device
-        copies from pageable memory invalidate a capture."""
-        from .optim import chunk_tables
+        """The static side of `_gather`, built OUTSIDE the captures (host-to-device copies from pageable memory invalidate a capture): per
+        segment (chunk table, offsets into the slice, pinned host pointers, device pointers).  The pointer pair is the gather's own and not
+        a `TensorList`: its addresses are known only inside the capture and travel through a copy node."""
+        from .tensor_list import ChunkTable
         dev = self.flat.device
-        self._gatherTables = {}
+        self._gatherTables, self._gatherGrads = {}, {}
         for k, params in enumerate(self.live_groups):
             if not params:
                 continue
             sizes = [p.numel() for p in params]
-            offs, at = [], 0
-            for n in sizes:
-                offs.append(at)
-                at += n
-            blk_t, blk_f, _ = chunk_tables(sizes)
-            self._gatherTables[k] = dict(
-                host=torch.empty(len(params), dtype=torch.int64, pin_memory=True), ptrs=torch.empty(len(params), dtype=torch.int64, device=dev),
-                offs=torch.tensor(offs, dtype=torch.int64).to(dev), numel=torch.tensor(sizes, dtype=torch.int64).to(dev),
-                blk_t=torch.tensor(blk_t, dtype=torch.int32).to(dev), blk_f=torch.tensor(blk_f, dtype=torch.int64).to(dev), nblocks=len(blk_t))
+            offs = torch.tensor([0] + sizes[:-1], dtype=torch.int64).cumsum(0)     # (densely packed: a gradient's slice is only 4-byte aligned)
+            self._gatherTables[k] = (ChunkTable(sizes, dev), offs.to(dev),
+                                     torch.empty(len(params), dtype=torch.int64, pin_memory=True), torch.empty(len(params), dtype=torch.int64, device=dev))
         torch.cuda.synchronize()
 
     # ---- replica state ---------------------------------------------------------------------------------------------------
@@ -597,10 +592,8 @@ class GraphedTrainStep:
         """The telemetry row of this step (monitor.StepMeter.update): every value goes by device pointer, nothing is read here."""
         opt = self.optimizer
         norm = self.grad_norm
-        wants = getattr(opt, "_wants_norm", None)             # (mcquic_amd.optim: Lamb always; SGD with max_grad_norm or skip_nonfinite)
-        if norm is None and callable(wants) and wants():
-            norm = opt.grad_norm                              # (SGD: a method; Lamb: a property)
-            norm = norm() if callable(norm) else norm
+        if norm is None and hasattr(opt, "_last_grad_norm"):  # (mcquic_amd.optim: Lamb always; SGD with max_grad_norm or skip_nonfinite)
+            norm = opt._last_grad_norm()
         skipped = getattr(opt, "skipped", None)
         self.meter.update(self.loss, self.counts, grad_norm=norm, lr=opt.param_groups[0]["lr"],
                           skipped=skipped if torch.is_tensor(skipped) else None)
