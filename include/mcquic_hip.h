@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   16
+#define MCQ_ABI_VERSION   17
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -567,6 +567,53 @@ int mcq_step_meter_update_f32(const float* const* freq_ema /* [levels] device po
                               const float* lr_dev /* or NULL */, double lr, const int64_t* skipped /* or NULL */, double upper_bound,
                               double momentum, double floor, double pixels, int64_t* state /* device [4] */, int64_t* steps /* [capacity] */,
                               float* ring /* [capacity][columns] */, int64_t capacity, void* stream);
+
+/* Learning-rate schedules stepped on the device (csrc/schedule.hip, the rule itself: csrc/schedule_rule.h; host mirror
+ * mcquic_amd.schedule): the reference's four schedulers (mcquic/train/lrSchedulers.py), stepped after every batch
+ * (mcquic/train/trainer.py `_stepFinish`), as ONE launch of ONE workgroup with one lane per parameter group, so that a captured
+ * training step follows its schedule without the host.  At most MCQ_LR_MAX_GROUPS parameter groups, MCQ_EINVAL beyond.
+ * `state` holds MCQ_LR_STATE_WORDS doubles per group -- the float64 state is the truth, the float32 `lr` tensors the optimizers
+ * read are only its rounding:
+ *   0 rate  1 cycle  2 step_in_cycle  3 cur_cycle_steps  4 max_lr  5 min_lr  6 base_lr  7 min_base_lr
+ * (Cosine uses all; Cyclic 0, 1, 4, 6; MultiStep 0, 6; Placeholder 0, 6.  The cycle counters are doubles because the reference's
+ * resume path leaves a fractional cycle length behind, first_cycle_steps * cycle_mult^n.)  One step:
+ *   e = last_epoch[0] + 1 is stored; per group the state is advanced and `rate` recomputed in the reference's order of operations;
+ *   *lr[g] = float(rate).
+ *   Placeholder  rate = base_lr
+ *   MultiStep    e <= first_milestone: base_lr * (e + 1) / first_milestone (this overshoots at e == first_milestone, and the first
+ *                milestone never decays); afterwards rate * gamma where e is one of `milestones` (distinct values), else rate
+ *   Cyclic       cycle = floor(1 + e / total_size); x = 1 + e / total_size - cycle; s = x / step_ratio where x <= step_ratio, else
+ *                (x - 1) / (step_ratio - 1); rate = base_lr + (max_lr - base_lr) s f, f = 1 (triangular), 1 / 2^(cycle - 1)
+ *                (triangular2), gamma^e (exp_range)
+ *   Cosine       step_in_cycle += 1; once it reaches cur_cycle_steps: cycle += 1, step_in_cycle -= cur_cycle_steps, cur_cycle_steps =
+ *                trunc((cur_cycle_steps - warmup_steps) cycle_mult) + warmup_steps, max_lr = base_lr gamma^cycle, min_lr =
+ *                min_base_lr gamma^cycle.  rate = (max_lr - min_lr) step_in_cycle / warmup_steps + min_lr during the warm-up, else
+ *                min_lr + (max_lr - min_lr) (1 + cos(pi (step_in_cycle - warmup_steps) / (cur_cycle_steps - warmup_steps))) / 2
+ * No atomics, plain vector stores, nothing read by the host: equal state gives equal bits, and the launch is captured like the
+ * optimizers' updates.  mcq_lr_schedule_host runs the same rule on HOST memory (`milestones`, `last_epoch`, `state` are host
+ * pointers, `lr` an array of ngroups floats or NULL): with `advance` one step as above; without, `rate` (and lr) re-evaluated from
+ * the state as it stands and last_epoch left alone -- how a resumed Cosine schedule is set up (MultiStep is a recurrence on the
+ * rate and has nothing to re-evaluate: MCQ_EINVAL). */
+#define MCQ_LR_MAX_GROUPS   64
+#define MCQ_LR_STATE_WORDS  8
+#define MCQ_LR_PLACEHOLDER  0
+#define MCQ_LR_MULTISTEP    1
+#define MCQ_LR_CYCLIC       2
+#define MCQ_LR_COSINE       3
+#define MCQ_LR_TRIANGULAR   0   /* mcq_lr_schedule.mode (Cyclic) */
+#define MCQ_LR_TRIANGULAR2  1
+#define MCQ_LR_EXP_RANGE    2
+typedef struct mcq_lr_schedule {
+    int32_t kind, mode, ngroups, nmilestones;
+    const int64_t* milestones;     /* MultiStep: nmilestones distinct values (device memory for the launch); else NULL / 0 */
+    double gamma;                  /* MultiStep, Cyclic exp_range, Cosine */
+    double first_milestone;        /* MultiStep: min(milestones), >= 1 */
+    double total_size, step_ratio; /* Cyclic: step_size_up + step_size_down (> 0), step_size_up / total_size (in (0, 1]) */
+    double warmup_steps, cycle_mult; /* Cosine: >= 0 and an integer; > 0 */
+} mcq_lr_schedule;
+int mcq_lr_schedule_step(const mcq_lr_schedule* rule, int64_t* last_epoch, double* state /* [ngroups][8] */,
+                         float* const* lr /* device array of ngroups device pointers */, void* stream);
+int mcq_lr_schedule_host(const mcq_lr_schedule* rule, int32_t advance, int64_t* last_epoch, double* state, float* lr /* or NULL */);
 
 /* u8 = trunc(clamp(((x + 1) / 2) * 255.999, 0, 255))   (mcquic/utils/vision.py:143-146 DeTransform). */
 int mcq_detransform_u8(const float* x, uint8_t* out, int64_t n, void* stream);

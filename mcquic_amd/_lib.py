@@ -36,6 +36,18 @@ class ConvDesc(Structure):
                 ("tile", c_int32), ("post_w", c_void_p), ("post_bias", c_void_p)]
 
 
+LR_MAX_GROUPS, LR_STATE_WORDS = 64, 8
+LR_PLACEHOLDER, LR_MULTISTEP, LR_CYCLIC, LR_COSINE = 0, 1, 2, 3
+LR_TRIANGULAR, LR_TRIANGULAR2, LR_EXP_RANGE = 0, 1, 2
+
+
+class LrSchedule(Structure):
+    """struct mcq_lr_schedule (include/mcquic_hip.h)."""
+    _fields_ = [("kind", c_int32), ("mode", c_int32), ("ngroups", c_int32), ("nmilestones", c_int32), ("milestones", c_void_p),
+                ("gamma", c_double), ("first_milestone", c_double), ("total_size", c_double), ("step_ratio", c_double),
+                ("warmup_steps", c_double), ("cycle_mult", c_double)]
+
+
 # every symbol include/mcquic_hip.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "mcq_packed_conv_weight_floats": (c_size_t, [c_int32, c_int32, c_int32]),
@@ -146,6 +158,8 @@ SYMBOLS = {
     "mcq_ema_update_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_double, c_int32, c_void_p,
                                      c_void_p]),
     "mcq_ema_swap_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
+    "mcq_lr_schedule_step": (c_int32, [POINTER(LrSchedule), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mcq_lr_schedule_host": (c_int32, [POINTER(LrSchedule), c_int32, c_void_p, c_void_p, c_void_p]),
     "mcq_step_meter_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int32]),
     "mcq_step_meter_columns": (c_int32, [c_int32]),
     "mcq_step_meter_update_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
@@ -185,7 +199,7 @@ SYMBOLS = {
     "mcq_abi_version": (c_int32, []),
 }
 
-ABI_VERSION = 16     # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
+ABI_VERSION = 17    # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
 
 _lib = None
 

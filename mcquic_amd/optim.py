@@ -7,7 +7,7 @@ the qp=2 model's 666 tensors, 1.7 ms per step at 0.8 TB/s (docs/experiments.md s
 this object owns; the update is a one-thread kernel (step count, bias corrections, on the device) plus one pass over 28 bytes per
 element.  Arithmetic and state layout are torch.optim.Adam's / AdamW's: `state_dict()` / `load_state_dict()` exchange checkpoints with
 them (per-parameter `step`, `exp_avg`, `exp_avg_sq`), a learning rate given as a device tensor is read by the kernel on every
-call (a scheduler fills it; a captured step needs no re-capture), and nothing is read back by the host, so
+call (`mcquic_amd.schedule` fills it, on the device; a captured step needs no re-capture), and nothing is read back by the host, so
 `parallel.GraphedTrainStep` captures it like any capturable optimizer.  float32 parameters on a HIP device only: there is no CPU path.
 
 `Lamb` (alias `FusedLAMB`) is the reference's third optimizer (mcquic/train/ddp.py:53-69, apex FusedLAMB's arithmetic) on the same tables

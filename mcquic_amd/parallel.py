@@ -250,8 +250,8 @@ class GraphedTrainStep:
     Under more than one rank the constructor broadcasts rank 0's parameters and buffers (as DDP does), so the replicas start
     equal.  An optimizer that already holds state (resumed from a checkpoint) keeps it: its tensors are restored after the
     throw-away update that brings missing state into existence.
-    A captured update bakes in whatever the optimizer read on the host at capture time: give a scheduled learning rate to the
-    optimizer as a TENSOR (torch.optim reads it on the device then; Adam / AdamW additionally need `capturable=True`), or pass
+    A captured update bakes in whatever the optimizer read on the host at capture time: pass `scheduler=` (below), or give a scheduled
+    learning rate to the optimizer as a TENSOR (torch.optim reads it on the device then; Adam / AdamW additionally need `capturable=True`), or pass
     `capture_post=False` and the update (with the EMA) runs eagerly after the exchange -- ~15 launches, still no per-layer host work.
     `transform` (a `data.transforms.TrainingInput`, or any `utils.vision.Augment`): `example_x` and every later `x` are RAW batches
     (uint8 or float32 at source size); the transform's two launches are captured at the head of the first segment and write the
@@ -273,14 +273,23 @@ class GraphedTrainStep:
     on the device at every replay when it is a device tensor, as it is now when it is a host number) and the optimizer's `skipped`
     count where it has one.  The constructor leaves the meter's count, shadow and ring bit for bit as they were.  Without a meter
     not one launch changes.
+    `scheduler` (a `mcquic_amd.schedule` scheduler of this optimizer): `scheduler.step()` follows the optimizer, the EMA and the frequency
+    EMA and precedes the meter -- the reference steps its scheduler after every batch and logs `get_last_lr()` afterwards
+    (mcquic/train/trainer.py `_stepFinish`) --, inside the post graph when that is captured: one more launch of one workgroup that
+    advances the schedule's state on the device and stores the next rate into the tensors the optimizer's kernel reads, so replays
+    follow the schedule with no host work in between.  The constructor leaves the schedule's state and the rates bit for bit as they
+    were.  Without a scheduler not one launch changes.
     """
 
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
-                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None):
+                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None, scheduler=None):
         if not example_x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
         self.model, self.optimizer, self.group, self.ema, self.meter = model, optimizer, group, ema, meter
+        if scheduler is not None and getattr(scheduler, "optimizer", None) is not optimizer:
+            raise ValueError("GraphedTrainStep: `scheduler` steps another optimizer's learning rates than `optimizer`'s")
+        self.scheduler = scheduler
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.x = example_x.detach().clone()
         self.transform, self.raw = transform, None
@@ -407,6 +416,9 @@ class GraphedTrainStep:
         if self.meter is not None:                            # (the same for the meter: count, shadow and ring keep their bits)
             self.meter.prepare()
             self.meter.warm()
+        if self.scheduler is not None:                        # (the same for the schedule: last_epoch, state and rates keep their bits)
+            self.scheduler.prepare()
+            self.scheduler.warm()
         if capture_post:
             before = self._snapshot_optimizer_state()
             try:
@@ -585,6 +597,8 @@ class GraphedTrainStep:
             n = c.countSink().numel()
             c.applyCounts(self.counts[off: off + n])
             off += n
+        if self.scheduler is not None:                        # (the reference's order, trainer.py `_stepFinish`: step the scheduler, then log
+            self.scheduler.step()                             #  get_last_lr(): the meter's `lr` column is the rate of the NEXT update)
         if self.meter is not None:
             self._meter_update()
 

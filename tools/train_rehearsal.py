@@ -61,6 +61,11 @@ def main():
     ap.add_argument("--sgd", action="store_true", help="torch.optim.SGD(momentum=0.9, lr as a float) under the step's own clipping: what --own-sgd is measured against")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="mcquic_amd.optim.EMA(model, decay=DECAY, warmup=True) inside the step's post graph; "
                                                                                "every evaluation also reports the PSNR under `ema.applied()`")
+    ap.add_argument("--schedule", choices=["warmup", "cosine", "cosine-host"], default="warmup",
+                    help="warmup: the linear --warmup ramp filled in by the host before every replay (the default).  cosine: "
+                         "mcquic_amd.schedule.CosineAnnealingWarmupRestarts(first_cycle_steps=--steps, warmup_steps=--warmup, lrScaleRatio=0.0) -- the "
+                         "reference's configs/a800_8.yaml shape -- stepped on the device inside the post graph.  cosine-host: the same rates "
+                         "computed and filled in by the host before every replay: what `cosine` is measured against")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from mcquic_amd import Compressor, parallel
@@ -91,7 +96,25 @@ def main():
     if args.ema is not None:
         from mcquic_amd import optim
         ema = optim.EMA(model, decay=args.ema, warmup=True)
-    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if (args.lamb or args.own_sgd) else 4.0, ema=ema)
+    sched = None
+    if args.schedule != "warmup":
+        if args.sgd or not args.warmup < args.steps:
+            ap.error("--schedule cosine needs an optimizer that reads a tensor rate on the device (not --sgd) and --warmup < --steps")
+    if args.schedule == "cosine":
+        from mcquic_amd import schedule
+        sched = schedule.CosineAnnealingWarmupRestarts(opt, first_cycle_steps=args.steps, warmup_steps=args.warmup, lrScaleRatio=0.0)
+        lr = opt.param_groups[0]["lr"]                            # (the tensor the scheduler adopted: `lr` itself)
+
+    base_rate = float(lr)                                         # (the float32 tensor's value: what the scheduler takes as its base rate too)
+
+    def cosine_rate(e):
+        """The rate the update after `e` scheduler steps reads (one cycle, lrScaleRatio 0.0), in the reference's order of operations."""
+        import math
+        sic = e % args.steps
+        if sic < args.warmup:
+            return base_rate * sic / args.warmup
+        return base_rate * (1 + math.cos(math.pi * (sic - args.warmup) / (args.steps - args.warmup))) / 2
+    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if (args.lamb or args.own_sgd) else 4.0, ema=ema, scheduler=sched)
     trace = {"loss": [], "grad_norm": [], "psnr": [], "reassigned": [], "non_finite": 0}
     if ema is not None:
         trace["psnr_ema"] = []
@@ -109,8 +132,10 @@ def main():
     t_steps = 0.0
     for i in range(1, args.steps + 1):
         x = images(args.batch, args.crop, gen, dev)
-        if args.warmup:
-            lr.fill_(args.lr * min(1.0, i / args.warmup))         # (a scheduler's job; the captured update reads the tensor)
+        if args.schedule == "cosine-host":
+            lr.fill_(cosine_rate(i - 1))
+        elif args.schedule == "warmup" and args.warmup:
+            lr.fill_(args.lr * min(1.0, i / args.warmup))         # (a scheduler's job: --schedule cosine; the captured update reads the tensor)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         loss = step(x)
@@ -137,7 +162,8 @@ def main():
     last = sum(v for _, v in trace["loss"][-3:]) / 3
     out = {"what": "GraphedTrainStep(Adam, lr in a device tensor, max_grad_norm=4.0) on fresh synthetic batches; loss.item() every step; every "
                    f"{args.every} steps: finiteness of all parameters, eager encode/decode PSNR on 4 held-out images, codebook re-assignment every {2 * args.every}",
-           "model": f"Compressor({args.channel}, {args.m}, {ks})", "lr": args.lr, "lr_warmup_steps": args.warmup, "optimizer": "mcquic_amd.optim.Lamb(max_grad_norm=4.0), no clipping in the step" if args.lamb else "mcquic_amd.optim.Adam" if args.own_adam else "mcquic_amd.optim.SGD(momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True), no clipping in the step" if args.own_sgd else "torch SGD(momentum=0.9) foreach" if args.sgd else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "crop": args.crop, "steps": args.steps,
+           "model": f"Compressor({args.channel}, {args.m}, {ks})", "lr": args.lr, "lr_warmup_steps": args.warmup, "schedule": args.schedule,
+           **({"last_lr": sched.get_last_lr()[0], "last_epoch": sched.last_epoch} if sched is not None else {"last_lr": float(lr)} if torch.is_tensor(lr) else {}), "optimizer": "mcquic_amd.optim.Lamb(max_grad_norm=4.0), no clipping in the step" if args.lamb else "mcquic_amd.optim.Adam" if args.own_adam else "mcquic_amd.optim.SGD(momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True), no clipping in the step" if args.own_sgd else "torch SGD(momentum=0.9) foreach" if args.sgd else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "crop": args.crop, "steps": args.steps,
            "ms_per_step": round(t_steps / args.steps * 1e3, 3), "loss_first": round(first, 6), "loss_last": round(last, 6),
            "psnr_first": trace["psnr"][0][1], "psnr_last": trace["psnr"][-1][1], "memset_nodes_ok": parallel.memset_nodes_replay_correctly(dev), "memory": mem,
            **({"skipped": int(opt.skipped)} if args.own_sgd else {}),
