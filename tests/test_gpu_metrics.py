@@ -44,6 +44,19 @@ def test_ms_ssim_ragged_shapes(dev, shape):
     np.testing.assert_allclose(got.numpy(), M.ms_ssim(x, y).numpy(), rtol=0, atol=2e-6)
 
 
+@pytest.mark.parametrize("shape", [(1, 3, 161, 2071), (1, 3, 2071, 161)])
+def test_ms_ssim_strips_reach_every_level_seam(dev, shape):
+    """A second column (row) tile at every pyramid level: tiles are 16 x 118 map positions, so level l has a second column tile only
+    from W >= 257 / 513 / 1025 / 2049 on (levels 1..4) -- wider than any other case of this file."""
+    from mcquic_amd import ops
+    n, c, h, w = shape
+    x, y = M.make_u8_pair(h * 1000 + w, n, h, w)
+    got = ops.ms_ssim(x.to(dev), y.to(dev)).cpu()
+    np.testing.assert_allclose(got.numpy(), M.ms_ssim(x, y).numpy(), rtol=0, atol=2e-6)
+    want = ((x.to(torch.int64) - y.to(torch.int64)) ** 2).flatten(1).sum(1)
+    assert torch.equal(ops.sqdiff_sum(x.to(dev), y.to(dev)).cpu(), want)
+
+
 def test_ms_ssim_properties(dev):
     from mcquic_amd import ops
     x, y = M.make_u8_pair(11, 3, 200, 300)

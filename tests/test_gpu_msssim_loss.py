@@ -4,7 +4,8 @@ tests/test_msssim_loss_oracle.py.
 
 Bars: the forward within 4x the reference's own float32-vs-float64 difference (at least 1e-6, at most 5e-6 absolute); the
 gradients' relative L2 error within 2x the reference's own float32 error (or 1e-4, whichever is larger), the crop's max-abs
-error within 4x the reference's.  Determinism is bitwise, eager and replayed."""
+error within 4x the reference's.  Determinism is bitwise, eager and replayed.
+The elementwise checks (every tile seam, `saved`, guard bands) are in tests/test_gpu_msssim_leaf.py."""
 import copy
 import importlib.util
 import os

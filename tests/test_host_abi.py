@@ -76,6 +76,36 @@ def test_ms_ssim_host_side():
     assert lib.mcq_sqdiff_sum_u8(None, None, None, 10, 1, None) == _lib.MCQ_EINVAL
 
 
+def test_ms_ssim_loss_host_side():
+    """mcq_ms_ssim_loss_f32 / _bwd_f32 refuse before any launch: more than 65535 planes (grid.z) is MCQ_ETOOLARGE, a side of 160 or
+    a data range of 0 MCQ_EINVAL; the size functions return 0 for a side of 160 and otherwise what tests/_msssim_refs.py restates."""
+    import ctypes
+    import _msssim_refs as R
+    from mcquic_amd import _lib
+    lib = _lib.load()
+    p = ctypes.c_void_p(64)                         # never dereferenced: the checks come first
+
+    def fwd(n, c, h, w, data_range=2.0):
+        return lib.mcq_ms_ssim_loss_f32(p, p, 1.0, data_range, p, p, p, p, n, c, h, w, None)
+
+    def bwd(n, c, h, w, data_range=2.0):
+        return lib.mcq_ms_ssim_loss_bwd_f32(p, p, 1.0, data_range, p, p, p, p, p, p, n, c, h, w, None)
+
+    for call in (fwd, bwd):
+        assert call(65536, 1, 161, 161) == _lib.MCQ_ETOOLARGE
+        assert call(256, 256, 161, 161) == _lib.MCQ_ETOOLARGE
+        assert call(1, 3, 160, 512) == _lib.MCQ_EINVAL
+        assert call(1, 3, 512, 160) == _lib.MCQ_EINVAL
+        assert call(1, 3, 161, 161, data_range=0.0) == _lib.MCQ_EINVAL
+    for h, w in ((160, 512), (512, 160)):
+        assert lib.mcq_ms_ssim_loss_saved_bytes(1, 3, h, w) == 0
+        assert lib.mcq_ms_ssim_loss_workspace_bytes(1, 3, h, w, 0) == 0 and lib.mcq_ms_ssim_loss_workspace_bytes(1, 3, h, w, 1) == 0
+    for n, c, h, w in ((1, 1, 161, 2071), (1, 2, 171, 258), (65, 1, 161, 161), (86, 3, 161, 161), (8, 3, 256, 256)):
+        assert lib.mcq_ms_ssim_loss_saved_bytes(n, c, h, w) == 4 * R.saved_layout(n * c, h, w)[2]
+        for backward in (0, 1):
+            assert lib.mcq_ms_ssim_loss_workspace_bytes(n, c, h, w, backward) == R.workspace_bytes(n * c, h, w, backward)
+
+
 def test_invalid_arguments_return_einval():
     from mcquic_amd import _lib
     lib = _lib.load()
