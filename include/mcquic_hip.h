@@ -30,7 +30,7 @@ extern "C" {
  * compares it with mcq_abi_version() of the library it loaded before calling anything else: a stale .so under new
  * prototypes (or the reverse) misaligns arguments silently otherwise.  3 = round 3 (mcq_rans_*_with_indexes take cdf_lens,
  * mcq_gate_f32 takes out_silu -- both changed in round 2 without a bump --, GroupNorm / logits-gradient entry points). */
-#define MCQ_ABI_VERSION   17
+#define MCQ_ABI_VERSION   18
 
 #define MCQ_OK            0
 #define MCQ_EINVAL       -1   /* NULL pointer / non-positive dimension / unsupported combination */
@@ -539,6 +539,57 @@ int mcq_ema_update_f32(const void* ptr_tables, int32_t ntensors, const int64_t* 
 int mcq_ema_swap_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
                      int32_t nblocks, void* stream);
 
+/* The non-finite guard of a training step (csrc/step_guard.hip; host mirror mcquic_amd.guard.StepGuard): ONE flag per step, decided on
+ * the device from the global norm G of the gradient, and the `_skip` forms of every entry point of the update, which obey it.
+ * `record` = 24 bytes of device memory, 8-byte aligned, zero-initialised by the owner:
+ *     { int32 skip; float grad_norm; int64 skipped; int64 consecutive }
+ * A guard call stores skip = !isfinite(G) and grad_norm = float(G); a skipped step adds 1 to `skipped` and to `consecutive`, a clean one
+ * stores consecutive = 0.  G = sqrt(sum g^2) as csrc/sgd.hip forms it: one double partial per mcq_adam_chunk()-element chunk, every sum
+ * a fixed tree (no atomics: equal inputs give equal bits; a finite gradient of 1e19 per element is NOT an overflow of its squares).
+ *   mcq_step_guard_list_f32      the gradients of a tensor table (row 1; tables as for mcq_adam_step_f32): this table's nblocks partials into
+ *                                `partials`; then, unless `record` is NULL (a further parameter group follows), the n_all_partials
+ *                                doubles at `all_partials` are summed and the record written.  Two launches (one without record).
+ *   mcq_step_guard_flat_f32      the same over one flat buffer of n floats; `partials`: mcq_step_guard_chunks(n) doubles.
+ *   mcq_step_guard_partials_f32  the record from partials that exist already (LAMB's and SGD's own, mcq_lamb_grad_partials_f32): one
+ *                                launch of one workgroup, no second pass over the gradients.
+ *   mcq_step_guard_norm_f32      the record from a float32 norm (squared = 0) or sum of squares (squared != 0: sqrtf of it, as
+ *                                mcq_clip_by_norm_f32 takes mcq_sumsq_f32's) that exists already: one launch of one lane.  The flag is then
+ *                                the lender's arithmetic -- a float32 sum of squares that overflowed is skipped.
+ * The `_skip` entry points take `const int32_t* skip` (= record, or NULL) in front of `stream` and are otherwise the entry points of the
+ * same name: with NULL they ARE those (the same kernels, launch for launch); with a pointer every workgroup reads the word once,
+ * branches uniformly, and when it is non-zero the launch writes nothing -- no parameter, moment, step count, average, update count,
+ * schedule state, rate or frequency entry (mcq_clip_by_norm_skip_f32 still stores norm_out; mcq_sgd_step_skip_f32 stores the scratch
+ * word its second launch obeys and leaves SGD's own `skipped` alone).  Nothing is read by the host. */
+int64_t mcq_step_guard_chunks(int64_t n);
+int mcq_step_guard_list_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                            int32_t nblocks, double* partials, const double* all_partials /* or NULL without record */, int32_t n_all_partials,
+                            void* record /* or NULL */, void* stream);
+int mcq_step_guard_flat_f32(const float* grad, int64_t n, double* partials, void* record, void* stream);
+int mcq_step_guard_partials_f32(const double* partials, int32_t n_partials, void* record, void* stream);
+int mcq_step_guard_norm_f32(const float* value, int32_t squared, void* record, void* stream);
+int mcq_clip_by_norm_skip_f32(float* x, const float* sumsq, float max_norm, float eps, float* norm_out /* or NULL */, int64_t n,
+                              const int32_t* skip /* or NULL */, void* stream);
+int mcq_adam_step_skip_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                           int32_t nblocks, float* step, const float* lr_dev /* or NULL */, double lr, double beta1, double beta2, double eps,
+                           double weight_decay, int32_t decoupled, int32_t maximize, void* scalars, const int32_t* skip /* or NULL */, void* stream);
+int mcq_lamb_grad_partials_skip_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor,
+                                    const int64_t* blk_first, int32_t nblocks, double* partials, const int32_t* skip /* or NULL */, void* stream);
+int mcq_lamb_step_skip_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                           const int32_t* tensor_first_blk, int32_t nblocks, const double* grad_partials, int32_t n_grad_partials,
+                           float* step, const float* lr_dev /* or NULL */, double lr, double beta1, double beta2, double eps, double weight_decay,
+                           int32_t bias_correction, int32_t adam_w_mode, int32_t grad_averaging, int32_t use_nvlamb, double max_grad_norm,
+                           float* grad_norm, float* ratios, void* workspace, void* scalars, const int32_t* skip /* or NULL */, void* stream);
+int mcq_sgd_step_skip_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                          int32_t nblocks, float* step, const float* lr_dev /* or NULL */, double lr, double momentum, double dampening,
+                          double weight_decay, int32_t nesterov, int32_t maximize, const double* grad_partials /* or NULL */,
+                          int32_t n_grad_partials, const float* max_grad_norm /* or NULL */, float* grad_norm /* or NULL without grad_partials */,
+                          int32_t skip_nonfinite, int64_t* skipped /* or NULL */, void* scalars, const int32_t* skip /* or NULL */, void* stream);
+int mcq_ema_update_skip_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                            int32_t nblocks, int64_t* num_updates, const float* decay_dev /* or NULL */, double decay, int32_t warmup,
+                            void* scalars, const int32_t* skip /* or NULL */, void* stream);
+int mcq_freq_ema_update_skip_f32(float* const* freq_ema /* [levels] device pointers */, const int32_t* m, const int32_t* k, int32_t levels,
+                                 const int64_t* counts, double ema, const int32_t* skip /* or NULL */, void* stream);
+
 /* Per-step training telemetry kept on the device (csrc/step_meter.hip; host mirror mcquic_amd.monitor.StepMeter): what the
  * reference's trainer reports after an update (mcquic/train/trainer.py:423-441, 463-491) as one float32 row per step in a ring
  * buffer, written by two launches that read every per-step value through a device pointer.  Level tables as for
@@ -613,6 +664,9 @@ typedef struct mcq_lr_schedule {
 } mcq_lr_schedule;
 int mcq_lr_schedule_step(const mcq_lr_schedule* rule, int64_t* last_epoch, double* state /* [ngroups][8] */,
                          float* const* lr /* device array of ngroups device pointers */, void* stream);
+/* (`skip`: the step's guard flag, see mcq_step_guard_list_f32 -- NULL is mcq_lr_schedule_step; set, the schedule stays where it is) */
+int mcq_lr_schedule_step_skip(const mcq_lr_schedule* rule, int64_t* last_epoch, double* state, float* const* lr, const int32_t* skip /* or NULL */,
+                              void* stream);
 int mcq_lr_schedule_host(const mcq_lr_schedule* rule, int32_t advance, int64_t* last_epoch, double* state, float* lr /* or NULL */);
 
 /* u8 = trunc(clamp(((x + 1) / 2) * 255.999, 0, 255))   (mcquic/utils/vision.py:143-146 DeTransform). */

@@ -159,6 +159,25 @@ SYMBOLS = {
                                      c_void_p]),
     "mcq_ema_swap_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p]),
     "mcq_lr_schedule_step": (c_int32, [POINTER(LrSchedule), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mcq_lr_schedule_step_skip": (c_int32, [POINTER(LrSchedule), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mcq_step_guard_chunks": (c_int64, [c_int64]),
+    "mcq_step_guard_list_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p]),
+    "mcq_step_guard_flat_f32": (c_int32, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p]),
+    "mcq_step_guard_partials_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "mcq_step_guard_norm_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p]),
+    "mcq_clip_by_norm_skip_f32": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
+    "mcq_adam_step_skip_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_double, c_double, c_double,
+                                         c_double, c_double, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mcq_lamb_grad_partials_skip_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p]),
+    "mcq_lamb_step_skip_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p,
+                                         c_double, c_double, c_double, c_double, c_double, c_int32, c_int32, c_int32, c_int32, c_double, c_void_p,
+                                         c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mcq_sgd_step_skip_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_double, c_double, c_double,
+                                        c_double, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "mcq_ema_update_skip_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_double, c_int32, c_void_p,
+                                          c_void_p, c_void_p]),
+    "mcq_freq_ema_update_skip_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_double, c_void_p, c_void_p]),
     "mcq_lr_schedule_host": (c_int32, [POINTER(LrSchedule), c_int32, c_void_p, c_void_p, c_void_p]),
     "mcq_step_meter_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int32]),
     "mcq_step_meter_columns": (c_int32, [c_int32]),
@@ -199,7 +218,7 @@ SYMBOLS = {
     "mcq_abi_version": (c_int32, []),
 }
 
-ABI_VERSION = 17    # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
+ABI_VERSION = 18    # MCQ_ABI_VERSION of include/mcquic_hip.h these prototypes were written against
 
 _lib = None
 

@@ -20,8 +20,8 @@ namespace {
 struct EmaScalars { float w; float omw; float decay; int pad; };   // the weight of the live value, 1 - w (both float32), d_t (for inspection)
 static_assert(sizeof(EmaScalars) == 16, "`scalars` is 16 bytes");
 
-__global__ __launch_bounds__(64) void ema_prepare_kernel(long long* __restrict__ num_updates, const float* __restrict__ decay_dev, double decay_host,
-                                                         int warmup, EmaScalars* __restrict__ sc) {
+__device__ __forceinline__ void ema_prepare(long long* __restrict__ num_updates, const float* __restrict__ decay_dev, double decay_host,
+                                            int warmup, EmaScalars* __restrict__ sc) {
     if (threadIdx.x) return;
     const long long n = num_updates[0];
     double d = decay_dev ? (double)decay_dev[0] : decay_host;
@@ -37,12 +37,24 @@ __global__ __launch_bounds__(64) void ema_prepare_kernel(long long* __restrict__
     num_updates[0] = n + 1;
 }
 
+__global__ __launch_bounds__(64) void ema_prepare_kernel(long long* __restrict__ num_updates, const float* __restrict__ decay_dev, double decay_host,
+                                                         int warmup, EmaScalars* __restrict__ sc) {
+    ema_prepare(num_updates, decay_dev, decay_host, warmup, sc);
+}
+
+// the `_skip` twins (mcq_ema_update_skip_f32): with the step's guard flag set (step_guard.hip) neither the count nor an average moves
+__global__ __launch_bounds__(64) void ema_prepare_skip_kernel(long long* __restrict__ num_updates, const float* __restrict__ decay_dev, double decay_host,
+                                                              int warmup, EmaScalars* __restrict__ sc, const int* __restrict__ skip) {
+    if (skip[0]) return;
+    ema_prepare(num_updates, decay_dev, decay_host, warmup, sc);
+}
+
 __device__ __forceinline__ float ema_lerp(float a, float p, float w, float omw, bool low) {
     const float d = p - a;
     return low ? a + w * d : p - d * omw;
 }
 
-__global__ __launch_bounds__(256) void ema_update_kernel(McqTensorList list, const EmaScalars* __restrict__ scp) {
+__device__ __forceinline__ void ema_update(const McqTensorList& list, const EmaScalars* __restrict__ scp) {
     const float w = scp->w, omw = scp->omw;
     const bool low = fabsf(w) < 0.5f;
     const McqChunk c = list.chunk();
@@ -67,6 +79,13 @@ __global__ __launch_bounds__(256) void ema_update_kernel(McqTensorList list, con
         done = first + (nvec << 2);                          // the tensor's last 1..3 elements go through the dword loop below
     }
     for (long long i = done + threadIdx.x; i < end; i += 256) a[i] = ema_lerp(a[i], p[i], w, omw, low);
+}
+
+__global__ __launch_bounds__(256) void ema_update_kernel(McqTensorList list, const EmaScalars* __restrict__ scp) { ema_update(list, scp); }
+
+__global__ __launch_bounds__(256) void ema_update_skip_kernel(McqTensorList list, const EmaScalars* __restrict__ scp, const int* __restrict__ skip) {
+    if (skip[0]) return;
+    ema_update(list, scp);
 }
 
 __global__ __launch_bounds__(256) void ema_swap_kernel(McqTensorList list) {
@@ -96,16 +115,29 @@ __global__ __launch_bounds__(256) void ema_swap_kernel(McqTensorList list) {
 
 }  // namespace
 
-extern "C" int mcq_ema_update_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
-                                  int32_t nblocks, int64_t* num_updates, const float* decay_dev, double decay, int32_t warmup, void* scalars,
-                                  void* stream) {
+extern "C" int mcq_ema_update_skip_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor,
+                                       const int64_t* blk_first, int32_t nblocks, int64_t* num_updates, const float* decay_dev, double decay,
+                                       int32_t warmup, void* scalars, const int32_t* skip, void* stream) {
     McqTensorList list;
     if (!mcq_tensor_list(&list, ptr_tables, ntensors, numel, blk_tensor, blk_first, nblocks) || !num_updates || !scalars) return MCQ_EINVAL;
     if (!(decay >= 0.0 && decay <= 1.0)) return MCQ_EINVAL;  // (NaN too; with decay_dev the host value is not used: pass 0)
     hipStream_t s = (hipStream_t)stream;
+    if (skip) {
+        hipLaunchKernelGGL(ema_prepare_skip_kernel, dim3(1), dim3(64), 0, s, (long long*)num_updates, decay_dev, decay, warmup ? 1 : 0,
+                           (EmaScalars*)scalars, (const int*)skip);
+        hipLaunchKernelGGL(ema_update_skip_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, list, (const EmaScalars*)scalars, (const int*)skip);
+        return mcq_check_launch();
+    }
     hipLaunchKernelGGL(ema_prepare_kernel, dim3(1), dim3(64), 0, s, (long long*)num_updates, decay_dev, decay, warmup ? 1 : 0, (EmaScalars*)scalars);
     hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)nblocks), dim3(256), 0, s, list, (const EmaScalars*)scalars);
     return mcq_check_launch();
+}
+
+extern "C" int mcq_ema_update_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                                  int32_t nblocks, int64_t* num_updates, const float* decay_dev, double decay, int32_t warmup, void* scalars,
+                                  void* stream) {
+    return mcq_ema_update_skip_f32(ptr_tables, ntensors, numel, blk_tensor, blk_first, nblocks, num_updates, decay_dev, decay, warmup, scalars,
+                                   nullptr, stream);
 }
 
 extern "C" int mcq_ema_swap_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,

@@ -12,8 +12,8 @@
 
 namespace {
 
-__global__ __launch_bounds__(MCQ_LR_MAX_GROUPS) void lr_schedule_kernel(mcq_lr_schedule r, long long* __restrict__ last_epoch,
-                                                                        double* __restrict__ state, float* const* __restrict__ lr) {
+__device__ __forceinline__ void lr_schedule(const mcq_lr_schedule& r, long long* __restrict__ last_epoch, double* __restrict__ state,
+                                            float* const* __restrict__ lr) {
     const int g = threadIdx.x;
     const long long e = last_epoch[0] + 1;
     __syncthreads();
@@ -29,12 +29,35 @@ __global__ __launch_bounds__(MCQ_LR_MAX_GROUPS) void lr_schedule_kernel(mcq_lr_s
     *lr[g] = (float)s[MCQ_LR_RATE];
 }
 
+__global__ __launch_bounds__(MCQ_LR_MAX_GROUPS) void lr_schedule_kernel(mcq_lr_schedule r, long long* __restrict__ last_epoch,
+                                                                        double* __restrict__ state, float* const* __restrict__ lr) {
+    lr_schedule(r, last_epoch, state, lr);
+}
+
+// mcq_lr_schedule_step_skip: with the step's guard flag set (step_guard.hip) the schedule stays where it is -- last_epoch, state and rates
+__global__ __launch_bounds__(MCQ_LR_MAX_GROUPS) void lr_schedule_skip_kernel(mcq_lr_schedule r, long long* __restrict__ last_epoch,
+                                                                             double* __restrict__ state, float* const* __restrict__ lr,
+                                                                             const int* __restrict__ skip) {
+    if (skip[0]) return;
+    lr_schedule(r, last_epoch, state, lr);
+}
+
 }  // namespace
 
-extern "C" int mcq_lr_schedule_step(const mcq_lr_schedule* rule, int64_t* last_epoch, double* state, float* const* lr, void* stream) {
+extern "C" int mcq_lr_schedule_step_skip(const mcq_lr_schedule* rule, int64_t* last_epoch, double* state, float* const* lr, const int32_t* skip,
+                                         void* stream) {
     if (!rule || !last_epoch || !state || !lr || !mcq_lr_rule_ok(*rule)) return MCQ_EINVAL;
+    if (skip) {
+        hipLaunchKernelGGL(lr_schedule_skip_kernel, dim3(1), dim3(MCQ_LR_MAX_GROUPS), 0, (hipStream_t)stream, *rule, (long long*)last_epoch, state, lr,
+                           (const int*)skip);
+        return mcq_check_launch();
+    }
     hipLaunchKernelGGL(lr_schedule_kernel, dim3(1), dim3(MCQ_LR_MAX_GROUPS), 0, (hipStream_t)stream, *rule, (long long*)last_epoch, state, lr);
     return mcq_check_launch();
+}
+
+extern "C" int mcq_lr_schedule_step(const mcq_lr_schedule* rule, int64_t* last_epoch, double* state, float* const* lr, void* stream) {
+    return mcq_lr_schedule_step_skip(rule, last_epoch, state, lr, nullptr, stream);
 }
 
 extern "C" int mcq_lr_schedule_host(const mcq_lr_schedule* rule, int32_t advance, int64_t* last_epoch, double* state, float* lr) {

@@ -20,11 +20,10 @@ struct SgdScalars { float lr; float clip; int first; int skip; };
 static_assert(sizeof(SgdScalars) == 16, "`scalars` is 16 bytes");
 struct SgdCoef { float momentum; float omd; float weight_decay; int nesterov; int maximize; };
 
-__global__ __launch_bounds__(256) void sgd_prepare_kernel(const double* __restrict__ part, int nparts, float* __restrict__ step,
-                                                          const float* __restrict__ lr_dev, double lr_host,
-                                                          const float* __restrict__ max_grad_norm, float* __restrict__ grad_norm,
-                                                          int skip_nonfinite, long long* __restrict__ skipped, SgdScalars* __restrict__ sc) {
-    __shared__ double red[256];
+__device__ __forceinline__ void sgd_prepare(const double* __restrict__ part, int nparts, float* __restrict__ step,
+                                            const float* __restrict__ lr_dev, double lr_host,
+                                            const float* __restrict__ max_grad_norm, float* __restrict__ grad_norm,
+                                            int skip_nonfinite, long long* __restrict__ skipped, SgdScalars* __restrict__ sc, double* red) {
     double s = 0.0;
     if (part) {                                              // (the same for every lane: launched with 256 lanes then, with 64 otherwise)
         for (int i = threadIdx.x; i < nparts; i += 256) s += part[i];
@@ -52,6 +51,29 @@ __global__ __launch_bounds__(256) void sgd_prepare_kernel(const double* __restri
     sc->clip = clip;
     sc->first = t == 0.0f ? 1 : 0;
     sc->skip = skip;
+}
+
+__global__ __launch_bounds__(256) void sgd_prepare_kernel(const double* __restrict__ part, int nparts, float* __restrict__ step,
+                                                          const float* __restrict__ lr_dev, double lr_host,
+                                                          const float* __restrict__ max_grad_norm, float* __restrict__ grad_norm,
+                                                          int skip_nonfinite, long long* __restrict__ skipped, SgdScalars* __restrict__ sc) {
+    __shared__ double red[256];
+    sgd_prepare(part, nparts, step, lr_dev, lr_host, max_grad_norm, grad_norm, skip_nonfinite, skipped, sc, red);
+}
+
+// mcq_sgd_step_skip_f32: the step's guard flag (step_guard.hip) in front of SGD's own.  When it is set this kernel writes the scratch
+// word (b) obeys and nothing else -- no step count, no norm, and not `skipped`: the step's guard has counted the step already.
+__global__ __launch_bounds__(256) void sgd_prepare_skip_kernel(const double* __restrict__ part, int nparts, float* __restrict__ step,
+                                                               const float* __restrict__ lr_dev, double lr_host,
+                                                               const float* __restrict__ max_grad_norm, float* __restrict__ grad_norm,
+                                                               int skip_nonfinite, long long* __restrict__ skipped, SgdScalars* __restrict__ sc,
+                                                               const int* __restrict__ ext_skip) {
+    __shared__ double red[256];
+    if (ext_skip[0]) {
+        if (threadIdx.x == 0) sc->skip = 1;
+        return;
+    }
+    sgd_prepare(part, nparts, step, lr_dev, lr_host, max_grad_norm, grad_norm, skip_nonfinite, skipped, sc, red);
 }
 
 template <bool MOMENTUM>
@@ -105,11 +127,11 @@ __global__ __launch_bounds__(256) void sgd_update_kernel(McqTensorList list, con
 
 }  // namespace
 
-extern "C" int mcq_sgd_step_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
-                                int32_t nblocks, float* step, const float* lr_dev, double lr, double momentum, double dampening,
-                                double weight_decay, int32_t nesterov, int32_t maximize, const double* grad_partials, int32_t n_grad_partials,
-                                const float* max_grad_norm, float* grad_norm, int32_t skip_nonfinite, int64_t* skipped, void* scalars,
-                                void* stream) {
+extern "C" int mcq_sgd_step_skip_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor,
+                                     const int64_t* blk_first, int32_t nblocks, float* step, const float* lr_dev, double lr, double momentum,
+                                     double dampening, double weight_decay, int32_t nesterov, int32_t maximize, const double* grad_partials,
+                                     int32_t n_grad_partials, const float* max_grad_norm, float* grad_norm, int32_t skip_nonfinite, int64_t* skipped,
+                                     void* scalars, const int32_t* skip, void* stream) {
     McqTensorList list;
     if (!mcq_tensor_list(&list, ptr_tables, ntensors, numel, blk_tensor, blk_first, nblocks) || !step || !scalars) return MCQ_EINVAL;
     if (!(momentum >= 0.0) || !(weight_decay >= 0.0) || !(dampening == dampening)) return MCQ_EINVAL;
@@ -117,11 +139,25 @@ extern "C" int mcq_sgd_step_f32(const void* ptr_tables, int32_t ntensors, const 
     if (!lr_dev && !(lr >= 0.0)) return MCQ_EINVAL;
     if (grad_partials ? (n_grad_partials <= 0 || !grad_norm) : (max_grad_norm || skip_nonfinite || skipped)) return MCQ_EINVAL;   // clip and guard need the partials
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(sgd_prepare_kernel, dim3(1), dim3(grad_partials ? 256 : 64), 0, s, grad_partials, (int)n_grad_partials, step, lr_dev, lr,
-                       max_grad_norm, grad_norm, skip_nonfinite ? 1 : 0, (long long*)skipped, (SgdScalars*)scalars);
+    if (skip)
+        hipLaunchKernelGGL(sgd_prepare_skip_kernel, dim3(1), dim3(grad_partials ? 256 : 64), 0, s, grad_partials, (int)n_grad_partials, step, lr_dev, lr,
+                           max_grad_norm, grad_norm, skip_nonfinite ? 1 : 0, (long long*)skipped, (SgdScalars*)scalars, (const int*)skip);
+    else
+        hipLaunchKernelGGL(sgd_prepare_kernel, dim3(1), dim3(grad_partials ? 256 : 64), 0, s, grad_partials, (int)n_grad_partials, step, lr_dev, lr,
+                           max_grad_norm, grad_norm, skip_nonfinite ? 1 : 0, (long long*)skipped, (SgdScalars*)scalars);
     // (1 - dampening rounded from double, as torch passes `alpha = 1 - dampening` to _foreach_add_)
     const SgdCoef k = {(float)momentum, (float)(1.0 - dampening), (float)weight_decay, nesterov ? 1 : 0, maximize ? 1 : 0};
     hipLaunchKernelGGL(momentum != 0.0 ? sgd_update_kernel<true> : sgd_update_kernel<false>, dim3((unsigned)nblocks), dim3(256), 0, s, list,
                        (const SgdScalars*)scalars, k);
     return mcq_check_launch();
+}
+
+extern "C" int mcq_sgd_step_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                                int32_t nblocks, float* step, const float* lr_dev, double lr, double momentum, double dampening,
+                                double weight_decay, int32_t nesterov, int32_t maximize, const double* grad_partials, int32_t n_grad_partials,
+                                const float* max_grad_norm, float* grad_norm, int32_t skip_nonfinite, int64_t* skipped, void* scalars,
+                                void* stream) {
+    return mcq_sgd_step_skip_f32(ptr_tables, ntensors, numel, blk_tensor, blk_first, nblocks, step, lr_dev, lr, momentum, dampening, weight_decay,
+                                 nesterov, maximize, grad_partials, n_grad_partials, max_grad_norm, grad_norm, skip_nonfinite, skipped, scalars,
+                                 nullptr, stream);
 }

@@ -132,8 +132,7 @@ struct FreqEmaK {
 };
 
 // one workgroup per (level, group) row: total, then freq = (1 - ema) * count / total + ema * freq, rounded op by op like torch
-__global__ __launch_bounds__(STEP_T) void freq_ema_update_kernel(FreqEmaK q) {
-    __shared__ long long sml[STEP_T / 64];
+__device__ __forceinline__ void freq_ema_update_row(const FreqEmaK& q, long long* sml) {
     int lv = 0;
     while (lv + 1 < q.levels && (int)blockIdx.x >= q.row0[lv + 1]) ++lv;
     const int g = (int)blockIdx.x - q.row0[lv];
@@ -176,6 +175,18 @@ __global__ __launch_bounds__(STEP_T) void freq_ema_update_kernel(FreqEmaK q) {
             if (i < k) f[i] = a + b;
         }
     }
+}
+
+__global__ __launch_bounds__(STEP_T) void freq_ema_update_kernel(FreqEmaK q) {
+    __shared__ long long sml[STEP_T / 64];
+    freq_ema_update_row(q, sml);
+}
+
+// mcq_freq_ema_update_skip_f32: with the step's guard flag set (step_guard.hip) no `_freqEMA` entry moves
+__global__ __launch_bounds__(STEP_T) void freq_ema_update_skip_kernel(FreqEmaK q, const int* __restrict__ skip) {
+    __shared__ long long sml[STEP_T / 64];
+    if (skip[0]) return;
+    freq_ema_update_row(q, sml);
 }
 
 struct Reparam2K {
@@ -233,8 +244,8 @@ extern "C" int mcq_vq_temperature_grad_f32(const float* dtrow, const float* temp
     return mcq_check_launch();
 }
 
-extern "C" int mcq_freq_ema_update_f32(float* const* freq_ema, const int32_t* m, const int32_t* k, int32_t levels, const int64_t* counts,
-                                       double ema, void* stream) {
+extern "C" int mcq_freq_ema_update_skip_f32(float* const* freq_ema, const int32_t* m, const int32_t* k, int32_t levels, const int64_t* counts,
+                                            double ema, const int32_t* skip, void* stream) {
     if (!freq_ema || !m || !k || !counts || levels <= 0 || levels > MCQ_VQ_MAX_LEVELS) return MCQ_EINVAL;
     FreqEmaK q;
     long long off = 0;
@@ -250,8 +261,14 @@ extern "C" int mcq_freq_ema_update_f32(float* const* freq_ema, const int32_t* m,
     // (1 - ema) and ema reach torch's kernels as Python floats cast to float32 (entropyCoder.py:42)
     q.keep = (float)ema; q.fresh = (float)(1.0 - ema);
     q.counts = reinterpret_cast<const long long*>(counts);
-    hipLaunchKernelGGL(freq_ema_update_kernel, dim3((unsigned)rows), dim3(STEP_T), 0, (hipStream_t)stream, q);
+    if (skip) hipLaunchKernelGGL(freq_ema_update_skip_kernel, dim3((unsigned)rows), dim3(STEP_T), 0, (hipStream_t)stream, q, (const int*)skip);
+    else hipLaunchKernelGGL(freq_ema_update_kernel, dim3((unsigned)rows), dim3(STEP_T), 0, (hipStream_t)stream, q);
     return mcq_check_launch();
+}
+
+extern "C" int mcq_freq_ema_update_f32(float* const* freq_ema, const int32_t* m, const int32_t* k, int32_t levels, const int64_t* counts,
+                                       double ema, void* stream) {
+    return mcq_freq_ema_update_skip_f32(freq_ema, m, k, levels, counts, ema, nullptr, stream);
 }
 
 extern "C" int mcq_nonneg_reparam_bwd2_f32(const float* p0, const float* dfolded0, float bound0, float* dp0, int64_t n0, const float* p1,

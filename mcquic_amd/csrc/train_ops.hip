@@ -409,6 +409,16 @@ __global__ __launch_bounds__(256) void clip_by_norm_kernel(float* __restrict__ x
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] *= coef;
 }
 
+// mcq_clip_by_norm_skip_f32: the same, but with the step's guard flag set (step_guard.hip) the factor is never applied
+__global__ __launch_bounds__(256) void clip_by_norm_skip_kernel(float* __restrict__ x, const float* __restrict__ sumsq, float max_norm, float eps,
+                                                                float* __restrict__ norm_out, int64_t n, const int* __restrict__ skip) {
+    const float norm = sqrtf(sumsq[0]);
+    const float coef = max_norm / (norm + eps);
+    if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) norm_out[0] = norm;
+    if (skip[0] || !(coef < 1.0f)) return;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) x[i] *= coef;
+}
+
 __global__ __launch_bounds__(256) void mse_bwd_kernel(const float* __restrict__ a, const float* __restrict__ b, const float* __restrict__ dloss,
                                                       float scale, float* __restrict__ da, float* __restrict__ db, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -641,12 +651,22 @@ extern "C" int mcq_sumsq_f32(const float* x, float* out, void* workspace, int64_
     return mcq_check_launch();
 }
 
-extern "C" int mcq_clip_by_norm_f32(float* x, const float* sumsq, float max_norm, float eps, float* norm_out, int64_t n, void* stream) {
+extern "C" int mcq_clip_by_norm_skip_f32(float* x, const float* sumsq, float max_norm, float eps, float* norm_out, int64_t n, const int32_t* skip,
+                                         void* stream) {
     if (!x || !sumsq || n <= 0 || !(max_norm > 0.0f) || !(eps >= 0.0f)) return MCQ_EINVAL;
     const int64_t want = (n + 1023) / 1024;
+    if (skip) {
+        hipLaunchKernelGGL(clip_by_norm_skip_kernel, dim3((unsigned)(want < 1 ? 1 : want > 4096 ? 4096 : want)), dim3(256), 0, (hipStream_t)stream, x,
+                           sumsq, max_norm, eps, norm_out, n, (const int*)skip);
+        return mcq_check_launch();
+    }
     hipLaunchKernelGGL(clip_by_norm_kernel, dim3((unsigned)(want < 1 ? 1 : want > 4096 ? 4096 : want)), dim3(256), 0, (hipStream_t)stream, x, sumsq,
                        max_norm, eps, norm_out, n);
     return mcq_check_launch();
+}
+
+extern "C" int mcq_clip_by_norm_f32(float* x, const float* sumsq, float max_norm, float eps, float* norm_out, int64_t n, void* stream) {
+    return mcq_clip_by_norm_skip_f32(x, sumsq, max_norm, eps, norm_out, n, nullptr, stream);
 }
 
 extern "C" int mcq_mse_bwd_f32(const float* a, const float* b, const float* dloss, float* da, float* db, int64_t n, void* stream) {

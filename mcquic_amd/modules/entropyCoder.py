@@ -196,11 +196,14 @@ class EntropyCoder(nn.Module):
             buf = self.__dict__["_countBuf"] = torch.empty(n, dtype=torch.int64, device=device)
         return buf
 
-    def _emaUpdate(self, counts):
-        """`counts`: the global histograms, flat (level after level) or as a list of [m_l, k_l] tensors."""
+    def _emaUpdate(self, counts, skip=None):
+        """`counts`: the global histograms, flat (level after level) or as a list of [m_l, k_l] tensors.  `skip`: a step's guard flag
+        (`ops.freq_ema_update_`; device counts only)."""
         if torch.is_tensor(counts) and counts.is_cuda:
             from .. import ops
-            ops.freq_ema_update_([f for f in self._freqEMA], counts, self._ema)      # all levels in one launch, in place
+            ops.freq_ema_update_([f for f in self._freqEMA], counts, self._ema, skip=skip)      # all levels in one launch, in place
+        elif skip is not None:
+            raise RuntimeError("mcquic_amd: the non-finite guard's flag is read by HIP kernels; there is no CPU path")
         else:
             if torch.is_tensor(counts):
                 from ..parallel import split_code_counts
@@ -226,8 +229,8 @@ class EntropyCoder(nn.Module):
         return buf
 
     @torch.no_grad()
-    def applyCounts(self, flat: torch.Tensor):
-        self._emaUpdate(flat)
+    def applyCounts(self, flat: torch.Tensor, skip=None):
+        self._emaUpdate(flat, skip)
 
     # ---- frequency / CDF tables (entropyCoder.py:46-79) ------------------------------------------------------
     def resetFreqAndCDF(self):

@@ -871,9 +871,10 @@ def vq_temperature_grad(dtrow: torch.Tensor, temperature: torch.Tensor, bound: f
     return out
 
 
-def freq_ema_update_(freqs: Sequence[torch.Tensor], counts: torch.Tensor, ema: float) -> None:
+def freq_ema_update_(freqs: Sequence[torch.Tensor], counts: torch.Tensor, ema: float, skip=None) -> None:
     """In place on every level's frequency EMA [m_l, k_l]: (1 - ema) * counts_l / sum_k counts_l + ema * freq_l
-    (mcquic/modules/entropyCoder.py:37-43) for all levels in ONE launch; `counts` = the levels' histograms back to back (int64)."""
+    (mcquic/modules/entropyCoder.py:37-43) for all levels in ONE launch; `counts` = the levels' histograms back to back (int64).
+    `skip`: a step's guard flag (one int32 on the device, `guard.StepGuard.skip`): set on the device, no entry moves."""
     fs = [_dev(f.detach(), "freq_ema") for f in freqs]
     for f, g in zip(fs, freqs):
         if f.data_ptr() != g.data_ptr():
@@ -886,6 +887,8 @@ def freq_ema_update_(freqs: Sequence[torch.Tensor], counts: torch.Tensor, ema: f
     ks = (ctypes.c_int32 * levels)(*[int(f.shape[1]) for f in fs])
     lib = _lib.load()
     cap = int(lib.mcq_vq_max_levels())
+    from .guard import skip_pointer
+    flag = skip_pointer(skip, counts.device, "freq_ema_update_")
     with _guard(counts.device):
         off = 0
         for l0 in range(0, levels, cap):                     # (a launch's tables hold `cap` levels; see vq_step_prologue)
@@ -894,8 +897,8 @@ def freq_ema_update_(freqs: Sequence[torch.Tensor], counts: torch.Tensor, ema: f
             ms_c = (ctypes.c_int32 * nl)(*ms[l0: l0 + nl])
             ks_c = (ctypes.c_int32 * nl)(*ks[l0: l0 + nl])
             size = sum(int(f.numel()) for f in fs[l0: l0 + nl])
-            check(lib.mcq_freq_ema_update_f32(ptrs, ms_c, ks_c, nl, _ptr(counts[off: off + size]), float(ema), _stream()),
-                  "mcq_freq_ema_update_f32")
+            check(lib.mcq_freq_ema_update_skip_f32(ptrs, ms_c, ks_c, nl, _ptr(counts[off: off + size]), float(ema), flag, _stream()),
+                  "mcq_freq_ema_update_skip_f32")
             off += size
 
 
@@ -1134,17 +1137,21 @@ def codebook_cosine_bwd(codebook: torch.Tensor, dout: torch.Tensor, gamma: float
     return out
 
 
-def clip_by_norm_(x: torch.Tensor, max_norm: float, eps: float = 1e-6) -> torch.Tensor:
+def clip_by_norm_(x: torch.Tensor, max_norm: float, eps: float = 1e-6, sq: Optional[torch.Tensor] = None, skip=None) -> torch.Tensor:
     """In place: x *= max_norm / (||x|| + eps) where that is < 1 (torch.nn.utils.clip_grad_norm_ over one flat buffer; the reference's
-    trainer.py:280).  Returns ||x|| BEFORE clipping as a 0-dim device tensor; no host read, so it can be captured."""
+    trainer.py:280).  Returns ||x|| BEFORE clipping as a 0-dim device tensor; no host read, so it can be captured.
+    `sq`: `sumsq(x)` where the caller has formed it already (a step's guard decides from it in between); `skip`: that guard's flag
+    (one int32 on the device, `guard.StepGuard.skip`): set on the device, the factor is not applied (the norm is still returned)."""
     x = _dev(x, "x")
     if not x.is_contiguous():
         raise ValueError("clip_by_norm_: needs a contiguous buffer (it is scaled in place)")
-    sq = sumsq(x)
+    sq = sumsq(x) if sq is None else _dev(sq, "sq")
     norm = torch.empty((), dtype=torch.float32, device=x.device)
+    from .guard import skip_pointer
+    flag = skip_pointer(skip, x.device, "clip_by_norm_")
     with _guard(x.device):
-        check(_lib.load().mcq_clip_by_norm_f32(_ptr(x), _ptr(sq), float(max_norm), float(eps), _ptr(norm), x.numel(), _stream()),
-              "mcq_clip_by_norm_f32")
+        check(_lib.load().mcq_clip_by_norm_skip_f32(_ptr(x), _ptr(sq), float(max_norm), float(eps), _ptr(norm), x.numel(), flag, _stream()),
+              "mcq_clip_by_norm_skip_f32")
     return norm
 
 

@@ -20,7 +20,14 @@ torch.optim.SGD, as the reference's registry has it: opt in by building `mcquic_
 
 `EMA` is not an optimizer: the exponential moving average of the weights on the same tables (row 1: the averages, one flat buffer),
 csrc/ema.hip, the scalar kernel plus one pass, and a second kernel that exchanges live and averaged weights in place to evaluate the
-average.  The reference has no such entry, so `REGISTRY` has none."""
+average.  The reference has no such entry, so `REGISTRY` has none.
+
+The non-finite guard (`mcquic_amd.guard`, csrc/step_guard.hip).  `Adam / AdamW / Lamb(..., skip_nonfinite=True)`: `step()` first forms the
+global norm of its own gradients on the device (Adam: one pass over its gradient table; Lamb: the partials it computes anyway), and a
+call whose norm is inf or NaN changes no parameter, no moment and no step count and is counted in `skipped` (a 0-dim int64 device
+tensor), as `SGD(skip_nonfinite=True)` has always done inside its own kernel.  A clean call produces the bits it produces without the
+option.  `attach_guard()` is how `parallel.GraphedTrainStep(..., skip_nonfinite=True)` drives all four with the step's ONE flag instead;
+`EMA.update(skip=...)` takes the same flag."""
 from __future__ import annotations
 
 import torch
@@ -46,6 +53,9 @@ class _Planned(torch.optim.Optimizer):
         super().__init__(params, defaults)
         self._plans = {}                                      # group index -> _Plan
         self._norm = None                                     # (see `_planned`)
+        self._guard_own = False                               # Adam / Lamb(skip_nonfinite=True): `_guard` is this object's own
+        self._guard = None                                    # a guard.StepGuard: own, or the step's (`attach_guard`)
+        self._guard_decided = False                           # the step's guard has run before `step()` is called
 
     # ---- state in flat buffers -------------------------------------------------------------------------------------------------
     class _Plan:
@@ -117,6 +127,52 @@ class _Planned(torch.optim.Optimizer):
     def _wants_norm(self) -> bool:
         return False
 
+    # ---- the non-finite guard ----------------------------------------------------------------------------------------------------
+    def attach_guard(self, guard, decided: bool = False) -> None:
+        """Obey a step's guard (`guard.StepGuard`; None detaches): every launch of `step()` takes its flag.  `decided`: the caller runs
+        the guard itself before each `step()` (over the flat gradient buffer, or from its clipping's norm); otherwise `step()` runs it --
+        from the partials of the gradient norm where this optimizer computes them (Lamb; SGD with `max_grad_norm`), else over its own
+        gradient tables.  Refused beside the optimizer's own `skip_nonfinite`: two guards would count one step twice."""
+        if guard is not None and (self._guard_own or getattr(self, "skip_nonfinite", False)):
+            raise ValueError(f"mcquic_amd.optim.{self._NAME}: both the step and the optimizer guard against a non-finite gradient "
+                             "(`skip_nonfinite`): one step would be counted twice; set one of them")
+        self._guard, self._guard_decided = guard, bool(decided) and guard is not None
+
+    def _own_guard(self, todo) -> None:
+        """(from `_planned`, outside any capture) the optimizer's own guard and the scratch its reduction needs."""
+        if self._guard_own and todo:
+            from .guard import StepGuard
+            dev = todo[0][1].step.device
+            if self._guard is None or self._guard.device != dev:
+                old, self._guard = self._guard, StepGuard(dev)
+                if old is not None:
+                    self._guard.record.copy_(old.record)
+        if self._guard is not None and todo and not self._guard_decided:
+            self._guard._room(sum(plan.nblocks for _, plan in todo))
+
+    def _flag(self, todo, partials=None, total: int = 0):
+        """The address of the flag this call's launches obey (None: no guard), after running the guard where that is this call's job."""
+        guard = self._guard
+        if guard is None:
+            return None
+        if not self._guard_decided:
+            if partials is not None:
+                guard.from_partials(partials, total)          # (the norm's partials exist already: no second pass over the gradients)
+            else:
+                guard.run_list([plan.table for _, plan in todo])
+        return guard.skip.data_ptr()
+
+    @property
+    def skipped(self) -> torch.Tensor:
+        """How many calls this optimizer's own guard has skipped (0-dim int64 on the device).  Adam / AdamW / Lamb have the counter with
+        `skip_nonfinite=True` only: without it nothing counts, and the attribute is absent as it always was."""
+        if not self._guard_own:
+            raise AttributeError(f"mcquic_amd.optim.{self._NAME}: `skipped` exists with skip_nonfinite=True only")
+        if self._guard is None:
+            from .guard import StepGuard
+            self._guard = StepGuard(next(p.device for g in self.param_groups for p in g["params"]))
+        return self._guard.skipped
+
     def _planned(self):
         """[(group, plan)] of the groups that hold gradients, tables current, and -- for an optimizer that `_wants_norm()` -- the buffers
         of the gradient norm they share: `self._norm` = (key, double partials of sum g^2 for all groups, G)."""
@@ -137,9 +193,10 @@ class _Planned(torch.optim.Optimizer):
             dev = out[0][1].step.device
             gnorm = self._norm[2] if self._norm is not None and self._norm[2].device == dev else torch.zeros((), dtype=torch.float32, device=dev)
             self._norm = (key, torch.zeros(max(sum(plan.nblocks for _, plan in out), 1), dtype=torch.float64, device=dev), gnorm)
+        self._own_guard([(g, plan) for g, plan in out if plan.nblocks > 0])
         return out
 
-    def _grad_partials(self, todo):
+    def _grad_partials(self, todo, skip=None):
         """(partials, total, G) for an optimizer that `_wants_norm()`, (None, 0, None) otherwise: the per-chunk sums of g^2 of every plan of
         `todo`, one launch each into one array of `total` doubles, from which every group's update derives the same norm G."""
         if not self._wants_norm():
@@ -148,8 +205,8 @@ class _Planned(torch.optim.Optimizer):
         total = 0
         with _guard(gnorm.device):
             for _, plan in todo:
-                check(_lib.load().mcq_lamb_grad_partials_f32(*plan.table.args(), partials.data_ptr() + 8 * total, _stream()),
-                      "mcq_lamb_grad_partials_f32")
+                check(_lib.load().mcq_lamb_grad_partials_skip_f32(*plan.table.args(), partials.data_ptr() + 8 * total, skip, _stream()),
+                      "mcq_lamb_grad_partials_skip_f32")
                 total += plan.nblocks
         return partials, total, gnorm
 
@@ -201,24 +258,29 @@ class Adam(_Planned):
     `decoupled=True` makes the decay AdamW's (`AdamW` below sets it and AdamW's default of 1e-2)."""
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0, *, decoupled: bool = False,
-                 maximize: bool = False):
+                 maximize: bool = False, skip_nonfinite: bool = False):
         self._check_adam_args(lr, betas, eps, weight_decay)
         # (capturable=True is what torch's load_state_dict looks at to keep `step` a float32 device tensor)
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, decoupled=bool(decoupled),
                                       maximize=bool(maximize), capturable=True))
+        self._guard_own = bool(skip_nonfinite)
 
     @torch.no_grad()
     def step(self, closure=None):
         self._no_closure(closure)
         lib = _lib.load()
-        for group, plan in self._planned():
+        todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
+        if not todo:
+            return None
+        flag = self._flag(todo)                               # (with a guard: ONE decision for all groups, before any is updated)
+        for group, plan in todo:
             lr_dev, lr_host = self._rate(group)
             b1, b2 = group["betas"]
             with _guard(plan.step.device):
-                check(lib.mcq_adam_step_f32(*plan.table.args(), plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(),
-                                            float(lr_host), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
-                                            1 if group["decoupled"] else 0, 1 if group["maximize"] else 0, plan.scalars.data_ptr(), _stream()),
-                      "mcq_adam_step_f32")
+                check(lib.mcq_adam_step_skip_f32(*plan.table.args(), plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(),
+                                                 float(lr_host), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]),
+                                                 1 if group["decoupled"] else 0, 1 if group["maximize"] else 0, plan.scalars.data_ptr(), flag,
+                                                 _stream()), "mcq_adam_step_skip_f32")
         return None
 
     def state_dict(self):
@@ -247,8 +309,9 @@ class Adam(_Planned):
 class AdamW(Adam):
     """torch.optim.AdamW: decoupled weight decay (param *= 1 - lr * weight_decay before the update), default 1e-2."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, *, maximize: bool = False):
-        super().__init__(params, lr, betas, eps, weight_decay, decoupled=True, maximize=maximize)
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2, *, maximize: bool = False,
+                 skip_nonfinite: bool = False):
+        super().__init__(params, lr, betas, eps, weight_decay, decoupled=True, maximize=maximize, skip_nonfinite=skip_nonfinite)
 
 
 class Lamb(_Planned):
@@ -274,7 +337,7 @@ class Lamb(_Planned):
         __slots__ = ("workspace", "ratios")
 
     def __init__(self, params, lr=1e-3, bias_correction=True, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.01, amsgrad=False,
-                 adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0, use_nvlamb=False):
+                 adam_w_mode=True, grad_averaging=True, set_grad_none=True, max_grad_norm=1.0, use_nvlamb=False, skip_nonfinite=False):
         if amsgrad:
             raise RuntimeError("mcquic_amd.optim.Lamb does not support the AMSGrad variant.")
         self._check_adam_args(lr, betas, eps, weight_decay)
@@ -284,6 +347,7 @@ class Lamb(_Planned):
                                       grad_averaging=bool(grad_averaging), max_grad_norm=max_grad_norm, adam_w_mode=bool(adam_w_mode),
                                       use_nvlamb=bool(use_nvlamb), capturable=True))
         self.set_grad_none = bool(set_grad_none)
+        self._guard_own = bool(skip_nonfinite)
 
     def zero_grad(self, set_to_none=None):
         super().zero_grad(self.set_grad_none if set_to_none is None else set_to_none)
@@ -319,17 +383,20 @@ class Lamb(_Planned):
         todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
         if not todo:
             return None
-        partials, total, gnorm = self._grad_partials(todo)    # the norm of ALL gradients first ...
+        decided = self._guard.skip.data_ptr() if self._guard is not None and self._guard_decided else None
+        partials, total, gnorm = self._grad_partials(todo, decided)      # the norm of ALL gradients first ...
+        flag = self._flag(todo, partials, total)              # (with a guard: the flag from those partials, LAMB's own G)
         with _guard(gnorm.device):
             for group, plan in todo:                          # ... then every group's update reads the same partials
                 lr_dev, lr_host = self._rate(group)
                 b1, b2 = group["betas"]
-                check(lib.mcq_lamb_step_f32(*plan.table.args(first_blk=True), partials.data_ptr(), total, plan.step.data_ptr(), None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(b1),
-                                            float(b2), float(group["eps"]), float(group["weight_decay"]), 1 if group["bias_correction"] else 0,
-                                            1 if group["adam_w_mode"] else 0, 1 if group["grad_averaging"] else 0,
-                                            1 if group["use_nvlamb"] else 0, float(group["max_grad_norm"]), gnorm.data_ptr(),
-                                            plan.ratios.data_ptr(), plan.workspace.data_ptr(), plan.scalars.data_ptr(), _stream()),
-                      "mcq_lamb_step_f32")
+                check(lib.mcq_lamb_step_skip_f32(*plan.table.args(first_blk=True), partials.data_ptr(), total, plan.step.data_ptr(),
+                                                 None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(b1),
+                                                 float(b2), float(group["eps"]), float(group["weight_decay"]), 1 if group["bias_correction"] else 0,
+                                                 1 if group["adam_w_mode"] else 0, 1 if group["grad_averaging"] else 0,
+                                                 1 if group["use_nvlamb"] else 0, float(group["max_grad_norm"]), gnorm.data_ptr(),
+                                                 plan.ratios.data_ptr(), plan.workspace.data_ptr(), plan.scalars.data_ptr(), flag, _stream()),
+                      "mcq_lamb_step_skip_f32")
         return None
 
     def load_state_dict(self, state_dict):
@@ -430,18 +497,20 @@ class SGD(_Planned):
         todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
         if not todo:
             return None
-        partials, total, gnorm = self._grad_partials(todo)    # with clipping or the guard: the norm of ALL gradients first
+        decided = self._guard.skip.data_ptr() if self._guard is not None and self._guard_decided else None
+        partials, total, gnorm = self._grad_partials(todo, decided)      # with clipping or the guard: the norm of ALL gradients first
+        flag = self._flag(todo, partials, total)              # (a step's guard, `attach_guard`; SGD's own lives in its scalar kernel)
         for i, (group, plan) in enumerate(todo):              # (every group derives the same factor and flag; the first one counts a skip)
             lr_dev, lr_host = self._rate(group)
             with _guard(plan.step.device):
-                check(lib.mcq_sgd_step_f32(*plan.table.args(), plan.step.data_ptr(),
+                check(lib.mcq_sgd_step_skip_f32(*plan.table.args(), plan.step.data_ptr(),
                                            None if lr_dev is None else lr_dev.data_ptr(), float(lr_host), float(group["momentum"]),
                                            float(group["dampening"]), float(group["weight_decay"]), 1 if group["nesterov"] else 0,
                                            1 if group["maximize"] else 0, None if partials is None else partials.data_ptr(), total,
                                            None if self.max_grad_norm is None else self._bound.data_ptr(),
                                            None if gnorm is None else gnorm.data_ptr(), 1 if self.skip_nonfinite else 0,
-                                           self._skipped.data_ptr() if self.skip_nonfinite and i == 0 else None, plan.scalars.data_ptr(), _stream()),
-                      "mcq_sgd_step_f32")
+                                           self._skipped.data_ptr() if self.skip_nonfinite and i == 0 else None, plan.scalars.data_ptr(), flag,
+                                           _stream()), "mcq_sgd_step_skip_f32")
         return None
 
     def state_dict(self):
@@ -550,7 +619,9 @@ class EMA:
 
     # ---- the average -----------------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def update(self) -> None:
+    def update(self, skip=None) -> None:
+        """`skip`: a step's guard flag (one int32 on the device, `guard.StepGuard.skip`): when it is set on the device, neither an
+        average nor the update count moves.  None: the launches are the ones they have always been."""
         if self.swapped:
             raise RuntimeError("mcquic_amd.optim.EMA: the averaged weights are swapped in (`swap()` / `applied()`): the model holds the average, "
                                "not the iterate; swap back before `update()`")
@@ -559,10 +630,12 @@ class EMA:
         if torch.is_tensor(decay) and (not decay.is_cuda or decay.dtype != torch.float32 or decay.numel() != 1):
             raise TypeError("mcquic_amd.optim.EMA: a tensor decay must be one float32 on the device")
         dev = torch.is_tensor(decay)
+        from .guard import skip_pointer
+        flag = skip_pointer(skip, self._flat.device, "mcquic_amd.optim.EMA.update")
         with _guard(self._flat.device):
-            check(_lib.load().mcq_ema_update_f32(*self._table.args(), self._count.data_ptr(), decay.data_ptr() if dev else None,
-                                                 0.0 if dev else float(decay), 1 if self.warmup else 0, self._scalars.data_ptr(), _stream()),
-                  "mcq_ema_update_f32")
+            check(_lib.load().mcq_ema_update_skip_f32(*self._table.args(), self._count.data_ptr(), decay.data_ptr() if dev else None,
+                                                      0.0 if dev else float(decay), 1 if self.warmup else 0, self._scalars.data_ptr(), flag,
+                                                      _stream()), "mcq_ema_update_skip_f32")
 
     @torch.no_grad()
     def warm(self) -> None:

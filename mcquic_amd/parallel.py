@@ -279,11 +279,28 @@ class GraphedTrainStep:
     advances the schedule's state on the device and stores the next rate into the tensors the optimizer's kernel reads, so replays
     follow the schedule with no host work in between.  The constructor leaves the schedule's state and the rates bit for bit as they
     were.  Without a scheduler not one launch changes.
+    `skip_nonfinite=True`: ONE device-side guard for the whole update (`mcquic_amd.guard.StepGuard`, csrc/step_guard.hip), exposed as
+    `step.guard` (`skip`, `skipped`, `consecutive`, `grad_norm`: 0-dim device tensors).  The update starts with it, after `/ world` and
+    before clipping: the global norm G of the gradient decides skip = !isfinite(G), and EVERY later launch of the update takes the flag --
+    the clip (the factor of a skipped step is never applied), the optimizer (`mcquic_amd.optim.Adam / AdamW / Lamb / SGD`; any other
+    optimizer is refused: it could not obey), the EMA, the frequency EMA and the scheduler.  A skipped step leaves every tensor the update
+    owns bit for bit as it was: parameters, optimizer state and step counts, the EMA shadow and its count, every `_freqEMA`, scheduler
+    state and rates; only the guard's record and the meter's row change (its `skipped` column is the guard's count; `step.grad_norm` is
+    the guard's norm).  A clean step produces the bits it produces with the guard off.  No second reduction is launched where a norm of
+    the same gradient exists: with `max_grad_norm` the guard takes the clip's sum of squares by pointer (one launch of one lane; the flag
+    is then float32's -- a finite gradient whose SQUARES overflow float32 is skipped rather than scaled to zero), Lamb and SGD with
+    `max_grad_norm` lend the partials of their own norm; otherwise the guard reduces the flat buffer itself (double partials per chunk,
+    a fixed tree: a finite gradient of 1e19 per element is not skipped).  The flag is computed from the ALL-REDUCED gradient only, never
+    from the rank-local loss: a NaN or inf on any rank survives the sum, every rank sees the same buffer and so every rank decides alike;
+    a flag from the local loss would let the replicas diverge.  `step.guard.check(max_consecutive=...)` is the one host read: it raises
+    the reference's `Loss becomes NAN. Train crashed.` once that many steps IN A ROW were skipped.  Setting it beside an optimizer's own
+    `skip_nonfinite` is refused, as `max_grad_norm` is.  With `skip_nonfinite=False` not one launch changes.
     """
 
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
-                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None, scheduler=None):
+                 broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None, scheduler=None,
+                 skip_nonfinite: bool = False):
         if not example_x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
         self.model, self.optimizer, self.group, self.ema, self.meter = model, optimizer, group, ema, meter
@@ -315,6 +332,16 @@ class GraphedTrainStep:
         if max_grad_norm is not None and getattr(optimizer, "max_grad_norm", None) is not None:
             raise ValueError("both the step and the optimizer clip (`max_grad_norm`): the gradient would be scaled twice; set one of them")
         self.max_grad_norm = max_grad_norm
+        self.guard = None                                     # guard.StepGuard with `skip_nonfinite`: the flag every launch of the update obeys
+        if skip_nonfinite:
+            if not hasattr(optimizer, "attach_guard"):
+                raise ValueError("skip_nonfinite needs an optimizer whose kernels take the guard's flag (mcquic_amd.optim.Adam / AdamW / Lamb / "
+                                 f"SGD); {type(optimizer).__module__}.{type(optimizer).__name__} would update through a skipped step")
+            if getattr(optimizer, "_guard_own", False) or getattr(optimizer, "skip_nonfinite", False):
+                raise ValueError("both the step and the optimizer guard against a non-finite gradient (`skip_nonfinite`): one step would be "
+                                 "counted twice; set one of them")
+            from .guard import StepGuard
+            self.guard = StepGuard(example_x.device)
         self.grad_norm = None                                 # 0-dim device tensor: the global gradient norm of the last step, before clipping
         if loss_fn is not None and not memset_nodes_replay_correctly(example_x.device):
             import warnings
@@ -408,6 +435,14 @@ class GraphedTrainStep:
             p.grad = self.flat[off: off + p.numel()].view_as(p)
             off += p.numel()
         self.post = None
+        if self.guard is not None:
+            # who runs the guard: the step from its clip's sum of squares; else the optimizer from the partials of its own norm (Lamb,
+            # SGD with max_grad_norm); else the step over the flat buffer
+            self._guard_lender = "clip" if self.max_grad_norm is not None else "optimizer" if self.optimizer._wants_norm() else "flat"
+            self.optimizer.attach_guard(self.guard, decided=self._guard_lender != "optimizer")
+            if self._guard_lender == "flat":
+                self.guard.prepare_flat(self.flat)
+            self.grad_norm = self.guard.grad_norm
         if hasattr(self.optimizer, "prepare"):                # (mcquic_amd.optim.Adam / Lamb / SGD: device tables for the flat gradient views, built
             self.optimizer.prepare()                          #  outside the capture)
         if self.ema is not None:                              # (its tables, and its kernels' first launch, outside the capture: a throw-away
@@ -419,6 +454,8 @@ class GraphedTrainStep:
         if self.scheduler is not None:                        # (the same for the schedule: last_epoch, state and rates keep their bits)
             self.scheduler.prepare()
             self.scheduler.warm()
+        if self.guard is not None:
+            self._warm_guard()
         if capture_post:
             before = self._snapshot_optimizer_state()
             try:
@@ -586,6 +623,8 @@ class GraphedTrainStep:
     def _post(self):
         if self.world > 1:
             self.flat.mul_(1.0 / self.world)
+        if self.guard is not None:
+            return self._post_guarded()
         if self.max_grad_norm is not None:                    # trainer.py:280 `clip_grad_norm(4.0)`: global norm of the AVERAGED gradient,
             from . import ops                                 # two launches over the flat buffer, nothing read by the host
             self.grad_norm = ops.clip_by_norm_(self.flat, self.max_grad_norm)
@@ -602,13 +641,70 @@ class GraphedTrainStep:
         if self.meter is not None:
             self._meter_update()
 
+    def _warm_guard(self):
+        """Every kernel of the guarded update once outside any capture, without moving a bit of state: the `_skip` launches under a
+        scratch guard whose flag is SET (a skipped launch writes nothing), the guard's own launches into that scratch record."""
+        from . import ops
+        from .guard import StepGuard
+        scratch = StepGuard(self.flat.device)
+        scratch.run_flat(self.flat)
+        scratch.from_partials(scratch._partials, 1)
+        sq = ops.sumsq(self.flat)
+        scratch.from_norm(sq, squared=True)
+        scratch.record[0] = 1                                 # (the int32 `skip` is the low word)
+        flag = scratch.skip
+        if self.max_grad_norm is not None:
+            ops.clip_by_norm_(self.flat, self.max_grad_norm, sq=sq, skip=flag)
+        self.optimizer.attach_guard(scratch, decided=True)
+        try:
+            self.optimizer.step()
+        finally:
+            self.optimizer.attach_guard(self.guard, decided=self._guard_lender != "optimizer")
+        if self.ema is not None:
+            self.ema.update(skip=flag)
+        off = 0
+        for c in self.coders:
+            n = c.countSink().numel()
+            c.applyCounts(self.counts[off: off + n], skip=flag)
+            off += n
+        if self.scheduler is not None:
+            self.scheduler.step(skip=flag)
+        torch.cuda.synchronize()
+
+    def _post_guarded(self):
+        """`_post` with `skip_nonfinite`: the guard first (on the all-reduced, averaged gradient), then the same launches in the same
+        order, each taking the flag."""
+        from . import ops
+        flag = self.guard.skip
+        if self._guard_lender == "clip":                      # the clip's sum of squares decides: no second reduction
+            sq = ops.sumsq(self.flat)
+            self.guard.from_norm(sq, squared=True)
+            ops.clip_by_norm_(self.flat, self.max_grad_norm, sq=sq, skip=flag)
+        elif self._guard_lender == "flat":
+            self.guard.run_flat(self.flat)
+        self.optimizer.step()                                 # (`attach_guard`: every launch obeys; the "optimizer" lender runs the guard here)
+        if self.ema is not None:
+            self.ema.update(skip=flag)
+        off = 0
+        for c in self.coders:
+            n = c.countSink().numel()
+            c.applyCounts(self.counts[off: off + n], skip=flag)
+            off += n
+        if self.scheduler is not None:
+            self.scheduler.step(skip=flag)
+        if self.meter is not None:
+            self._meter_update()
+
     def _meter_update(self):
         """The telemetry row of this step (monitor.StepMeter.update): every value goes by device pointer, nothing is read here."""
         opt = self.optimizer
         norm = self.grad_norm
+        if self.guard is not None:                            # (the guard's record: its norm, its count of skipped steps)
+            self.meter.update(self.loss, self.counts, grad_norm=self.guard.grad_norm, lr=opt.param_groups[0]["lr"], skipped=self.guard.skipped)
+            return
         if norm is None and hasattr(opt, "_last_grad_norm"):  # (mcquic_amd.optim: Lamb always; SGD with max_grad_norm or skip_nonfinite)
             norm = opt._last_grad_norm()
-        skipped = getattr(opt, "skipped", None)
+        skipped = getattr(opt, "skipped", None)              # (optim.SGD always; optim.Adam / AdamW / Lamb with their own `skip_nonfinite`)
         self.meter.update(self.loss, self.counts, grad_norm=norm, lr=opt.param_groups[0]["lr"],
                           skipped=skipped if torch.is_tensor(skipped) else None)
 

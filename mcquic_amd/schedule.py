@@ -150,15 +150,19 @@ class _DeviceScheduler:
             self._tables = (ptrs, miles, self._rule(len(self._lrs), miles.data_ptr() if miles is not None else None))
 
     @torch.no_grad()
-    def step(self) -> None:
-        """One `scheduler.step()` on the device: last_epoch += 1, every group's state advanced, float32(rate) stored into its `lr`."""
+    def step(self, skip=None) -> None:
+        """One `scheduler.step()` on the device: last_epoch += 1, every group's state advanced, float32(rate) stored into its `lr`.
+        `skip`: a step's guard flag (one int32 on the device, `guard.StepGuard.skip`): when it is set on the device the schedule stays
+        where it is -- last_epoch, state and rates."""
         self._no_cpu()
         if self._tables is None or any(g["lr"] is not lr for g, lr in zip(self.optimizer.param_groups, self._lrs)):
             self.prepare()
         ptrs, _, rule = self._tables
+        from .guard import skip_pointer
+        flag = skip_pointer(skip, self._buf.device, "mcquic_amd.schedule: step")
         with _guard(self._buf.device):
-            check(_lib.load().mcq_lr_schedule_step(ctypes.byref(rule), self._buf.data_ptr(), self._buf.data_ptr() + 8, ptrs.data_ptr(), _stream()),
-                  "mcq_lr_schedule_step")
+            check(_lib.load().mcq_lr_schedule_step_skip(ctypes.byref(rule), self._buf.data_ptr(), self._buf.data_ptr() + 8, ptrs.data_ptr(), flag,
+                                                        _stream()), "mcq_lr_schedule_step_skip")
 
     @torch.no_grad()
     def warm(self) -> None:
