@@ -619,6 +619,54 @@ int mcq_step_meter_update_f32(const float* const* freq_ema /* [levels] device po
                               double momentum, double floor, double pixels, int64_t* state /* device [4] */, int64_t* steps /* [capacity] */,
                               float* ring /* [capacity][columns] */, int64_t capacity, void* stream);
 
+/* The trainer's periodic log payload made on the device (csrc/step_snapshot.hip; host mirror mcquic_amd.monitor.StepSnapshot): what
+ * the reference's `MainTrainer.log` (mcquic/train/trainer.py:463-491) builds on the host from whole tensors of the step.  Additions:
+ * the ABI number stays.
+ *
+ * mcq_histogram_f32: np.histogram(v, bins) of n float32 values, v = x (transform 0) or log10f(clamp(-x, min = eps)) (transform 1:
+ * `neg`, `clamp(min)` -- a NaN passes through --, `log10`, each rounded to float32), evaluated in registers and never stored.
+ * Three launches.  Pass 1: min and max of v over the FINITE entries, a fixed two-stage reduction (equal inputs give equal bits).
+ * Pass 2: per-workgroup LDS integer counts, folded into `counts` with integer atomics (exact in any order).  Restated from
+ * numpy/lib/_histograms_impl.py (`_get_outer_edges`, `_get_bin_edges`, the uniform-bin fast path of `histogram`), in float64
+ * throughout -- what np.histogram returns for the same values widened to float64 (for a float32 ARRAY numpy >= 2 keeps the edges
+ * in float32; widened values are the same numbers, the edges then carry float64):
+ *   range   (min, max); (0, 1) without a finite value; if min == max: (min - 0.5, max + 0.5)
+ *   edges   np.linspace(first, last, bins + 1): i * ((last - first) / bins) + first (i / bins * (last - first) + first if that step is
+ *           0), two roundings; the last edge is `last` itself
+ *   index   int(((v - first) / (last - first)) * bins), `bins` folded into bins - 1; then one down if v < edges[i], then one up if
+ *           v >= edges[i + 1] unless i is the last bin (closed on the right)
+ * A non-finite v is counted in stats[1] and left out, where numpy raises ("autodetected range ... is not finite"); stats[0] counts
+ * the finite ones (= sum of `counts`).  Where numpy raises "Too many bins for data range" (all values equal and |v| >= 2^53, so
+ * that a half does not widen the range) everything lands in bin 0.  1 <= bins <= 4096, n <= 2^40 (MCQ_ETOOLARGE beyond);
+ * `workspace`: mcq_histogram_workspace_bytes(n, bins) bytes, 8-byte aligned (0 for arguments the call refuses).  A workgroup takes
+ * mcq_histogram_chunk() elements per trip, as float4 loads when x is 16-byte aligned and the chunk is full. */
+int32_t mcq_histogram_chunk(void);
+size_t mcq_histogram_workspace_bytes(int64_t n, int32_t bins);
+int mcq_histogram_f32(const float* x, int64_t n, int32_t transform, float eps, int32_t bins, int64_t* counts /* [bins] */,
+                      double* edges /* [bins + 1] */, int64_t* stats /* [2]: finite, non-finite */, void* workspace, void* stream);
+/* out[i] = log10f(clamp(-x[i], min = eps)): transform 1 of mcq_histogram_f32, written out. */
+int mcq_log_distance_f32(const float* x, float* out, int64_t n, float eps, void* stream);
+
+/* `Validator.visualizeIntermediate` (mcquic/validate/validator.py:30-38) of int64 codes [N, m, h, w] -> uint8 [N, 1, 4h, 4w]:
+ * t = (float(c) / float(max) - 0.5f) * 2 with the maximum over the WHOLE tensor (all images, all groups; launch 1, one workgroup,
+ * left in maxbuf[0]), DeTransform as mcq_detransform_u8, group 0 only, each value stored to the 4 x 4 block that
+ * F.interpolate(scale_factor=4, mode="nearest") fills (launch 2).  A maximum of 0 is 0 / 0 in the reference, a NaN converted to
+ * uint8, which is unspecified: 0 is written here.  `out` 4-byte aligned.  mcq_code_image_first_u8 writes the first `keep` <= N
+ * images only ([keep, 1, 4h, 4w]); the maximum is still the whole tensor's. */
+int mcq_code_image_u8(const int64_t* codes, uint8_t* out, int64_t* maxbuf /* device [1] */, int32_t N, int32_t m, int32_t h, int32_t w,
+                      void* stream);
+int mcq_code_image_first_u8(const int64_t* codes, uint8_t* out, int64_t* maxbuf /* device [1] */, int32_t N, int32_t m, int32_t h, int32_t w,
+                            int32_t keep, void* stream);
+
+/* Group 0 of every level's normalised frequency EMA, f / sum f (`NormalizedFreq[l][0]`, mcquic/modules/entropyCoder.py:46-52), back
+ * to back in `out` (sum_l k_l floats), and `Compressor.CodeUsage` in usage[0]: entries of ALL groups with f / sum f > 1e-6 (float32
+ * against float32(1e-6), strict) over all entries, divided in float32.  The row sum is formed in double in a fixed order and
+ * rounded to float32 once; the quotient is float32.  Level tables as for mcq_step_meter_update_f32; `workspace`:
+ * mcq_snapshot_freq_workspace_bytes(m, k, levels) bytes (0 for an invalid table), 4-byte aligned.  Two launches, no atomics. */
+size_t mcq_snapshot_freq_workspace_bytes(const int32_t* m, const int32_t* k, int32_t levels);
+int mcq_snapshot_freq_f32(const float* const* freq_ema /* [levels] device pointers */, const int32_t* m, const int32_t* k, int32_t levels,
+                          float* out, float* usage /* device [1] */, void* workspace, void* stream);
+
 /* Learning-rate schedules stepped on the device (csrc/schedule.hip, the rule itself: csrc/schedule_rule.h; host mirror
  * mcquic_amd.schedule): the reference's four schedulers (mcquic/train/lrSchedulers.py), stepped after every batch
  * (mcquic/train/trainer.py `_stepFinish`), as ONE launch of ONE workgroup with one lane per parameter group, so that a captured

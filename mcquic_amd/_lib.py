@@ -183,6 +183,14 @@ SYMBOLS = {
     "mcq_step_meter_columns": (c_int32, [c_int32]),
     "mcq_step_meter_update_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
                                             c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mcq_histogram_chunk": (c_int32, []),
+    "mcq_histogram_workspace_bytes": (c_size_t, [c_int64, c_int32]),
+    "mcq_histogram_f32": (c_int32, [c_void_p, c_int64, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "mcq_log_distance_f32": (c_int32, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    "mcq_code_image_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "mcq_code_image_first_u8": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p]),
+    "mcq_snapshot_freq_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int32]),
+    "mcq_snapshot_freq_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mcq_sumsq_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "mcq_clip_by_norm_f32": (c_int32, [c_void_p, c_void_p, c_float, c_float, c_void_p, c_int64, c_void_p]),
     "mcq_detransform_u8": (c_int32, [c_void_p, c_void_p, c_int64, c_void_p]),

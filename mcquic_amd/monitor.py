@@ -4,6 +4,9 @@ rate, the `Loss becomes NAN. Train crashed.` guard; trainer.py:463-491 `log`: `C
 one float32 row per step in a ring buffer by two HIP launches (csrc/step_meter.hip) that read every value through a device pointer.
 The host copies the buffer back when it likes, with one copy; nothing else here synchronises, so the launches sit in the captured
 post graph of `parallel.GraphedTrainStep(..., meter=...)` and a replay stays free of host reads.
+
+`StepSnapshot` is the periodic payload of that `log` (the LogDistance histogram, the frequency and code-map pictures, the batch and its
+reconstruction as images), made by the kernels of csrc/step_snapshot.hip into one buffer when the host asks for it.
 """
 from __future__ import annotations
 
@@ -13,7 +16,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from .ops import _guard, _stream, check
 
 HEAD = ("loss", "db", "db_ema", "grad_norm", "lr", "skipped", "code_usage", "bpp")
@@ -203,3 +206,172 @@ class StepMeter:
         self._steps.copy_(sd["steps"].to(dev, torch.int64))
         self._last_read = int(sd.get("last_read", 0))
 
+
+class StepSnapshot:
+    """The reference trainer's periodic log payload (`MainTrainer.log`, mcquic/train/trainer.py:463-491) made on the device and read with
+    one copy, where the reference moves the whole level-0 slab of logits to the host and bins it there:
+
+        snap = StepSnapshot(model, batch_shape=(n, 3, H, W), bins=64, images=4)
+        snap.prepare()                                  # tables + ONE device buffer; nothing is allocated afterwards
+        snap.capture(images, restored, codes, logits)   # launches only, on the current stream, capturable; no host read
+        payload = snap.read()                           # ONE device-to-host copy
+
+    or, behind a `parallel.GraphedTrainStep(..., keep_outputs=True)`: `payload = step.snapshot(snap)`.  `read()` keys are the reference's
+    wandb keys (there is no wandb import here: wrap them yourself):
+
+        Hist/LogDistance     (counts int64 [bins], edges float64 [bins + 1]) of log10(clamp(-logits[0][0, 0], 1e-6)) in np.histogram's
+                             form (`wandb.Histogram(np_histogram=...)`): level 0, image 0, group 0.  Non-finite values are left out and
+                             counted: `snap.stats` = (finite, non-finite) of the last read.  The edges and the bin index are numpy's
+                             evaluated in float64 (numpy >= 2 keeps float32 edges for a float32 array)
+        Hist/FreqLvNN        (group 0 of the level's normalised frequency EMA float32 [k], np.arange(0.5, k + 1.5)), as the reference pairs them
+        Hist/CodeLvNN        uint8 [images, 1, 4h, 4w]: `Validator.visualizeIntermediate` of the level's codes (group 0, scaled by the maximum of
+                             the WHOLE batch's codes, enlarged 4x); an all-zero code tensor gives 0
+        Train/Raw, Train/Res uint8 [images, 3, H, W]: `ops.detransform` of the batch and of its reconstruction
+        Stat/CodeUsage       float: `Compressor.CodeUsage` of the frequency EMA
+
+    `images`: only the first `images` images of the batch are kept (None, or more than the batch has: all, as the reference logs them).  `code_shapes`: (h, w) of every
+    level's code map, in the order of the model's `codes`; by default the 16x stem and a halving per level, (H / 16 >> l, W / 16 >> l).
+    HIP device and float32 only: there is no CPU path.  Inside a captured graph the kernels' first launch must have happened before:
+    run one eager `capture` first."""
+
+    EPS = 1e-6                                                # Consts.Eps
+
+    def __init__(self, model, batch_shape, bins: int = 64, images: Optional[int] = 4, code_shapes=None):
+        coders = [m for m in model.modules() if hasattr(m, "deferCounts")]
+        if not coders:
+            raise ValueError("mcquic_amd.monitor.StepSnapshot: the model has no entropy coder (no module with `deferCounts`)")
+        self.freqs = [f for c in coders for f in c._freqEMA]
+        for f in self.freqs:
+            if not f.is_cuda:
+                raise RuntimeError(f"mcquic_amd: the model's frequency tables must live on a HIP device (got {f.device}); "
+                                   "the HIP kernels have no CPU fallback")
+            if f.dtype != torch.float32:
+                raise TypeError(f"mcquic_amd: the model's frequency tables must be torch.float32 (got {f.dtype})")
+            if f.device != self.freqs[0].device:
+                raise RuntimeError("mcquic_amd.monitor.StepSnapshot: the coders must live on one device")
+        if len(batch_shape) != 4 or int(batch_shape[1]) != 3 or min(int(s) for s in batch_shape) < 1:
+            raise ValueError(f"mcquic_amd.monitor.StepSnapshot: batch_shape (n, 3, H, W) is required (got {tuple(batch_shape)})")
+        self.batch_shape = tuple(int(s) for s in batch_shape)
+        n, _, H, W = self.batch_shape
+        self.keep = n if images is None else min(int(images), n)
+        if self.keep < 1 or not 1 <= int(bins) <= ops.HIST_MAX_BINS:
+            raise ValueError(f"mcquic_amd.monitor.StepSnapshot: images >= 1 and 1 <= bins <= {ops.HIST_MAX_BINS} are required")
+        self.bins = int(bins)
+        self.ms, self.ks = [int(f.shape[0]) for f in self.freqs], [int(f.shape[1]) for f in self.freqs]
+        self.levels = len(self.freqs)
+        lib = _lib.load()
+        if self.levels > int(lib.mcq_vq_max_levels()):
+            raise ValueError(f"mcquic_amd.monitor.StepSnapshot: {self.levels} levels, the kernels' tables hold {int(lib.mcq_vq_max_levels())}")
+        if code_shapes is None:
+            code_shapes = [((H // 16) >> l, (W // 16) >> l) for l in range(self.levels)]
+        self.code_shapes = [(int(h), int(w)) for h, w in code_shapes]
+        if len(self.code_shapes) != self.levels or min(min(s) for s in self.code_shapes) < 1:
+            raise ValueError(f"mcquic_amd.monitor.StepSnapshot: one positive (h, w) per level is required (got {self.code_shapes})")
+        self.slab = self.code_shapes[0][0] * self.code_shapes[0][1] * self.ks[0]        # logits[0][0, 0]: [h, w, k]
+        self.stats = None
+        self._buf = self._tables = self._key = None
+
+    # ---- the buffer: [counts] [edges] [stats] [usage] [code maxima] [freq] [code images] [raw] [res] | workspaces (not read back) ----
+    def _layout(self):
+        n, _, H, W = self.batch_shape
+        words = lambda nbytes: (int(nbytes) + 7) // 8
+        at, off = {}, 0
+        for name, size in [("counts", self.bins), ("edges", self.bins + 1), ("stats", 2), ("usage", 1), ("max", self.levels),
+                           ("freq", words(4 * sum(self.ks)))] + \
+                          [(f"code{l}", words(self.keep * 16 * h * w)) for l, (h, w) in enumerate(self.code_shapes)] + \
+                          [("raw", words(self.keep * 3 * H * W)), ("res", words(self.keep * 3 * H * W))]:
+            at[name] = (off, size)
+            off += size
+        return at, off
+
+    @torch.no_grad()
+    def prepare(self) -> None:
+        """The level tables, the buffer and the workspaces for the addresses the frequency tables have NOW.  Rebuilt when a table's
+        storage address changes (not inside a capture)."""
+        key = tuple(f.data_ptr() for f in self.freqs)
+        if key == self._key:
+            return
+        for f in self.freqs:
+            if not (f.is_cuda and f.is_contiguous() and f.device == self.freqs[0].device):
+                raise RuntimeError("mcquic_amd.monitor.StepSnapshot: contiguous frequency tables on one HIP device only (there is no CPU path)")
+        if torch.cuda.is_current_stream_capturing() and self._buf is None:
+            raise RuntimeError("mcquic_amd.monitor.StepSnapshot: call `prepare()` before capturing (the buffer cannot be allocated inside a graph)")
+        n = self.levels
+        ms, ks = (ctypes.c_int32 * n)(*self.ms), (ctypes.c_int32 * n)(*self.ks)
+        if self._buf is None:
+            lib = _lib.load()
+            hist_ws, freq_ws = int(lib.mcq_histogram_workspace_bytes(self.slab, self.bins)), int(lib.mcq_snapshot_freq_workspace_bytes(ms, ks, n))
+            if hist_ws <= 0 or freq_ws <= 0:
+                raise ValueError("mcquic_amd.monitor.StepSnapshot: the level table or the slab is not one the kernels take")
+            self._at, self._payload = self._layout()
+            w1, w2 = (hist_ws + 7) // 8, (freq_ws + 7) // 8
+            self._buf = torch.zeros(self._payload + w1 + w2, dtype=torch.int64, device=self.freqs[0].device)
+            self._hist_ws, self._freq_ws = self._buf[self._payload: self._payload + w1], self._buf[self._payload + w1:]
+        self._tables = ((ctypes.c_void_p * n)(*key), ms, ks)
+        self._key = key
+
+    def _view(self, name: str) -> torch.Tensor:
+        off, size = self._at[name]
+        return self._buf[off: off + size]
+
+    def _tensor(self, t, name: str, dtype, shape):
+        dev = self.freqs[0].device
+        if not torch.is_tensor(t) or not t.is_cuda or t.device != dev:
+            raise RuntimeError(f"mcquic_amd: `{name}` must live on the snapshot's HIP device; the HIP kernels have no CPU fallback")
+        if t.dtype != dtype:
+            raise TypeError(f"mcquic_amd: `{name}` must be {dtype} (got {t.dtype})")
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError(f"mcquic_amd.monitor.StepSnapshot: `{name}` must be contiguous {tuple(shape)} (got {tuple(t.shape)})")
+        return t
+
+    # ---- one snapshot ----------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def capture(self, images: torch.Tensor, restored: torch.Tensor, codes, logits) -> None:
+        """Make the payload of one step in the buffer: thirteen launches at three levels, on the current stream, nothing read by the host.
+        `images`, `restored`: the batch and its reconstruction, float32 [n, 3, H, W]; `codes`: the int64 [n, m_l, h_l, w_l] code maps of
+        all levels; `logits`: the levels' logits ([n, m, h, w, k] float32; only `logits[0][0, 0]` is read), or that level-0 tensor itself."""
+        self.prepare()
+        dev = self.freqs[0].device
+        images = self._tensor(images, "images", torch.float32, self.batch_shape)
+        restored = self._tensor(restored, "restored", torch.float32, self.batch_shape)
+        if len(codes) != self.levels:
+            raise ValueError(f"mcquic_amd.monitor.StepSnapshot: {self.levels} code levels are required (got {len(codes)})")
+        codes = [self._tensor(c, f"codes[{l}]", torch.int64, (self.batch_shape[0], self.ms[l]) + self.code_shapes[l]) for l, c in enumerate(codes)]
+        lg = logits if torch.is_tensor(logits) else logits[0]
+        h0, w0 = self.code_shapes[0]
+        lg = self._tensor(lg, "logits[0]", torch.float32, (self.batch_shape[0], self.ms[0], h0, w0, self.ks[0]))
+        lib = _lib.load()
+        ptrs, ms, ks = self._tables
+        with _guard(dev):
+            stream = _stream()
+            check(lib.mcq_histogram_f32(lg.data_ptr(), self.slab, ops.HIST_LOG_DISTANCE, self.EPS, self.bins, self._view("counts").data_ptr(),
+                                        self._view("edges").data_ptr(), self._view("stats").data_ptr(), self._hist_ws.data_ptr(), stream),
+                  "mcq_histogram_f32")
+            check(lib.mcq_snapshot_freq_f32(ptrs, ms, ks, self.levels, self._view("freq").data_ptr(), self._view("usage").data_ptr(),
+                                            self._freq_ws.data_ptr(), stream), "mcq_snapshot_freq_f32")
+        for l, c in enumerate(codes):
+            ops.code_image(c, keep=self.keep, out=self._view(f"code{l}").view(torch.uint8)[: self.keep * 16 * c.shape[2] * c.shape[3]],
+                           maxbuf=self._view("max")[l: l + 1])
+        pixels = self.keep * 3 * self.batch_shape[2] * self.batch_shape[3]
+        ops.detransform(images[: self.keep], out=self._view("raw").view(torch.uint8)[:pixels])
+        ops.detransform(restored[: self.keep], out=self._view("res").view(torch.uint8)[:pixels])
+
+    def read(self) -> dict:
+        """The payload of the last `capture`, keyed as the reference's `wandb.log` payload.  One device-to-host copy of the buffer (a host
+        synchronisation: call it when you want to look)."""
+        if self._buf is None:
+            raise RuntimeError("mcquic_amd.monitor.StepSnapshot: nothing was captured yet (`prepare()`, then `capture(...)`)")
+        host = self._buf[: self._payload].cpu().numpy()
+        part = lambda name: host[self._at[name][0]: self._at[name][0] + self._at[name][1]]
+        _, _, H, W = self.batch_shape
+        self.stats = tuple(int(v) for v in part("stats"))
+        out = {"Hist/LogDistance": (part("counts").copy(), part("edges").view(np.float64).copy())}
+        freq, off = part("freq").view(np.float32), 0
+        for l, (k, (h, w)) in enumerate(zip(self.ks, self.code_shapes)):
+            out[f"Hist/FreqLv{l:02d}"] = (freq[off: off + k].copy(), np.arange(0.5, k + 1.5, 1.0))
+            out[f"Hist/CodeLv{l:02d}"] = part(f"code{l}").view(np.uint8)[: self.keep * 16 * h * w].reshape(self.keep, 1, 4 * h, 4 * w).copy()
+            off += k
+        for name, key in (("raw", "Train/Raw"), ("res", "Train/Res")):
+            out[key] = part(name).view(np.uint8)[: self.keep * 3 * H * W].reshape(self.keep, 3, H, W).copy()
+        out["Stat/CodeUsage"] = float(part("usage").view(np.float32)[0])
+        return out

@@ -1197,12 +1197,77 @@ def group_norm_bwd(x: torch.Tensor, dy: torch.Tensor, weight: Optional[torch.Ten
     return dx, dw, db
 
 
-def detransform(x: torch.Tensor) -> torch.Tensor:
-    """[-1, 1] fp32 -> uint8 (mcquic/utils/vision.py:143-146)."""
+def detransform(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """[-1, 1] fp32 -> uint8 (mcquic/utils/vision.py:143-146).  `out`: a contiguous uint8 tensor of x's size on x's device to write
+    into (nothing is allocated then)."""
     x = _dev(x, "x")
-    out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or out.device != x.device or out.numel() != x.numel() or not out.is_contiguous():
+        raise ValueError(f"mcquic_amd: `out` must be {x.numel()} contiguous uint8 values on {x.device}")
     with _guard(x.device):
         check(_lib.load().mcq_detransform_u8(_ptr(x), _ptr(out), x.numel(), _stream()), "mcq_detransform_u8")
+    return out
+
+
+# ---- the trainer's log payload (csrc/step_snapshot.hip; gathered by monitor.StepSnapshot) ------------------------------------------
+HIST_IDENTITY, HIST_LOG_DISTANCE = 0, 1
+HIST_MAX_BINS = 4096
+
+
+def histogram(x: torch.Tensor, bins: int = 64, transform: int = HIST_IDENTITY, eps: float = 1e-6):
+    """`np.histogram(v, bins)` of a float32 device tensor, v = x or (`HIST_LOG_DISTANCE`) `(-x).clamp(eps).log10()` evaluated in
+    registers: (counts int64 [bins], edges float64 [bins + 1], stats int64 [2]: finite, non-finite values) as device tensors.  The
+    edges and the bin index are numpy's in float64 (include/mcquic_hip.h has the statement); non-finite values are counted in
+    `stats[1]` and left out, where numpy raises.  Nothing is read by the host."""
+    x = _dev(x, "x")
+    n, bins = x.numel(), int(bins)
+    lib = _lib.load()
+    nbytes = int(lib.mcq_histogram_workspace_bytes(n, bins))
+    if nbytes <= 0 or transform not in (HIST_IDENTITY, HIST_LOG_DISTANCE):
+        raise ValueError(f"mcquic_amd.ops.histogram: n > 0, 1 <= bins <= {HIST_MAX_BINS} and a known transform are required "
+                         f"(got n={n}, bins={bins}, transform={transform})")
+    counts = torch.empty(bins, dtype=torch.int64, device=x.device)
+    edges = torch.empty(bins + 1, dtype=torch.float64, device=x.device)
+    stats = torch.empty(2, dtype=torch.int64, device=x.device)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=x.device)
+    with _guard(x.device):
+        check(lib.mcq_histogram_f32(_ptr(x), n, int(transform), float(eps), bins, _ptr(counts), _ptr(edges), _ptr(stats), _ptr(ws), _stream()),
+              "mcq_histogram_f32")
+    return counts, edges, stats
+
+
+def log_distance(x: torch.Tensor, eps: float = 1e-6) -> torch.Tensor:
+    """`(-x).clamp(eps).log10()` (mcquic/train/trainer.py:469), float32 op by op: what `histogram(..., HIST_LOG_DISTANCE)` bins."""
+    x = _dev(x, "x")
+    out = torch.empty_like(x)
+    with _guard(x.device):
+        check(_lib.load().mcq_log_distance_f32(_ptr(x), _ptr(out), x.numel(), float(eps), _stream()), "mcq_log_distance_f32")
+    return out
+
+
+def code_image(codes: torch.Tensor, keep: Optional[int] = None, out: Optional[torch.Tensor] = None,
+               maxbuf: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """`Validator.visualizeIntermediate` (mcquic/validate/validator.py:30-38): int64 codes [N, m, h, w] -> uint8 [N, 1, 4h, 4w], group 0
+    scaled by the maximum over the WHOLE tensor, de-transformed and enlarged 4x (nearest).  `keep`: the first `keep` images only (the
+    maximum is still the whole tensor's).  An all-zero tensor gives 0 (0 / 0 in the reference).  `out` / `maxbuf` (int64 [1]): buffers to
+    write into, nothing is allocated then."""
+    codes = _dev(codes, "codes", torch.int64)
+    if codes.dim() != 4 or codes.numel() == 0:
+        raise ValueError(f"mcquic_amd.ops.code_image: codes [N, m, h, w] are required (got {tuple(codes.shape)})")
+    N, m, h, w = (int(s) for s in codes.shape)
+    keep = N if keep is None else int(keep)
+    if not 1 <= keep <= N:
+        raise ValueError(f"mcquic_amd.ops.code_image: 1 <= keep <= {N} is required (got {keep})")
+    if out is None:
+        out = torch.empty((keep, 1, 4 * h, 4 * w), dtype=torch.uint8, device=codes.device)
+    elif (out.dtype != torch.uint8 or out.device != codes.device or out.numel() != keep * 16 * h * w or not out.is_contiguous()
+          or out.data_ptr() % 4):
+        raise ValueError(f"mcquic_amd: `out` must be {keep * 16 * h * w} contiguous, 4-byte aligned uint8 values on {codes.device}")
+    if maxbuf is None:
+        maxbuf = torch.empty(1, dtype=torch.int64, device=codes.device)
+    with _guard(codes.device):
+        check(_lib.load().mcq_code_image_first_u8(_ptr(codes), _ptr(out), _ptr(maxbuf), N, m, h, w, keep, _stream()), "mcq_code_image_first_u8")
     return out
 
 

@@ -295,18 +295,23 @@ class GraphedTrainStep:
     a flag from the local loss would let the replicas diverge.  `step.guard.check(max_consecutive=...)` is the one host read: it raises
     the reference's `Loss becomes NAN. Train crashed.` once that many steps IN A ROW were skipped.  Setting it beside an optimizer's own
     `skip_nonfinite` is refused, as `max_grad_norm` is.  With `skip_nonfinite=False` not one launch changes.
+
+    `keep_outputs=True` keeps references to the reconstruction, the codes and the level-0 logits of the captured forward pass (`step.outputs`;
+    the graph's pool is larger by the logits, no launch is added), so that `step.snapshot(snap)` can make the reference trainer's periodic log
+    payload (`monitor.StepSnapshot`) of the last replay whenever the host wants one, outside the graphs.
     """
 
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
                  broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None, scheduler=None,
-                 skip_nonfinite: bool = False):
+                 skip_nonfinite: bool = False, keep_outputs: bool = False):
         if not example_x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
         self.model, self.optimizer, self.group, self.ema, self.meter = model, optimizer, group, ema, meter
         if scheduler is not None and getattr(scheduler, "optimizer", None) is not optimizer:
             raise ValueError("GraphedTrainStep: `scheduler` steps another optimizer's learning rates than `optimizer`'s")
         self.scheduler = scheduler
+        self.keep_outputs, self.outputs = bool(keep_outputs), None      # (xHat, codes, level-0 logits) of the last replay, for `snapshot`
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
         self.x = example_x.detach().clone()
         self.transform, self.raw = transform, None
@@ -588,6 +593,7 @@ class GraphedTrainStep:
             xHat = m._decoder(yh)
             loss = self.loss_fn((xHat, yh, codes, lgl), self.x)
             _backward(loss)                                   # decoder parameters, d yHat (, d logits)
+            self._keep((xHat, yHat, codes, logits))
             self.loss = loss.detach()
             self._carry = (y, yl, yHat, yh, logits, lgl)
         elif k == 1:
@@ -618,7 +624,31 @@ class GraphedTrainStep:
         out = self.model(self.x, **self.kwargs)
         loss = self.loss_fn(out, self.x)
         _backward(loss)
+        self._keep(out)
         return loss.detach()
+
+    def _keep(self, out):
+        """With `keep_outputs`: references to the reconstruction, the codes and the level-0 logits of the forward pass, so that the
+        capture's allocations stay theirs after the backward pass (no launch is added; the graph's pool is larger by the logits)."""
+        if not self.keep_outputs:
+            return
+        if not (isinstance(out, (tuple, list)) and len(out) == 4 and len(out[3]) > 0):
+            raise ValueError("GraphedTrainStep(keep_outputs=True): the model's training forward must return (xHat, yHat, codes, logits)")
+        self.outputs = (out[0].detach(), [c.detach() for c in out[2]], out[3][0].detach())
+
+    @torch.no_grad()
+    def snapshot(self, snap) -> dict:
+        """The log payload of the LAST replay (`monitor.StepSnapshot.read()`'s dict) from the step's static input and outputs: `snap`'s
+        launches go to the current stream, behind the replay, when the host wants one (the reference: every `ValFreq // 10` steps);
+        nothing of it is in the captured graphs.  Needs `keep_outputs=True`."""
+        if self.closed:
+            raise RuntimeError("GraphedTrainStep: the step was closed; build a new one")
+        if self.outputs is None:
+            raise RuntimeError("GraphedTrainStep.snapshot: build the step with `keep_outputs=True` (the captured forward pass frees its "
+                               "reconstruction, codes and logits otherwise)")
+        xHat, codes, logits0 = self.outputs
+        snap.capture(self.x, xHat, codes, logits0)
+        return snap.read()
 
     def _post(self):
         if self.world > 1:
