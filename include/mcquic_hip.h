@@ -467,6 +467,24 @@ int mcq_clip_by_norm_f32(float* x, const float* sumsq, float max_norm, float eps
 int mcq_gather_flat_f32(const void* src_ptrs, float* flat, const int64_t* dst_offsets, const int64_t* numel, const int32_t* blk_tensor,
                         const int64_t* blk_first, int32_t nblocks, void* stream);
 
+/* Gradient accumulation over the k micro-steps of one update (parallel.GraphedTrainStep(accumulate=k)).  `phase` is ONE device
+ * int32 the host sets between launches (0 .. k-1): the same captured launch serves every micro-step.
+ *   mcq_gather_accum_flat_f32  mcq_gather_flat_f32's tables and walk; per element, in float32 and in this order:
+ *                                phase 0            flat = src
+ *                                0 < phase < k-1    flat = flat + src
+ *                                phase = k-1        flat = (flat + src) * (1.0f / k)      (one add, then one multiply)
+ *                              so that k launches leave (((g0 + g1) + ...) + g_{k-1}) * fl(1 / k).  The slices are only 4-byte
+ *                              aligned: 128-bit accesses between a scalar head and tail.  k < 2 is MCQ_EINVAL (mcq_gather_flat_f32
+ *                              is the copy).  A phase outside 0 .. k-1 is taken as the nearer end.
+ *   mcq_accum_step_scalars     the step's scalars by the same phases in one launch: counts_acc[i] = counts[i] at phase 0 and
+ *                              += counts[i] afterwards (n int64 code counts: exact), and loss_acc[0] from loss[0] by the rule above
+ *                              (the mean of the k micro losses after the last phase).  Either pair may be NULL (with n = 0 for
+ *                              the counts), not both. */
+int mcq_gather_accum_flat_f32(const void* src_ptrs, float* flat, const int64_t* dst_offsets, const int64_t* numel, const int32_t* blk_tensor,
+                              const int64_t* blk_first, int32_t nblocks, const int32_t* phase, int32_t k, void* stream);
+int mcq_accum_step_scalars(const int64_t* counts, int64_t* counts_acc, int64_t n, const float* loss, float* loss_acc, const int32_t* phase,
+                           int32_t k, void* stream);
+
 /* Adam / AdamW over a whole model in ONE launch (the `self._optimizer.step()` of mcquic/train/trainer.py:283 with the reference's
  * `Adam`, configs/a800_8.yaml:20-25; arithmetic of torch.optim.Adam / AdamW: lerp of exp_avg, mul + addcmul of exp_avg_sq, bias
  * corrections from the step count, param -= lr / bc1 * exp_avg / (sqrt(exp_avg_sq) / sqrt(bc2) + eps); L2 or decoupled decay).

@@ -694,6 +694,93 @@ extern "C" int mcq_gather_flat_f32(const void* src_ptrs, float* flat, const int6
     return mcq_check_launch();
 }
 
+// ---- gradient accumulation over the k micro-steps of one update (parallel.GraphedTrainStep(accumulate=k)) --------------------------------
+// One element of micro-step `phase`, in float32 and in this order: the first overwrites, the later ones add, the last one also
+// scales -- ((g0 + g1) + ... + g_{k-1}) * fl(1 / k), one add and then one multiply (the library is built with -ffp-contract=off, and
+// (d + s) * c has no fused form anyway).
+__device__ __forceinline__ float accum_rule(float d, float s, bool first, bool last, float inv_k) {
+    const float r = first ? s : d + s;
+    return last ? r * inv_k : r;
+}
+
+// gather_flat_kernel's walk (workgroup b owns chunk b of the tables), accumulating: read src and, past phase 0, dst; write dst.  A
+// tensor's slice of the flat buffer is only 4-byte aligned (the slices are densely packed), and every chunk of a tensor starts a
+// multiple of MCQ_LIST_CHUNK floats behind it: up to three scalar elements bring dst to 16 bytes, the body moves dst as float4 (src too
+// where it is 16-byte aligned at the same element, else as four dwords), up to three scalar elements finish.  `phase` is one word
+// the host sets between replays: it is the same in every lane, so every branch on it is wave-uniform.
+__global__ __launch_bounds__(256) void gather_accum_flat_kernel(const unsigned long long* __restrict__ src_ptrs, float* __restrict__ flat,
+                                                                const long long* __restrict__ dst_off, McqChunkTable chunks,
+                                                                const int* __restrict__ phase, int k, float inv_k) {
+    const McqChunk c = chunks.chunk();
+    const int ph = *phase;
+    const bool first = ph <= 0, last = ph >= k - 1;
+    const float* __restrict__ src = (const float*)src_ptrs[c.t] + c.first;
+    float* __restrict__ dst = flat + dst_off[c.t] + c.first;
+    const int n = (int)(c.end - c.first);                    // <= MCQ_LIST_CHUNK
+    int head = (int)((4 - (((unsigned long long)dst >> 2) & 3)) & 3);
+    if (head > n) head = n;
+    const int nvec = (n - head) >> 2, tail0 = head + 4 * nvec;
+    const int tid = (int)threadIdx.x;
+    if (tid < head) dst[tid] = accum_rule(first ? 0.0f : dst[tid], src[tid], first, last, inv_k);
+    if (tail0 + tid < n) dst[tail0 + tid] = accum_rule(first ? 0.0f : dst[tail0 + tid], src[tail0 + tid], first, last, inv_k);
+    float4* __restrict__ dv = (float4*)(dst + head);
+    const float* __restrict__ sb = src + head;
+    const bool src16 = (((unsigned long long)sb) & 15) == 0;
+    static_assert(MCQ_LIST_CHUNK == 4 * 4 * 256, "a lane owns at most four float4 of a chunk");
+    float4 s[4], d[4];                                       // every load of the lane in flight before the first store
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int v = tid + 256 * u;
+        d[u] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (v < nvec) {
+            if (src16) s[u] = ((const float4*)sb)[v];
+            else s[u] = make_float4(sb[4 * v], sb[4 * v + 1], sb[4 * v + 2], sb[4 * v + 3]);
+            if (!first) d[u] = dv[v];
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int v = tid + 256 * u;
+        if (v < nvec)
+            dv[v] = make_float4(accum_rule(d[u].x, s[u].x, first, last, inv_k), accum_rule(d[u].y, s[u].y, first, last, inv_k),
+                                accum_rule(d[u].z, s[u].z, first, last, inv_k), accum_rule(d[u].w, s[u].w, first, last, inv_k));
+    }
+}
+
+// the step's scalars by the same phases: the int64 code counts of this micro-step into the step's accumulator (exact sums), and the
+// micro-step's loss into the loss the step returns (accum_rule: the mean of the k losses after the last one)
+__global__ __launch_bounds__(256) void accum_step_scalars_kernel(const long long* __restrict__ counts, long long* __restrict__ counts_acc,
+                                                                 long long n, const float* __restrict__ loss, float* __restrict__ loss_acc,
+                                                                 const int* __restrict__ phase, int k, float inv_k) {
+    const int ph = *phase;
+    const bool first = ph <= 0, last = ph >= k - 1;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < n; i += gridDim.x * 256ll)
+        counts_acc[i] = first ? counts[i] : counts_acc[i] + counts[i];
+    if (loss && blockIdx.x == 0 && threadIdx.x == 0) *loss_acc = accum_rule(first ? 0.0f : *loss_acc, *loss, first, last, inv_k);
+}
+
+extern "C" int mcq_gather_accum_flat_f32(const void* src_ptrs, float* flat, const int64_t* dst_offsets, const int64_t* numel,
+                                         const int32_t* blk_tensor, const int64_t* blk_first, int32_t nblocks, const int32_t* phase, int32_t k,
+                                         void* stream) {
+    if (!src_ptrs || !flat || !dst_offsets || !numel || !blk_tensor || !blk_first || nblocks <= 0 || !phase || k < 2) return MCQ_EINVAL;
+    hipLaunchKernelGGL(gather_accum_flat_kernel, dim3((unsigned)nblocks), dim3(256), 0, (hipStream_t)stream, (const unsigned long long*)src_ptrs,
+                       flat, (const long long*)dst_offsets, McqChunkTable{(const long long*)numel, (const int*)blk_tensor, (const long long*)blk_first},
+                       (const int*)phase, (int)k, 1.0f / (float)k);
+    return mcq_check_launch();
+}
+
+extern "C" int mcq_accum_step_scalars(const int64_t* counts, int64_t* counts_acc, int64_t n, const float* loss, float* loss_acc,
+                                      const int32_t* phase, int32_t k, void* stream) {
+    const bool has_counts = counts || counts_acc || n != 0, has_loss = loss || loss_acc;
+    if (!phase || k < 2 || !(has_counts || has_loss)) return MCQ_EINVAL;
+    if (has_counts && (!counts || !counts_acc || n <= 0)) return MCQ_EINVAL;
+    if (has_loss && (!loss || !loss_acc)) return MCQ_EINVAL;
+    const int64_t want = (n + 255) / 256;
+    hipLaunchKernelGGL(accum_step_scalars_kernel, dim3((unsigned)(want < 1 ? 1 : want > 1024 ? 1024 : want)), dim3(256), 0, (hipStream_t)stream,
+                       (const long long*)counts, (long long*)counts_acc, (long long)n, loss, loss_acc, (const int*)phase, (int)k, 1.0f / (float)k);
+    return mcq_check_launch();
+}
+
 extern "C" int mcq_silu_f32(const float* x, float* y, int64_t n, void* stream) {
     if (!x || !y || n <= 0) return MCQ_EINVAL;
     hipLaunchKernelGGL(silu_fwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, y, n);

@@ -1155,6 +1155,50 @@ def clip_by_norm_(x: torch.Tensor, max_norm: float, eps: float = 1e-6, sq: Optio
     return norm
 
 
+def _phase_word(phase: torch.Tensor, k: int, what: str) -> torch.Tensor:
+    if not isinstance(k, int) or isinstance(k, bool) or k < 2:
+        raise ValueError(f"{what}: k must be an int >= 2 (one micro-step is the plain copy)")
+    phase = _dev(phase, "phase", torch.int32)
+    if phase.numel() != 1:
+        raise ValueError(f"{what}: `phase` is one int32 on the device")
+    return phase
+
+
+def gather_accum_flat_(ptrs: torch.Tensor, flat: torch.Tensor, offsets: torch.Tensor, table, phase: torch.Tensor, k: int) -> None:
+    """Micro-step `phase` of k into `flat` (mcq_gather_accum_flat_f32): per element flat = src at phase 0, flat + src afterwards, and
+    (flat + src) * float32(1 / k) at phase k - 1, all in float32.  `ptrs` / `offsets`: int64 device arrays of the sources' addresses and
+    of their offsets into `flat` (floats); `table`: their `tensor_list.ChunkTable`; `phase`: one device int32, read by the launch."""
+    phase = _phase_word(phase, k, "gather_accum_flat_")
+    if not flat.is_contiguous():
+        raise ValueError("gather_accum_flat_: needs a contiguous buffer (it is accumulated in place)")
+    flat = _dev(flat, "flat")
+    ptrs, offsets = _dev(ptrs, "ptrs", torch.int64), _dev(offsets, "offsets", torch.int64)
+    with _guard(flat.device):
+        check(_lib.load().mcq_gather_accum_flat_f32(_ptr(ptrs), _ptr(flat), _ptr(offsets), _ptr(table.numel), _ptr(table.blk_tensor),
+                                                    _ptr(table.blk_first), table.nblocks, _ptr(phase), k, _stream()), "mcq_gather_accum_flat_f32")
+
+
+def accum_step_scalars_(counts: Optional[torch.Tensor], counts_acc: Optional[torch.Tensor], loss: Optional[torch.Tensor],
+                        loss_acc: Optional[torch.Tensor], phase: torch.Tensor, k: int) -> None:
+    """The scalars of micro-step `phase` of k in one launch (mcq_accum_step_scalars): the int64 code counts into `counts_acc` (overwritten
+    at phase 0, added to afterwards: exact), the 0-dim float32 `loss` into `loss_acc` by `gather_accum_flat_`'s rule (the mean of the k
+    losses after the last phase).  Either pair may be None."""
+    phase = _phase_word(phase, k, "accum_step_scalars_")
+    n = 0
+    if counts is not None or counts_acc is not None:
+        if counts is None or counts_acc is None or counts.numel() != counts_acc.numel() or counts.numel() == 0 or not counts_acc.is_contiguous():
+            raise ValueError("accum_step_scalars_: `counts` and the contiguous `counts_acc` hold the same number of entries (not none)")
+        counts, counts_acc = _dev(counts, "counts", torch.int64), _dev(counts_acc, "counts_acc", torch.int64)
+        n = counts.numel()
+    if loss is not None or loss_acc is not None:
+        if loss is None or loss_acc is None or loss.numel() != 1 or loss_acc.numel() != 1:
+            raise ValueError("accum_step_scalars_: `loss` and `loss_acc` hold one float32 each")
+        loss, loss_acc = _dev(loss, "loss"), _dev(loss_acc, "loss_acc")
+    with _guard(phase.device):
+        check(_lib.load().mcq_accum_step_scalars(_ptr(counts), _ptr(counts_acc), n, _ptr(loss), _ptr(loss_acc), _ptr(phase), k, _stream()),
+              "mcq_accum_step_scalars")
+
+
 def group_norm(x: torch.Tensor, weight: Optional[torch.Tensor], bias: Optional[torch.Tensor], groups: int, eps: float = 1e-5,
                dual_silu: bool = False, want_stats: bool = False):
     """nn.GroupNorm(groups, C) on [n, C, h, w] (mcq_group_norm_f32; `denseNorm=True`, mcquic/nn/blocks.py:179-200).

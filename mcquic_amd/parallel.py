@@ -299,14 +299,32 @@ class GraphedTrainStep:
     `keep_outputs=True` keeps references to the reconstruction, the codes and the level-0 logits of the captured forward pass (`step.outputs`;
     the graph's pool is larger by the logits, no launch is added), so that `step.snapshot(snap)` can make the reference trainer's periodic log
     payload (`monitor.StepSnapshot`) of the last replay whenever the host wants one, outside the graphs.
+    `accumulate=k` (an int >= 1, `step.accumulate`): gradient accumulation -- one call consumes k micro-batches and makes ONE update, so the
+    reference's effective batch (`batchSize` x its 8+ GPUs, which `totalStep` and the schedules are written for) is reached on fewer GPUs
+    without a larger capture.  `example_x` stays ONE micro-batch [n, ...]; `step(x)` takes [k n, ...] (raw with a `transform`), micro-batch j
+    being x[j n: (j + 1) n].  The SAME segment graphs are replayed k times -- captured memory does not grow with k --: before each replay
+    the host enqueues the copy of the micro-batch and of j into a device phase word (from a pinned [0 .. k-1] array; no host read, no
+    synchronisation), and two launches read it: the gather into the flat buffer accumulates (`mcq_gather_accum_flat_f32`: per element, in
+    float32, g0, then + g_j in order, then * float32(1 / k) inside the last micro-step -- (((g0 + g1) + ...) + g_{k-1}) * fl(1 / k)), and one
+    launch at the end of the first segment (`mcq_accum_step_scalars`) adds the code counts into an int64 accumulator of the step's
+    (`step.counts`: the SUM over the micro-batches, what the frequency EMA and the meter get) and forms `step.loss`, the mean of the k micro
+    losses by the same rule.  Nothing is exchanged before the last micro-step: there the slices and the counts are all-reduced as ever
+    (overlapped segment by segment), then `/ world` and the update ONCE -- clip, guard, optimizer, `ema`, frequency EMA, `scheduler`, `meter`
+    see the accumulated, averaged gradient; a NaN of any micro-batch survives the sum, so the guard skips the whole update.  The frequency EMA
+    does not move between micro-steps: all k forwards draw `_randomDrop` from the same table, as one large batch would; a `transform` draws
+    fresh decisions in every replay.  `step.outputs` / `step.snapshot(snap)` describe the LAST micro-batch; the meter's `pixels` is the
+    caller's and per update: k n H W.  With accumulate=1 not one launch or buffer changes (`step.counts` is the coder's sink itself).
     """
 
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
                  broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None, scheduler=None,
-                 skip_nonfinite: bool = False, keep_outputs: bool = False):
+                 skip_nonfinite: bool = False, keep_outputs: bool = False, accumulate: int = 1):
         if not example_x.is_cuda:
             raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
+        if not isinstance(accumulate, int) or isinstance(accumulate, bool) or accumulate < 1:
+            raise ValueError(f"accumulate must be an int >= 1 (micro-batches per update), got {accumulate!r}")
+        self.accumulate = accumulate
         self.model, self.optimizer, self.group, self.ema, self.meter = model, optimizer, group, ema, meter
         if scheduler is not None and getattr(scheduler, "optimizer", None) is not optimizer:
             raise ValueError("GraphedTrainStep: `scheduler` steps another optimizer's learning rates than `optimizer`'s")
@@ -405,6 +423,7 @@ class GraphedTrainStep:
                 self.slices.append(self.flat[off: off + n])
                 off += n
             self._gather_tables()
+            self._accum_buffers()
             self._init_optimizer_state()
             torch.cuda.synchronize()
             with torch.no_grad():
@@ -424,6 +443,8 @@ class GraphedTrainStep:
                         sinks = [c.countSink() for c in self.coders]
                         # (one coder per model: its count buffer itself -- the sampling kernels add into it, nothing is copied)
                         self.counts = (sinks[0] if len(sinks) == 1 else torch.cat(sinks)) if sinks else None
+                        if self.accumulate > 1:
+                            self._accum_scalars()
                 self.graphs.append(g)
             self.graph = self.graphs[0]
             self._carry = None                               # (the autograd graph between segments: only needed while capturing)
@@ -487,9 +508,38 @@ class GraphedTrainStep:
         self._gatherGrads[k] = grads                          # (alive as long as the tables point at them)
         host.copy_(torch.tensor([g.data_ptr() for g in grads], dtype=torch.int64))
         ptrs.copy_(host, non_blocking=True)                   # (a copy NODE inside the capture: re-read from the pinned tensor on every replay)
+        if self.accumulate > 1:                               # the same tables, accumulating by the phase word (mcq_gather_accum_flat_f32)
+            from . import ops
+            ops.gather_accum_flat_(ptrs, self.slices[k], offs, table, self._phase, self.accumulate)
+            return
         with _guard(dev):
             check(lib.mcq_gather_flat_f32(ptrs.data_ptr(), self.slices[k].data_ptr(), offs.data_ptr(), table.numel.data_ptr(),
                                           table.blk_tensor.data_ptr(), table.blk_first.data_ptr(), table.nblocks, _stream()), "mcq_gather_flat_f32")
+
+    def _accum_buffers(self):
+        """With `accumulate` > 1, OUTSIDE the captures and alive as long as the step: the device phase word the accumulating launches
+        read, the pinned [0 .. k-1] array the host copies it from before every replay, the int64 accumulator of the code counts (as long
+        as the coders' sinks together) and the float32 accumulator of the loss.  With accumulate=1 nothing is made."""
+        self._phase = self._phaseHost = self._countsAcc = self._lossAcc = None
+        if self.accumulate == 1:
+            return
+        dev = self.flat.device
+        self._phase = torch.zeros(1, dtype=torch.int32, device=dev)
+        self._phaseHost = torch.arange(self.accumulate, dtype=torch.int32).pin_memory()
+        n = sum(c.countSink().numel() for c in self.coders)
+        self._countsAcc = torch.zeros(n, dtype=torch.int64, device=dev) if n else None
+        self._lossAcc = torch.zeros((), dtype=torch.float32, device=dev)
+
+    def _accum_scalars(self):
+        """The last launch of segment 0's capture with `accumulate` > 1 (mcq_accum_step_scalars): this micro-step's counts (`self.counts`:
+        the sink the prologue zeroes on every replay) into the step's accumulator and its loss into the mean; from here on `self.counts`
+        and `self.loss` ARE the accumulators -- what the all-reduce, `applyCounts`, the meter and the caller read."""
+        from . import ops
+        if not (torch.is_tensor(self.loss) and self.loss.dtype == torch.float32 and self.loss.numel() == 1):
+            raise ValueError("GraphedTrainStep(accumulate > 1): the loss must be one float32 on the device (its mean over the micro-batches is "
+                             "formed by a kernel)")
+        ops.accum_step_scalars_(self.counts, self._countsAcc, self.loss, self._lossAcc, self._phase, self.accumulate)
+        self.counts, self.loss = self._countsAcc, self._lossAcc
 
     def _gather_tables(self):
         """The static side of `_gather`, built OUTSIDE the captures (host-to-device copies from pageable memory invalidate a capture): per
@@ -756,13 +806,25 @@ class GraphedTrainStep:
             raise RuntimeError("GraphedTrainStep: the EMA's averaged weights are swapped in (`ema.applied()` / `ema.swap()`); training would "
                                "update the average as if it were the iterate -- swap back first")
         static = self.x if self.raw is None else self.raw
-        if tuple(x.shape) != tuple(static.shape):             # (`copy_` would BROADCAST a smaller batch into the static input silently)
-            raise RuntimeError(f"GraphedTrainStep was captured for shards of shape {tuple(static.shape)}, got {tuple(x.shape)}")
+        acc, n = self.accumulate, static.shape[0]
+        if tuple(x.shape) != (acc * n,) + tuple(static.shape[1:]):     # (`copy_` would BROADCAST a smaller batch into the static input silently)
+            raise RuntimeError(f"GraphedTrainStep was captured for shards of shape {tuple(static.shape)}" +
+                               (f" and accumulate={acc} (k = {acc} of them per call: {(acc * n,) + tuple(static.shape[1:])})" if acc > 1 else "") +
+                               f", got {tuple(x.shape)}")
         if self.raw is not None and x.dtype != static.dtype:  # (`copy_` would convert a uint8 batch to float without the / 255)
             raise RuntimeError(f"GraphedTrainStep was captured for {static.dtype} shards, got {x.dtype}")
-        static.copy_(x, non_blocking=True)
+        for j in range(acc - 1):                              # micro-steps 0 .. k-2: accumulate, exchange nothing
+            static.copy_(x[j * n: (j + 1) * n], non_blocking=True)
+            self._phase.copy_(self._phaseHost[j: j + 1], non_blocking=True)     # (stream-ordered like the input's copy: no host read, no sync)
+            for g in self.graphs:
+                g.replay()
+        if acc > 1:
+            static.copy_(x[(acc - 1) * n:], non_blocking=True)
+            self._phase.copy_(self._phaseHost[acc - 1:], non_blocking=True)
+        else:
+            static.copy_(x, non_blocking=True)
         works = []
-        for k, g in enumerate(self.graphs):
+        for k, g in enumerate(self.graphs):                   # the last (or only) micro-step: the buffers hold the mean / the summed counts
             g.replay()
             if self.world > 1:
                 works.append(self._start_all_reduce(self.slices[k]))       # ... while the next segment replays

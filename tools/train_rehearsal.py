@@ -6,7 +6,7 @@ validation, codebook re-assignment, mcquic/train/hooks.py:100-121) over syntheti
 eager encode / decode, `reAssignCodebook`, finiteness checks -- the work that exposed the memset-node defect (docs/experiments.md
 section 9.9).  Prints one JSON line: loss trace, validation PSNR trace, gradient norms, step time.
 
-    python tools/train_rehearsal.py [--steps 600] [--channel 128] [--batch 8] [--crop 256] [--out profiles/r04_train_rehearsal.json]
+    python tools/train_rehearsal.py [--steps 600] [--channel 128] [--batch 8] [--accumulate 1] [--crop 256] [--out profiles/r04_train_rehearsal.json]
 """
 import argparse
 import json
@@ -66,6 +66,8 @@ def main():
                          "mcquic_amd.schedule.CosineAnnealingWarmupRestarts(first_cycle_steps=--steps, warmup_steps=--warmup, lrScaleRatio=0.0) -- the "
                          "reference's configs/a800_8.yaml shape -- stepped on the device inside the post graph.  cosine-host: the same rates "
                          "computed and filled in by the host before every replay: what `cosine` is measured against")
+    ap.add_argument("--accumulate", type=int, default=1, metavar="K", help="gradient accumulation: every call takes K micro-batches of --batch images and makes "
+                                                                           "ONE update (GraphedTrainStep(accumulate=K)); ms_per_step is then the time of a call")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
     from mcquic_amd import Compressor, parallel
@@ -114,7 +116,8 @@ def main():
         if sic < args.warmup:
             return base_rate * sic / args.warmup
         return base_rate * (1 + math.cos(math.pi * (sic - args.warmup) / (args.steps - args.warmup))) / 2
-    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if (args.lamb or args.own_sgd) else 4.0, ema=ema, scheduler=sched)
+    step = parallel.GraphedTrainStep(model, opt, x, max_grad_norm=None if (args.lamb or args.own_sgd) else 4.0, ema=ema, scheduler=sched,
+                                     accumulate=args.accumulate)
     trace = {"loss": [], "grad_norm": [], "psnr": [], "reassigned": [], "non_finite": 0}
     if ema is not None:
         trace["psnr_ema"] = []
@@ -131,7 +134,7 @@ def main():
     torch.cuda.synchronize()
     t_steps = 0.0
     for i in range(1, args.steps + 1):
-        x = images(args.batch, args.crop, gen, dev)
+        x = images(args.batch * args.accumulate, args.crop, gen, dev)
         if args.schedule == "cosine-host":
             lr.fill_(cosine_rate(i - 1))
         elif args.schedule == "warmup" and args.warmup:
@@ -163,7 +166,7 @@ def main():
     out = {"what": "GraphedTrainStep(Adam, lr in a device tensor, max_grad_norm=4.0) on fresh synthetic batches; loss.item() every step; every "
                    f"{args.every} steps: finiteness of all parameters, eager encode/decode PSNR on 4 held-out images, codebook re-assignment every {2 * args.every}",
            "model": f"Compressor({args.channel}, {args.m}, {ks})", "lr": args.lr, "lr_warmup_steps": args.warmup, "schedule": args.schedule,
-           **({"last_lr": sched.get_last_lr()[0], "last_epoch": sched.last_epoch} if sched is not None else {"last_lr": float(lr)} if torch.is_tensor(lr) else {}), "optimizer": "mcquic_amd.optim.Lamb(max_grad_norm=4.0), no clipping in the step" if args.lamb else "mcquic_amd.optim.Adam" if args.own_adam else "mcquic_amd.optim.SGD(momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True), no clipping in the step" if args.own_sgd else "torch SGD(momentum=0.9) foreach" if args.sgd else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "crop": args.crop, "steps": args.steps,
+           **({"last_lr": sched.get_last_lr()[0], "last_epoch": sched.last_epoch} if sched is not None else {"last_lr": float(lr)} if torch.is_tensor(lr) else {}), "optimizer": "mcquic_amd.optim.Lamb(max_grad_norm=4.0), no clipping in the step" if args.lamb else "mcquic_amd.optim.Adam" if args.own_adam else "mcquic_amd.optim.SGD(momentum=0.9, max_grad_norm=4.0, skip_nonfinite=True), no clipping in the step" if args.own_sgd else "torch SGD(momentum=0.9) foreach" if args.sgd else ("torch Adam fused" if args.fused else "torch Adam foreach"), "post_captured": step.post is not None, "batch": args.batch, "accumulate": args.accumulate, "crop": args.crop, "steps": args.steps,
            "ms_per_step": round(t_steps / args.steps * 1e3, 3), "loss_first": round(first, 6), "loss_last": round(last, 6),
            "psnr_first": trace["psnr"][0][1], "psnr_last": trace["psnr"][-1][1], "memset_nodes_ok": parallel.memset_nodes_replay_correctly(dev), "memory": mem,
            **({"skipped": int(opt.skipped)} if args.own_sgd else {}),
