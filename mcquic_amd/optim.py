@@ -124,8 +124,17 @@ class _Planned(torch.optim.Optimizer):
         `parallel.GraphedTrainStep` calls before it captures `step()` (table uploads are host-to-device copies)."""
         self._planned()
 
-    def _wants_norm(self) -> bool:
-        return False
+    # ---- what a training step asks (parallel.GraphedTrainStep) ---------------------------------------------------------------------
+    guards_itself = property(lambda self: self._guard_own, doc="Its own `skip_nonfinite` is on: a step's guard beside it is refused.")
+    lends_norm = False                                        # it computes the norm of all gradients: a guard borrows the partials
+
+    def last_grad_norm(self):
+        """The device tensor that holds G of the last step, or None (no step yet, or an optimizer that computes none)."""
+        return self._norm[2] if self.lends_norm and self._norm is not None else None
+
+    def skip_count(self):
+        """`skipped` where the optimizer has the counter (its own `skip_nonfinite`; SGD always), else None."""
+        return self.skipped if self._guard_own else None
 
     # ---- the non-finite guard ----------------------------------------------------------------------------------------------------
     def attach_guard(self, guard, decided: bool = False) -> None:
@@ -133,7 +142,7 @@ class _Planned(torch.optim.Optimizer):
         the guard itself before each `step()` (over the flat gradient buffer, or from its clipping's norm); otherwise `step()` runs it --
         from the partials of the gradient norm where this optimizer computes them (Lamb; SGD with `max_grad_norm`), else over its own
         gradient tables.  Refused beside the optimizer's own `skip_nonfinite`: two guards would count one step twice."""
-        if guard is not None and (self._guard_own or getattr(self, "skip_nonfinite", False)):
+        if guard is not None and self.guards_itself:
             raise ValueError(f"mcquic_amd.optim.{self._NAME}: both the step and the optimizer guard against a non-finite gradient "
                              "(`skip_nonfinite`): one step would be counted twice; set one of them")
         self._guard, self._guard_decided = guard, bool(decided) and guard is not None
@@ -174,13 +183,13 @@ class _Planned(torch.optim.Optimizer):
         return self._guard.skipped
 
     def _planned(self):
-        """[(group, plan)] of the groups that hold gradients, tables current, and -- for an optimizer that `_wants_norm()` -- the buffers
+        """[(group, plan)] of the groups that hold gradients, tables current, and -- for an optimizer that `lends_norm` -- the buffers
         of the gradient norm they share: `self._norm` = (key, double partials of sum g^2 for all groups, G)."""
         live = []
         for gi, group in enumerate(self.param_groups):
             params = self._checked(group)
             if params:
-                if live and self._wants_norm() and params[0].device != live[0][2][0].device:
+                if live and self.lends_norm and params[0].device != live[0][2][0].device:
                     raise RuntimeError(f"mcquic_amd.optim.{self._NAME}: all param groups must live on one device (the gradient norm spans them)")
                 live.append((gi, group, params))
         out = []
@@ -189,7 +198,7 @@ class _Planned(torch.optim.Optimizer):
             plan.table.fill(params, [p.grad for p in params])
             out.append((group, plan))
         key = tuple((id(plan), plan.nblocks) for _, plan in out)
-        if out and self._wants_norm() and (self._norm is None or self._norm[0] != key):
+        if out and self.lends_norm and (self._norm is None or self._norm[0] != key):
             dev = out[0][1].step.device
             gnorm = self._norm[2] if self._norm is not None and self._norm[2].device == dev else torch.zeros((), dtype=torch.float32, device=dev)
             self._norm = (key, torch.zeros(max(sum(plan.nblocks for _, plan in out), 1), dtype=torch.float64, device=dev), gnorm)
@@ -197,9 +206,9 @@ class _Planned(torch.optim.Optimizer):
         return out
 
     def _grad_partials(self, todo, skip=None):
-        """(partials, total, G) for an optimizer that `_wants_norm()`, (None, 0, None) otherwise: the per-chunk sums of g^2 of every plan of
+        """(partials, total, G) for an optimizer that `lends_norm`, (None, 0, None) otherwise: the per-chunk sums of g^2 of every plan of
         `todo`, one launch each into one array of `total` doubles, from which every group's update derives the same norm G."""
-        if not self._wants_norm():
+        if not self.lends_norm:
             return None, 0, None
         _, partials, gnorm = self._norm
         total = 0
@@ -210,13 +219,18 @@ class _Planned(torch.optim.Optimizer):
                 total += plan.nblocks
         return partials, total, gnorm
 
-    def _last_grad_norm(self):
-        """The device tensor that holds G of the last step, or None (no step yet, or an optimizer that computes none)."""
-        return self._norm[2] if self._wants_norm() and self._norm is not None else None
-
-    def _no_closure(self, closure) -> None:
+    def _begin(self, closure):
+        """The opening every `step()` shares: (todo, partials, total, G, flag) -- the non-empty plans (none: nothing to launch), the norm
+        of ALL gradients first where the optimizer forms one, then ONE decision for all groups before any is updated.  With a guard that
+        has not decided yet the flag comes from those partials (Lamb, SGD: no second pass), else from a pass over the gradient tables."""
         if closure is not None:
             raise NotImplementedError(f"mcquic_amd.optim.{self._NAME}: closures are not supported (the reference's trainer passes none)")
+        todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
+        if not todo:
+            return todo, None, 0, None, None
+        decided = self._guard.skip.data_ptr() if self._guard is not None and self._guard_decided else None
+        partials, total, gnorm = self._grad_partials(todo, decided)
+        return todo, partials, total, gnorm, self._flag(todo, partials, total)
 
     def load_state_dict(self, state_dict):
         """The loaded tensors are copied INTO the existing flat buffers on the next step (same parameters: same addresses, which a
@@ -267,12 +281,8 @@ class Adam(_Planned):
 
     @torch.no_grad()
     def step(self, closure=None):
-        self._no_closure(closure)
+        todo, _, _, _, flag = self._begin(closure)            # (no norm of its own: a guard looks at the gradient tables)
         lib = _lib.load()
-        todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
-        if not todo:
-            return None
-        flag = self._flag(todo)                               # (with a guard: ONE decision for all groups, before any is updated)
         for group, plan in todo:
             lr_dev, lr_host = self._rate(group)
             b1, b2 = group["betas"]
@@ -352,8 +362,7 @@ class Lamb(_Planned):
     def zero_grad(self, set_to_none=None):
         super().zero_grad(self.set_grad_none if set_to_none is None else set_to_none)
 
-    def _wants_norm(self) -> bool:
-        return True
+    lends_norm = True
 
     def _extend_plan(self, plan, dev) -> None:
         plan.table.tensor_first_blk                           # (uploaded now: the first `step()` after `prepare()` may be a captured one)
@@ -378,16 +387,12 @@ class Lamb(_Planned):
 
     @torch.no_grad()
     def step(self, closure=None):
-        self._no_closure(closure)
-        lib = _lib.load()
-        todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
+        todo, partials, total, gnorm, flag = self._begin(closure)       # (with a guard: the flag from the partials of LAMB's own G)
         if not todo:
             return None
-        decided = self._guard.skip.data_ptr() if self._guard is not None and self._guard_decided else None
-        partials, total, gnorm = self._grad_partials(todo, decided)      # the norm of ALL gradients first ...
-        flag = self._flag(todo, partials, total)              # (with a guard: the flag from those partials, LAMB's own G)
+        lib = _lib.load()
         with _guard(gnorm.device):
-            for group, plan in todo:                          # ... then every group's update reads the same partials
+            for group, plan in todo:                          # every group's update reads the same partials
                 lr_dev, lr_host = self._rate(group)
                 b1, b2 = group["betas"]
                 check(lib.mcq_lamb_step_skip_f32(*plan.table.args(first_blk=True), partials.data_ptr(), total, plan.step.data_ptr(),
@@ -461,8 +466,11 @@ class SGD(_Planned):
     def _state_names(self, group) -> tuple:
         return ("momentum_buffer",) if group["momentum"] != 0 else ()
 
-    def _wants_norm(self) -> bool:
-        return self.max_grad_norm is not None or self.skip_nonfinite
+    guards_itself = property(lambda self: self.skip_nonfinite)          # (inside its scalar kernel, with a counter of its own)
+    lends_norm = property(lambda self: self.max_grad_norm is not None or self.skip_nonfinite)
+
+    def skip_count(self):
+        return self.skipped
 
     def _planned(self):
         out = super()._planned()
@@ -476,7 +484,7 @@ class SGD(_Planned):
 
     def grad_norm(self) -> torch.Tensor:
         """G of the last call, skipped or not: the norm of all gradients before clipping (0-dim float32 on the device)."""
-        if not self._wants_norm():
+        if not self.lends_norm:
             raise RuntimeError("mcquic_amd.optim.SGD: the gradient norm is computed only with `max_grad_norm` or `skip_nonfinite`")
         if self._norm is None:
             raise RuntimeError("mcquic_amd.optim.SGD: no step has run yet")
@@ -492,14 +500,9 @@ class SGD(_Planned):
 
     @torch.no_grad()
     def step(self, closure=None):
-        self._no_closure(closure)
+        # (the norm with clipping or a guard only; the flag is a step's guard's, `attach_guard`: SGD's own lives in its scalar kernel)
+        todo, partials, total, gnorm, flag = self._begin(closure)
         lib = _lib.load()
-        todo = [(group, plan) for group, plan in self._planned() if plan.nblocks > 0]
-        if not todo:
-            return None
-        decided = self._guard.skip.data_ptr() if self._guard is not None and self._guard_decided else None
-        partials, total, gnorm = self._grad_partials(todo, decided)      # with clipping or the guard: the norm of ALL gradients first
-        flag = self._flag(todo, partials, total)              # (a step's guard, `attach_guard`; SGD's own lives in its scalar kernel)
         for i, (group, plan) in enumerate(todo):              # (every group derives the same factor and flag; the first one counts a skip)
             lr_dev, lr_host = self._rate(group)
             with _guard(plan.step.device):

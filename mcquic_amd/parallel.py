@@ -320,26 +320,65 @@ class GraphedTrainStep:
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
                  broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None, scheduler=None,
                  skip_nonfinite: bool = False, keep_outputs: bool = False, accumulate: int = 1):
-        if not example_x.is_cuda:
-            raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
-        if not isinstance(accumulate, int) or isinstance(accumulate, bool) or accumulate < 1:
-            raise ValueError(f"accumulate must be an int >= 1 (micro-batches per update), got {accumulate!r}")
-        self.accumulate = accumulate
-        self.model, self.optimizer, self.group, self.ema, self.meter = model, optimizer, group, ema, meter
-        if scheduler is not None and getattr(scheduler, "optimizer", None) is not optimizer:
-            raise ValueError("GraphedTrainStep: `scheduler` steps another optimizer's learning rates than `optimizer`'s")
-        self.scheduler = scheduler
+        self.model, self.optimizer, self.group, self.ema, self.meter, self.scheduler = model, optimizer, group, ema, meter, scheduler
+        self.accumulate, self.max_grad_norm, self.kwargs = accumulate, max_grad_norm, dict(forward_kwargs or {})
         self.keep_outputs, self.outputs = bool(keep_outputs), None      # (xHat, codes, level-0 logits) of the last replay, for `snapshot`
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
-        self.x = example_x.detach().clone()
-        self.transform, self.raw = transform, None
-        if transform is not None:                             # the static input holds RAW images; the transform's two launches write self.x
-            self.raw = self.x
-            self.transform = transform.to(self.raw.device)    # (its generator state and gain table: on the device before any capture)
-            with torch.no_grad():
-                self.x = self.transform(self.raw).detach()
-        self.kwargs = dict(forward_kwargs or {})
-        staged = all(hasattr(model, a) for a in ("_encoder", "_quantizer", "_decoder", "_repackStale")) and set(self.kwargs) <= {"uniforms"}
+        self.grad_norm = None                                 # 0-dim device tensor: the global gradient norm of the last step, before clipping
+        self._check_arguments(example_x, loss_fn, segments, skip_nonfinite)
+        self._static_input(example_x, transform)
+        self.loss_fn = loss_fn or _default_loss
+        self.params = [p for p in model.parameters() if p.requires_grad]
+        self.coders = [m for m in model.modules() if hasattr(m, "deferCounts")]
+        self.closed = False
+        if self.world > 1 and broadcast:
+            self._broadcast_state()
+        model.train()
+        for c in self.coders:
+            c.deferCounts(True)
+        # (under a process group RCCL's watchdog thread may query events while we capture: thread-local mode keeps a capture from
+        #  being invalidated by what OTHER threads do; the autograd thread's launches are captured either way -- capture follows
+        #  the stream, not the thread)
+        self._mode = dict(capture_error_mode="thread_local") if (dist.is_available() and dist.is_initialized()) else {}
+        # warm-up and capture share ONE side stream: autograd's gradient accumulators remember the stream they were created on, and
+        # a capture on another stream would pull that one (the legacy default stream, if the warm-up ran there) into the graph
+        self._stream = torch.cuda.Stream(self.x.device)
+        self._stream.wait_stream(torch.cuda.current_stream(self.x.device))
+        from .nn import blocks
+        streams, blocks._BRANCH_STREAMS = blocks._BRANCH_STREAMS, False     # nested stream forks crash hipGraph capture (ROCm 7.2): one stream
+        try:
+            self._warm_segments(warmup)                       # inside: the warm-up runs (and traces) the single-stream launches the capture records
+            pinned = self._pin_operand_streams()              # inside: sets `_packMasks`, which the captured re-pack reads
+            # inside because they lie between the two: they need the warm-up's gradients, and the captures need them; a failure of any
+            # of them hands the coders back to the eager update like a failed capture
+            self._flat_layout()
+            self._gather_tables()
+            self._accum_buffers()
+            self._init_optimizer_state()
+            self._capture_segments()                          # inside: one stream, and the re-pack masks
+        except BaseException:
+            for c in self.coders:
+                c.deferCounts(False)
+            raise
+        finally:
+            model.__dict__.pop("_packMasks", None)
+            blocks._BRANCH_STREAMS = streams
+        self._pinned = pinned + [c.countSink() for c in self.coders]     # (what the graphs hold addresses of: alive as long as the step)
+        self._bind_grads()
+        self._prepare_update()
+        self._capture_post(capture_post)
+
+    # ---- the constructor's phases, in its order ------------------------------------------------------------------------------
+    def _check_arguments(self, example_x, loss_fn, segments, skip_nonfinite):
+        """Every refusal of the constructor, before anything is built; leaves `self.segments` and `self.guard`."""
+        optimizer, max_grad_norm = self.optimizer, self.max_grad_norm
+        if not example_x.is_cuda:
+            raise RuntimeError("GraphedTrainStep needs a HIP device (hipGraph capture)")
+        if not isinstance(self.accumulate, int) or isinstance(self.accumulate, bool) or self.accumulate < 1:
+            raise ValueError(f"accumulate must be an int >= 1 (micro-batches per update), got {self.accumulate!r}")
+        if self.scheduler is not None and getattr(self.scheduler, "optimizer", None) is not optimizer:
+            raise ValueError("GraphedTrainStep: `scheduler` steps another optimizer's learning rates than `optimizer`'s")
+        staged = all(hasattr(self.model, a) for a in ("_encoder", "_quantizer", "_decoder", "_repackStale")) and set(self.kwargs) <= {"uniforms"}
         if segments is None:
             segments = 3 if (self.world > 1 and staged) else 1
         if segments not in (1, 3):
@@ -354,145 +393,146 @@ class GraphedTrainStep:
             raise ValueError("max_grad_norm must be positive (or None: no clipping)")
         if max_grad_norm is not None and getattr(optimizer, "max_grad_norm", None) is not None:
             raise ValueError("both the step and the optimizer clip (`max_grad_norm`): the gradient would be scaled twice; set one of them")
-        self.max_grad_norm = max_grad_norm
         self.guard = None                                     # guard.StepGuard with `skip_nonfinite`: the flag every launch of the update obeys
         if skip_nonfinite:
-            if not hasattr(optimizer, "attach_guard"):
+            if not self._own_optimizer():
                 raise ValueError("skip_nonfinite needs an optimizer whose kernels take the guard's flag (mcquic_amd.optim.Adam / AdamW / Lamb / "
                                  f"SGD); {type(optimizer).__module__}.{type(optimizer).__name__} would update through a skipped step")
-            if getattr(optimizer, "_guard_own", False) or getattr(optimizer, "skip_nonfinite", False):
+            if optimizer.guards_itself:
                 raise ValueError("both the step and the optimizer guard against a non-finite gradient (`skip_nonfinite`): one step would be "
                                  "counted twice; set one of them")
             from .guard import StepGuard
             self.guard = StepGuard(example_x.device)
-        self.grad_norm = None                                 # 0-dim device tensor: the global gradient norm of the last step, before clipping
         if loss_fn is not None and not memset_nodes_replay_correctly(example_x.device):
             import warnings
             warnings.warn("this process replays memset nodes of captured hipGraphs wrongly (ROCm 7.2; DEBUG_CLR_GRAPH_PACKET_CAPTURE=0 was not "
                           "in the environment when the HIP runtime started): a library reduction inside `loss_fn` (x.mean(), x.sum() over "
                           "~1e5+ elements) may return stale values from a replay.  Import mcquic_amd before the first device call, or set the "
-                          "variable yourself.", RuntimeWarning, stacklevel=2)
-        self.loss_fn = loss_fn or _default_loss
-        self.params = [p for p in model.parameters() if p.requires_grad]
-        self.coders = [m for m in model.modules() if hasattr(m, "deferCounts")]
-        self.closed = False
-        if self.world > 1 and broadcast:
-            self._broadcast_state()
-        model.train()
-        for c in self.coders:
-            c.deferCounts(True)
-        from . import ops
-        from .nn import blocks
-        streams = blocks._BRANCH_STREAMS
-        blocks._BRANCH_STREAMS = False                       # nested stream forks crash hipGraph capture (ROCm 7.2): one stream
-        # (under a process group RCCL's watchdog thread may query events while we capture: thread-local mode keeps a capture from
-        #  being invalidated by what OTHER threads do; the autograd thread's launches are captured either way -- capture follows
-        #  the stream, not the thread)
-        mode = dict(capture_error_mode="thread_local") if (dist.is_available() and dist.is_initialized()) else {}
-        # warm-up and capture share ONE side stream: autograd's gradient accumulators remember the stream they were created on, and
-        # a capture on another stream would pull that one (the legacy default stream, if the warm-up ran there) into the graph
-        self._stream = torch.cuda.Stream(self.x.device)
-        self._stream.wait_stream(torch.cuda.current_stream(self.x.device))
-        try:
-            ops.section_trace(True)                          # which copy of its operand stream every conv launch of the step reads
-            try:
-                with torch.cuda.stream(self._stream):
-                    for _ in range(max(1, warmup)):          # caches, workspaces, the coders' count sinks
-                        for k in range(self.segments):
-                            self._segment(k)
-                torch.cuda.current_stream(self.x.device).wait_stream(self._stream)
-            finally:
-                ops.section_trace(False)
-            masks, pinned = {}, []
-            for m in model.modules():
-                for pk in (m.__dict__.get("_packed"), getattr(m.__dict__.get("_dgradCache"), "packed", None)):
-                    if pk is not None and hasattr(pk, "wp"):
-                        pinned.append(pk.wp)                 # the graphs re-pack into / read from these addresses for as long as they live
-                        used = ops.sections_used(pk)
-                        if used:
-                            masks[id(pk)] = used
-            model.__dict__["_packMasks"] = masks             # the captured re-pack refreshes those copies only (replays repeat the launches)
-            # flat layout = segment order (backward order), parameters without a gradient left out
-            groups = self._param_groups()
-            self.live_groups = [[p for p in g if p.grad is not None] for g in groups]
-            self.live = [p for g in self.live_groups for p in g]
-            self.flat = torch.empty(sum(p.numel() for p in self.live), dtype=torch.float32, device=self.x.device)
-            self.slices, off = [], 0
-            for g in self.live_groups:
-                n = sum(p.numel() for p in g)
-                self.slices.append(self.flat[off: off + n])
-                off += n
-            self._gather_tables()
-            self._accum_buffers()
-            self._init_optimizer_state()
-            torch.cuda.synchronize()
+                          "variable yourself.", RuntimeWarning, stacklevel=3)
+
+    def _own_optimizer(self) -> bool:
+        """Is the optimizer one of `mcquic_amd.optim`'s: does it answer `guards_itself`, `lends_norm`, `last_grad_norm()`, `skip_count()`?"""
+        from .optim import _Planned
+        return isinstance(self.optimizer, _Planned)
+
+    def _static_input(self, example_x, transform):
+        """`self.x`, the model's static input; with a transform `self.raw` holds the RAW images and the transform's two launches write self.x."""
+        self.x = example_x.detach().clone()
+        self.transform, self.raw = transform, None
+        if transform is not None:
+            self.raw = self.x
+            self.transform = transform.to(self.raw.device)    # (its generator state and gain table: on the device before any capture)
             with torch.no_grad():
-                torch._foreach_add_(self.params, 0.0)        # every parameter "changed": the capture records all re-packs
-            for p in self.params:
-                p.grad = None
-            self.graphs = []
-            pool = torch.cuda.graph_pool_handle() if self.segments > 1 else None
-            self.counts = None
-            for k in range(self.segments):
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=pool, stream=self._stream, **mode):
-                    self._segment(k)
-                    if self.live_groups[k]:
-                        self._gather(k)
-                    if k == 0:
-                        sinks = [c.countSink() for c in self.coders]
-                        # (one coder per model: its count buffer itself -- the sampling kernels add into it, nothing is copied)
-                        self.counts = (sinks[0] if len(sinks) == 1 else torch.cat(sinks)) if sinks else None
-                        if self.accumulate > 1:
-                            self._accum_scalars()
-                self.graphs.append(g)
-            self.graph = self.graphs[0]
-            self._carry = None                               # (the autograd graph between segments: only needed while capturing)
-            self._pinned = pinned + [c.countSink() for c in self.coders]
-        except BaseException:
-            for c in self.coders:
-                c.deferCounts(False)
-            raise
+                self.x = self.transform(self.raw).detach()
+
+    def _warm_segments(self, warmup: int):
+        """The segments eagerly on the capture's stream: caches, workspaces, the coders' count sinks, every parameter's `.grad` -- and the
+        trace of which copy of its operand stream every conv launch of the step reads."""
+        from . import ops
+        ops.section_trace(True)
+        try:
+            with torch.cuda.stream(self._stream):
+                for _ in range(max(1, warmup)):
+                    for k in range(self.segments):
+                        self._segment(k)
+            torch.cuda.current_stream(self.x.device).wait_stream(self._stream)
         finally:
-            model.__dict__.pop("_packMasks", None)
-            blocks._BRANCH_STREAMS = streams
+            ops.section_trace(False)
+
+    def _pin_operand_streams(self) -> list:
+        """The operand streams the graphs re-pack into / read from, to be kept for as long as they live; the copies the warm-up's launches
+        read go into the model's `_packMasks`: the captured re-pack refreshes those only (replays repeat the launches)."""
+        from . import ops
+        masks, pinned = {}, []
+        for m in self.model.modules():
+            for pk in (m.__dict__.get("_packed"), getattr(m.__dict__.get("_dgradCache"), "packed", None)):
+                if pk is not None and hasattr(pk, "wp"):
+                    pinned.append(pk.wp)
+                    used = ops.sections_used(pk)
+                    if used:
+                        masks[id(pk)] = used
+        self.model.__dict__["_packMasks"] = masks
+        return pinned
+
+    def _flat_layout(self):
+        """`live_groups`, `live`, `flat`, `slices`: the flat layout is the segments' order (backward order), parameters the warm-up gave no
+        gradient left out."""
+        self.live_groups = [[p for p in g if p.grad is not None] for g in self._param_groups()]
+        self.live = [p for g in self.live_groups for p in g]
+        self.flat = torch.empty(sum(p.numel() for p in self.live), dtype=torch.float32, device=self.x.device)
+        self.slices, off = [], 0
+        for g in self.live_groups:
+            n = sum(p.numel() for p in g)
+            self.slices.append(self.flat[off: off + n])
+            off += n
+
+    def _capture_segments(self):
+        """`graphs` (and `graph`, the first): each segment with the gather of its gradients behind it; the first one leaves `counts`."""
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            torch._foreach_add_(self.params, 0.0)             # every parameter "changed": the capture records all re-packs
+        for p in self.params:
+            p.grad = None
+        self.graphs, self.counts = [], None
+        pool = torch.cuda.graph_pool_handle() if self.segments > 1 else None
+        for k in range(self.segments):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=pool, stream=self._stream, **self._mode):
+                self._segment(k)
+                if self.live_groups[k]:
+                    self._gather(k)
+                if k == 0:
+                    sinks = [c.countSink() for c in self.coders]
+                    # (one coder per model: its count buffer itself -- the sampling kernels add into it, nothing is copied)
+                    self.counts = (sinks[0] if len(sinks) == 1 else torch.cat(sinks)) if sinks else None
+                    if self.accumulate > 1:
+                        self._accum_scalars()
+            self.graphs.append(g)
+        self.graph = self.graphs[0]
+        self._carry = None                                    # (the autograd graph between segments: only needed while capturing)
+
+    def _bind_grads(self):
+        """Every live parameter's `.grad` becomes its view of the flat buffer: the optimizer reads the reduced gradients."""
         off = 0
-        for p in self.live:                                  # the optimizer reads the reduced gradients
+        for p in self.live:
             p.grad = self.flat[off: off + p.numel()].view_as(p)
             off += p.numel()
-        self.post = None
+
+    def _prepare_update(self):
+        """Everything the update needs before it can be captured: who runs the guard, then every participant's device tables and its
+        kernels' first launch -- a throw-away update after which its state has its bits back (the EMA's averages and count; the meter's
+        count, shadow and ring; the schedule's last_epoch, state and rates)."""
         if self.guard is not None:
             # who runs the guard: the step from its clip's sum of squares; else the optimizer from the partials of its own norm (Lamb,
             # SGD with max_grad_norm); else the step over the flat buffer
-            self._guard_lender = "clip" if self.max_grad_norm is not None else "optimizer" if self.optimizer._wants_norm() else "flat"
+            self._guard_lender = "clip" if self.max_grad_norm is not None else "optimizer" if self.optimizer.lends_norm else "flat"
             self.optimizer.attach_guard(self.guard, decided=self._guard_lender != "optimizer")
             if self._guard_lender == "flat":
                 self.guard.prepare_flat(self.flat)
             self.grad_norm = self.guard.grad_norm
-        if hasattr(self.optimizer, "prepare"):                # (mcquic_amd.optim.Adam / Lamb / SGD: device tables for the flat gradient views, built
-            self.optimizer.prepare()                          #  outside the capture)
-        if self.ema is not None:                              # (its tables, and its kernels' first launch, outside the capture: a throw-away
-            self.ema.prepare()                                #  update after which averages and count have their bits back)
-            self.ema.warm()
-        if self.meter is not None:                            # (the same for the meter: count, shadow and ring keep their bits)
-            self.meter.prepare()
-            self.meter.warm()
-        if self.scheduler is not None:                        # (the same for the schedule: last_epoch, state and rates keep their bits)
-            self.scheduler.prepare()
-            self.scheduler.warm()
+        if hasattr(self.optimizer, "prepare"):                # (mcquic_amd.optim.Adam / Lamb / SGD: device tables for the flat gradient views)
+            self.optimizer.prepare()
+        for h in (self.ema, self.meter, self.scheduler):
+            if h is not None:
+                h.prepare()
+                h.warm()
         if self.guard is not None:
             self._warm_guard()
-        if capture_post:
-            before = self._snapshot_optimizer_state()
-            try:
-                post = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(post, stream=self._stream, **mode):
-                    self._post()
-                self.post = post
-            except Exception:                                # an optimizer that cannot be captured: its update runs eagerly
-                torch.cuda.synchronize()
-                self.post = None
-                self._restore_optimizer_state(before)        # (host-side counters may have moved before the capture gave up)
+
+    def _capture_post(self, capture_post: bool):
+        """`post`: the update as one graph, or None -- not asked for, or an optimizer that cannot be captured: its update runs eagerly."""
+        self.post = None
+        if not capture_post:
+            return
+        before = self._snapshot_optimizer_state()
+        try:
+            post = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(post, stream=self._stream, **self._mode):
+                self._update(self.guard)
+            self.post = post
+        except Exception:
+            torch.cuda.synchronize()
+            self._restore_optimizer_state(before)            # (host-side counters may have moved before the capture gave up)
 
     def _gather(self, k: int):
         """Segment k's gradients into its slice of the flat buffer: ONE launch over device tables (mcq_gather_flat_f32) instead of
@@ -700,93 +740,70 @@ class GraphedTrainStep:
         snap.capture(self.x, xHat, codes, logits0)
         return snap.read()
 
-    def _post(self):
+    def _update(self, guard=None, decides: bool = True):
+        """The update, written once -- captured as the post graph, or run eagerly after the exchange: `/ world`, clip, optimizer, EMA,
+        frequency EMA, scheduler, meter.  `guard`: the `StepGuard` whose flag every launch takes, or None: the launches are the ones
+        they have always been (every entry point selects its plain kernel for a flag that is None).  `decides`: the guard's own launches
+        run here, on the all-reduced, averaged gradient (not in `_warm_guard`, whose scratch flag is set by hand)."""
+        from . import ops
+        flag = None if guard is None else guard.skip
         if self.world > 1:
             self.flat.mul_(1.0 / self.world)
-        if self.guard is not None:
-            return self._post_guarded()
         if self.max_grad_norm is not None:                    # trainer.py:280 `clip_grad_norm(4.0)`: global norm of the AVERAGED gradient,
-            from . import ops                                 # two launches over the flat buffer, nothing read by the host
-            self.grad_norm = ops.clip_by_norm_(self.flat, self.max_grad_norm)
-        self.optimizer.step()
+            sq = ops.sumsq(self.flat)                         # two launches over the flat buffer, nothing read by the host
+            if guard is not None and decides:                 # the clip's sum of squares decides: no second reduction
+                guard.from_norm(sq, squared=True)
+            norm = ops.clip_by_norm_(self.flat, self.max_grad_norm, sq=sq, skip=flag)
+            if guard is None:                                 # (with a guard `grad_norm` is the guard's)
+                self.grad_norm = norm
+        elif guard is not None and decides and self._guard_lender == "flat":
+            guard.run_flat(self.flat)
+        self.optimizer.step()                                 # (`attach_guard`: every launch obeys; the "optimizer" lender runs the guard here)
         if self.ema is not None:
-            self.ema.update()
-        off = 0
-        for c in self.coders:
-            n = c.countSink().numel()
-            c.applyCounts(self.counts[off: off + n])
-            off += n
+            self.ema.update(skip=flag)
+        self._apply_counts(flag)
         if self.scheduler is not None:                        # (the reference's order, trainer.py `_stepFinish`: step the scheduler, then log
-            self.scheduler.step()                             #  get_last_lr(): the meter's `lr` column is the rate of the NEXT update)
+            self.scheduler.step(skip=flag)                    #  get_last_lr(): the meter's `lr` column is the rate of the NEXT update)
         if self.meter is not None:
             self._meter_update()
 
+    def _apply_counts(self, skip=None):
+        """The frequency EMA of every coder from its part of the GLOBAL counts."""
+        off = 0
+        for c in self.coders:
+            n = c.countSink().numel()
+            c.applyCounts(self.counts[off: off + n], skip=skip)
+            off += n
+
     def _warm_guard(self):
-        """Every kernel of the guarded update once outside any capture, without moving a bit of state: the `_skip` launches under a
-        scratch guard whose flag is SET (a skipped launch writes nothing), the guard's own launches into that scratch record."""
+        """Every kernel of the guarded update once outside any capture, without moving a bit of state: the guard's own three launches into
+        a scratch record, then the update under that scratch guard with its flag SET (a skipped launch writes nothing)."""
         from . import ops
         from .guard import StepGuard
         scratch = StepGuard(self.flat.device)
         scratch.run_flat(self.flat)
         scratch.from_partials(scratch._partials, 1)
-        sq = ops.sumsq(self.flat)
-        scratch.from_norm(sq, squared=True)
+        scratch.from_norm(ops.sumsq(self.flat), squared=True)
         scratch.record[0] = 1                                 # (the int32 `skip` is the low word)
-        flag = scratch.skip
-        if self.max_grad_norm is not None:
-            ops.clip_by_norm_(self.flat, self.max_grad_norm, sq=sq, skip=flag)
         self.optimizer.attach_guard(scratch, decided=True)
+        meter, self.meter = self.meter, None                  # (it has warmed itself and obeys no flag: a row of the warm-up would stay)
         try:
-            self.optimizer.step()
+            self._update(scratch, decides=False)
         finally:
+            self.meter = meter
             self.optimizer.attach_guard(self.guard, decided=self._guard_lender != "optimizer")
-        if self.ema is not None:
-            self.ema.update(skip=flag)
-        off = 0
-        for c in self.coders:
-            n = c.countSink().numel()
-            c.applyCounts(self.counts[off: off + n], skip=flag)
-            off += n
-        if self.scheduler is not None:
-            self.scheduler.step(skip=flag)
         torch.cuda.synchronize()
-
-    def _post_guarded(self):
-        """`_post` with `skip_nonfinite`: the guard first (on the all-reduced, averaged gradient), then the same launches in the same
-        order, each taking the flag."""
-        from . import ops
-        flag = self.guard.skip
-        if self._guard_lender == "clip":                      # the clip's sum of squares decides: no second reduction
-            sq = ops.sumsq(self.flat)
-            self.guard.from_norm(sq, squared=True)
-            ops.clip_by_norm_(self.flat, self.max_grad_norm, sq=sq, skip=flag)
-        elif self._guard_lender == "flat":
-            self.guard.run_flat(self.flat)
-        self.optimizer.step()                                 # (`attach_guard`: every launch obeys; the "optimizer" lender runs the guard here)
-        if self.ema is not None:
-            self.ema.update(skip=flag)
-        off = 0
-        for c in self.coders:
-            n = c.countSink().numel()
-            c.applyCounts(self.counts[off: off + n], skip=flag)
-            off += n
-        if self.scheduler is not None:
-            self.scheduler.step(skip=flag)
-        if self.meter is not None:
-            self._meter_update()
 
     def _meter_update(self):
         """The telemetry row of this step (monitor.StepMeter.update): every value goes by device pointer, nothing is read here."""
-        opt = self.optimizer
-        norm = self.grad_norm
+        opt, norm, skipped = self.optimizer, self.grad_norm, None
         if self.guard is not None:                            # (the guard's record: its norm, its count of skipped steps)
-            self.meter.update(self.loss, self.counts, grad_norm=self.guard.grad_norm, lr=opt.param_groups[0]["lr"], skipped=self.guard.skipped)
-            return
-        if norm is None and hasattr(opt, "_last_grad_norm"):  # (mcquic_amd.optim: Lamb always; SGD with max_grad_norm or skip_nonfinite)
-            norm = opt._last_grad_norm()
-        skipped = getattr(opt, "skipped", None)              # (optim.SGD always; optim.Adam / AdamW / Lamb with their own `skip_nonfinite`)
-        self.meter.update(self.loss, self.counts, grad_norm=norm, lr=opt.param_groups[0]["lr"],
-                          skipped=skipped if torch.is_tensor(skipped) else None)
+            norm, skipped = self.guard.grad_norm, self.guard.skipped
+        elif self._own_optimizer():
+            if norm is None:                                  # (Lamb always; SGD with max_grad_norm or skip_nonfinite)
+                norm = opt.last_grad_norm()
+            skipped = opt.skip_count()                        # (SGD always; Adam / AdamW / Lamb with their own `skip_nonfinite`)
+        self.meter.update(self.loss, self.counts, grad_norm=norm, lr=opt.param_groups[0]["lr"], skipped=skipped)
 
     def _start_all_reduce(self, buf: torch.Tensor):
         """Sum `buf` over the ranks without waiting for it: under RCCL an async all-reduce (its stream waits for what the current
@@ -814,32 +831,37 @@ class GraphedTrainStep:
         if self.raw is not None and x.dtype != static.dtype:  # (`copy_` would convert a uint8 batch to float without the / 255)
             raise RuntimeError(f"GraphedTrainStep was captured for {static.dtype} shards, got {x.dtype}")
         for j in range(acc - 1):                              # micro-steps 0 .. k-2: accumulate, exchange nothing
-            static.copy_(x[j * n: (j + 1) * n], non_blocking=True)
-            self._phase.copy_(self._phaseHost[j: j + 1], non_blocking=True)     # (stream-ordered like the input's copy: no host read, no sync)
-            for g in self.graphs:
-                g.replay()
-        if acc > 1:
-            static.copy_(x[(acc - 1) * n:], non_blocking=True)
-            self._phase.copy_(self._phaseHost[acc - 1:], non_blocking=True)
-        else:
-            static.copy_(x, non_blocking=True)
-        works = []
-        for k, g in enumerate(self.graphs):                   # the last (or only) micro-step: the buffers hold the mean / the summed counts
-            g.replay()
-            if self.world > 1:
-                works.append(self._start_all_reduce(self.slices[k]))       # ... while the next segment replays
-                if k == 0 and self.counts is not None:
-                    works.append(self._start_all_reduce(self.counts))
-        for w in works:
+            self._micro_step(static, x, j, exchange=False)
+        # the last (or only) micro-step: the buffers hold the mean / the summed counts
+        for w in self._micro_step(static, x, acc - 1, exchange=self.world > 1):
             if w is not None:
                 w.wait()                                      # (the current stream waits; the host does not)
         if self.post is not None:
             self.post.replay()
         else:
-            self._post()
+            self._update(self.guard)
         for c in self.coders:
             c.resetFreqAndCDF()
         return self.loss
+
+    def _micro_step(self, static, x, j: int, exchange: bool) -> list:
+        """Micro-batch j into the static input (with `accumulate` > 1 also j into the phase word: stream-ordered like the input's copy, no
+        host read, no sync), then the segments' replays; with `exchange` the all-reduce of each segment's slice (and of the counts,
+        behind the first) is started as soon as the segment is enqueued, while the next one replays: the works to join."""
+        if self.accumulate > 1:
+            n = static.shape[0]
+            static.copy_(x[j * n: (j + 1) * n], non_blocking=True)
+            self._phase.copy_(self._phaseHost[j: j + 1], non_blocking=True)
+        else:
+            static.copy_(x, non_blocking=True)
+        works = []
+        for k, g in enumerate(self.graphs):
+            g.replay()
+            if exchange:
+                works.append(self._start_all_reduce(self.slices[k]))
+                if k == 0 and self.counts is not None:
+                    works.append(self._start_all_reduce(self.counts))
+        return works
 
     def invalidate(self):
         """Replays change the parameters without the host seeing it (no version counter moves): mark every parameter changed so

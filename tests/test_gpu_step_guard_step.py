@@ -2,7 +2,8 @@
 [64, 32, 16]), two 64 x 64 images, segments=1), with the whole update in use: EMA, scheduler, meter.  Three batches -- clean, one NaN pixel,
 clean.  A NaN input is ordinary arithmetic: nothing faults, the loss and every gradient come out NaN.  The skipped step must leave every
 state dict bit for bit; the third step must land where a guard-OFF twin lands that only ever saw the two clean batches (its device
-generator set to the states the guarded run had in front of them): the guard changes nothing about a clean step."""
+generator set to the states the guarded run had in front of them): the guard changes nothing about a clean step.  Both with the update
+captured as the post graph and with `capture_post=False`, where the same update runs eagerly after the exchange."""
 import collections
 import copy
 import json
@@ -50,17 +51,18 @@ def _same(a, b):
     return len(a) == len(b) and all(torch.equal(x.detach(), y.detach()) for x, y in zip(a, b))
 
 
+@pytest.mark.parametrize("capture_post", [True, False], ids=["post-graph", "post-eager"])
 @pytest.mark.parametrize("config", sorted(CONFIGS))
-def test_nan_batch_is_skipped_and_the_run_continues_as_if_it_never_came(dev, config):
+def test_nan_batch_is_skipped_and_the_run_continues_as_if_it_never_came(dev, config, capture_post):
     from mcquic_amd import ops
     from test_gpu_ema_step import _setup
     kind, clip = CONFIGS[config]
     model, xs, _ = _setup(dev)
     bad = xs[1].clone()
     bad[1, 2, 7, 5] = float("nan")
-    ours = _build(dev, kind, clip, model, xs[0], skip_nonfinite=True)
-    twin = _build(dev, kind, clip, copy.deepcopy(model), xs[0])
-    assert ours["step"].post is not None and twin["step"].post is not None and twin["step"].guard is None
+    ours = _build(dev, kind, clip, model, xs[0], skip_nonfinite=True, capture_post=capture_post)
+    twin = _build(dev, kind, clip, copy.deepcopy(model), xs[0], capture_post=capture_post)
+    assert (ours["step"].post is not None) == capture_post and (twin["step"].post is not None) == capture_post and twin["step"].guard is None
     assert _same(_state(ours), _state(twin)), "the constructors left both where they started"
     guard, step = ours["step"].guard, ours["step"]
 
