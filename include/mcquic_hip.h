@@ -637,6 +637,35 @@ int mcq_step_meter_update_f32(const float* const* freq_ema /* [levels] device po
                               double momentum, double floor, double pixels, int64_t* state /* device [4] */, int64_t* steps /* [capacity] */,
                               float* ring /* [capacity][columns] */, int64_t capacity, void* stream);
 
+/* Per-parameter gradient / weight / update norms kept on the device (csrc/param_stats.hip; host mirror mcquic_amd.monitor.ParamStats).
+ * Tables as for mcq_adam_step_f32, pointer rows: 0 param, 1 grad (a NULL entry: a gradient of zeros), 2 shadow (read and written only
+ * with `updates`; a flat float32 copy of the weights the caller owns), plus tensor_first_blk[ntensors + 1] as mcq_lamb_step_f32 takes
+ * it.  `state` (device int64 [4]): 0 count, advanced by every finish; 1 first_bad_step and 2 first_bad_tensor (-1 = none), set, and then
+ * kept, by the first recorded row with a non-finite gradient (the lowest such tensor); 3 rows recorded so far.  A step is SAMPLED when
+ * count % every == 0 and RECORDED when it is sampled or skip[0] (a step's guard flag, or NULL) is set; on any other step every workgroup
+ * reads the decision and returns, apart from one lane latching it and one lane advancing count.
+ *   mcq_param_stats_before_f32   sampled steps: the weights into the shadow (call it in front of the optimizer, only with `updates`)
+ *   mcq_param_stats_after_f32    recorded steps: one partial record per chunk into `workspace` (mcq_param_stats_workspace_bytes(nblocks,
+ *                                ntensors) bytes, 8-byte aligned; 0 for counts that are not positive), sums of products in double
+ *   mcq_param_stats_finish_f32   one workgroup per tensor: row ring[(rows % capacity) * ntensors + t] of mcq_param_stats_columns() = 5 floats
+ *                                  0 weight_norm ||w||   1 grad_norm ||g|| over the finite elements   2 grad_absmax over the finite elements
+ *                                  3 grad_nonfinite (count of inf / NaN)   4 update_norm ||w - shadow|| (0 in a row recorded only because
+ *                                  of `skip`; NaN without `updates`)
+ *                                each a double sum's square root rounded to float32 once; steps[rows % capacity] = count; rows and count
+ *                                advance.  A tensor without elements: zeros.
+ * `every`, `capacity` and `updates` must be the same in the three calls of a step.  No atomics, fixed trees: equal inputs at equal
+ * addresses give equal bits.  Nothing is read by the host. */
+int32_t mcq_param_stats_columns(void);
+size_t mcq_param_stats_workspace_bytes(int32_t nblocks, int32_t ntensors);
+int mcq_param_stats_before_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                               int32_t nblocks, const int64_t* state /* device [4] */, int64_t every, void* stream);
+int mcq_param_stats_after_f32(const void* ptr_tables, int32_t ntensors, const int64_t* numel, const int32_t* blk_tensor, const int64_t* blk_first,
+                              int32_t nblocks, const int64_t* state /* device [4] */, int64_t every, int64_t capacity, int32_t updates,
+                              const int32_t* skip /* or NULL */, void* workspace, void* stream);
+int mcq_param_stats_finish_f32(const int32_t* tensor_first_blk, const int32_t* blk_tensor, int32_t ntensors, int32_t nblocks,
+                               const void* workspace, int32_t updates, int64_t* state /* device [4] */, int64_t* steps /* [capacity] */,
+                               float* ring /* [capacity][ntensors][5] */, void* stream);
+
 /* The trainer's periodic log payload made on the device (csrc/step_snapshot.hip; host mirror mcquic_amd.monitor.StepSnapshot): what
  * the reference's `MainTrainer.log` (mcquic/train/trainer.py:463-491) builds on the host from whole tensors of the step.  Additions:
  * the ABI number stays.

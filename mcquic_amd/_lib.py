@@ -185,6 +185,12 @@ SYMBOLS = {
     "mcq_step_meter_columns": (c_int32, [c_int32]),
     "mcq_step_meter_update_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double,
                                             c_void_p, c_double, c_double, c_double, c_double, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "mcq_param_stats_columns": (c_int32, []),
+    "mcq_param_stats_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "mcq_param_stats_before_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
+    "mcq_param_stats_after_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_int64, c_int32,
+                                            c_void_p, c_void_p, c_void_p]),
+    "mcq_param_stats_finish_f32": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "mcq_histogram_chunk": (c_int32, []),
     "mcq_histogram_workspace_bytes": (c_size_t, [c_int64, c_int32]),
     "mcq_histogram_f32": (c_int32, [c_void_p, c_int64, c_int32, c_float, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -7,6 +7,9 @@ post graph of `parallel.GraphedTrainStep(..., meter=...)` and a replay stays fre
 
 `StepSnapshot` is the periodic payload of that `log` (the LogDistance histogram, the frequency and code-map pictures, the batch and its
 reconstruction as images), made by the kernels of csrc/step_snapshot.hip into one buffer when the host asks for it.
+
+`ParamStats` is what neither says: per parameter tensor, the norms of weights, gradient and update and the count of non-finite gradient
+elements (csrc/param_stats.hip), recorded around the optimizer's update of `parallel.GraphedTrainStep(..., stats=...)`.
 """
 from __future__ import annotations
 
@@ -375,3 +378,185 @@ class StepSnapshot:
             out[key] = part(name).view(np.uint8)[: self.keep * 3 * H * W].reshape(self.keep, 3, H, W).copy()
         out["Stat/CodeUsage"] = float(part("usage").view(np.float32)[0])
         return out
+
+
+STAT_COLUMNS = ("weight_norm", "grad_norm", "grad_absmax", "grad_nonfinite", "update_norm")
+
+
+class ParamStats:
+    """Per-parameter gradient, weight and update norms of every step that is looked at, kept on the device (csrc/param_stats.hip):
+
+        stats = ParamStats(model, capacity=64, every=1, updates=True)       # trainable parameters, in model.named_parameters() order
+        step = parallel.GraphedTrainStep(model, opt, example_x, ..., stats=stats)
+        rows = stats.read()          # ONE device-to-host copy: the rows recorded since the last read(), as numpy arrays
+        stats.blame()                # None, or (step, parameter name): the first recorded non-finite gradient (reads two words)
+        # by hand, in an eager loop: stats.before(); opt.step(); stats.after(skip=None)
+
+    `model`: an nn.Module (its parameters with `requires_grad`), or an iterable of tensors (named "0", "1", ...); a tensor's gradient is
+    its `.grad` at the time of the call (None: a gradient of zeros).  One recorded row holds five float32 columns per tensor t, every
+    reduction over the whole tensor, sums of squares formed in double and rounded once (`read()` keys, [rows, T] arrays):
+
+        weight_norm      ||w||_2 after the update (the weights as `after()` finds them)
+        grad_norm        ||g||_2 of the gradient the optimizer consumed -- averaged over ranks and micro-batches, after the step's own
+                         clipping if it clips -- over the FINITE elements only
+        grad_absmax      max |g| over the finite elements; 0 when there are none
+        grad_nonfinite   number of inf / NaN elements of g (exact up to 2^24, as a float32)
+        update_norm      ||w_after - w_before||_2: `before()` copies the weights into a shadow (one flat float32 buffer of the model's
+                         size, allocated once in `prepare()`); NaN in every row when `updates=False` (no shadow, no `before` launch)
+
+    plus `update_ratio` = update_norm / weight_norm, formed on the host.  Sampling is decided on the device: `count` advances on every
+    `after()`; a step is recorded when count % every == 0, or when `skip` (a guard's flag) is set for it -- a skipped step always leaves a
+    row; `steps` holds the count at which each row was made.  On any other step the three launches read the decision and return.  A row
+    made ONLY because the step was skipped does not read the shadow (no `before` refreshed it): its update_norm is 0, as a skipped update
+    moves no weight.  `first_bad_step` / `first_bad_tensor` (-1 = none) are set, and stay set, by the first recorded row in which some
+    tensor has grad_nonfinite > 0: the lowest such tensor.  The ring holds the last `capacity` rows; `read()` reports how many were
+    overwritten unread as `dropped`.  HIP device and float32 only: there is no CPU path."""
+
+    def __init__(self, model, capacity: int = 64, every: int = 1, updates: bool = True):
+        if isinstance(model, torch.nn.Module):
+            named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+        else:
+            named = [(str(i), p) for i, p in enumerate(model)]
+        if not named or not any(p.numel() for _, p in named):
+            raise ValueError("mcquic_amd.monitor.ParamStats: nothing to watch (no trainable parameter with elements)")
+        for n, p in named:
+            if not p.is_cuda:
+                raise RuntimeError(f"mcquic_amd: the watched parameters must live on a HIP device (got {p.device} for {n}); "
+                                   "the HIP kernels have no CPU fallback")
+            if p.dtype != torch.float32:
+                raise TypeError(f"mcquic_amd: the watched parameters must be torch.float32 (got {p.dtype} for {n})")
+            if p.device != named[0][1].device:
+                raise RuntimeError("mcquic_amd.monitor.ParamStats: the parameters must live on one device")
+        if capacity < 1 or every < 1:
+            raise ValueError("mcquic_amd.monitor.ParamStats: capacity >= 1 and every >= 1 are required")
+        self.names, self.params = [n for n, _ in named], [p for _, p in named]
+        self.sizes = [p.numel() for p in self.params]
+        self.capacity, self.every, self.updates = int(capacity), int(every), bool(updates)
+        self.tensors, self.columns = len(self.params), int(_lib.load().mcq_param_stats_columns())
+        dev = self.params[0].device
+        # ONE buffer, so that read() is one copy: [count, first_bad_step, first_bad_tensor, rows] [steps] [ring]
+        cells = self.capacity * self.tensors * self.columns
+        self._buf = torch.zeros(_STATE + self.capacity + (cells + 1) // 2, dtype=torch.int64, device=dev)
+        self._count, self.first_bad_step, self.first_bad_tensor, self._rows = self._buf[0], self._buf[1], self._buf[2], self._buf[3]
+        self._steps = self._buf[_STATE: _STATE + self.capacity]
+        self._ring = self._buf[_STATE + self.capacity:].view(torch.float32)[:cells].view(self.capacity, self.tensors, self.columns)
+        self._buf[1:3].fill_(-1)
+        self._last_read = 0
+        self._table = self._ws = self._shadow = None
+        self._none = torch.empty(0, dtype=torch.float32)      # (data_ptr() 0: the table entry of a parameter without a gradient)
+
+    # ---- launch tables -------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def prepare(self) -> None:
+        """The device tables for the addresses the parameters and their gradients have NOW, the workspace and (with `updates`) the
+        shadow; `parallel.GraphedTrainStep` calls it before it captures.  Refilled when an address changes (not inside a capture)."""
+        dev = self._buf.device
+        for p in self.params:
+            g = p.grad
+            if not (p.is_cuda and p.is_contiguous() and p.device == dev):
+                raise RuntimeError("mcquic_amd.monitor.ParamStats: contiguous parameters on the statistics' HIP device only (there is no CPU path)")
+            if g is not None and not (g.is_cuda and g.is_contiguous() and g.device == dev and g.dtype == torch.float32 and g.numel() == p.numel()):
+                raise RuntimeError("mcquic_amd.monitor.ParamStats: contiguous float32 gradients of the parameters' sizes on their HIP device only")
+        if self._table is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("mcquic_amd.monitor.ParamStats: call `prepare()` before capturing (the workspace cannot be allocated inside a graph)")
+            from .tensor_list import TensorList, flat_layout
+            self._table = TensorList(self.sizes, dev, rows=3, moved="mcquic_amd.monitor.ParamStats: parameter or gradient addresses changed "
+                                                                     "since the last call")
+            nbytes = int(_lib.load().mcq_param_stats_workspace_bytes(self._table.nblocks, self.tensors))
+            self._ws = torch.zeros(nbytes // 8, dtype=torch.int64, device=dev)
+            shadows = None
+            if self.updates:                                  # (the rows a caller owns are filled once: the shadows never move)
+                offsets, total = flat_layout(self.sizes)
+                self._shadow = torch.zeros(total, dtype=torch.float32, device=dev)
+                shadows = [self._shadow[o: o + n] for o, n in zip(offsets, self.sizes)]
+            self._table.fill(self.params, None, shadows)
+        self._table.fill(self.params, [self._none if p.grad is None else p.grad for p in self.params])
+
+    # ---- one step ------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def before(self) -> None:
+        """In front of the optimizer's step: on a sampled step the weights go into the shadow (one launch, capturable after `prepare()`);
+        nothing is launched with `updates=False`."""
+        self.prepare()
+        if not self.updates:
+            return
+        with _guard(self._buf.device):
+            check(_lib.load().mcq_param_stats_before_f32(*self._table.args(), self._buf.data_ptr(), self.every, _stream()),
+                  "mcq_param_stats_before_f32")
+
+    @torch.no_grad()
+    def after(self, skip=None) -> None:
+        """Behind the optimizer's step: the row of this step, if it is recorded, and count + 1 (two launches, capturable after
+        `prepare()`).  `skip`: the step's guard flag (one int32 on the device, `guard.StepGuard.skip`) or None."""
+        self.prepare()
+        from .guard import skip_pointer
+        dev = self._buf.device
+        flag = skip_pointer(skip, dev, "mcquic_amd.monitor.ParamStats.after")
+        lib, t = _lib.load(), self._table
+        with _guard(dev):
+            check(lib.mcq_param_stats_after_f32(*t.args(), self._buf.data_ptr(), self.every, self.capacity, int(self.updates), flag,
+                                                self._ws.data_ptr(), _stream()), "mcq_param_stats_after_f32")
+            check(lib.mcq_param_stats_finish_f32(t.tensor_first_blk.data_ptr(), t.blk_tensor.data_ptr(), self.tensors, t.nblocks,
+                                                 self._ws.data_ptr(), int(self.updates), self._buf.data_ptr(), self._steps.data_ptr(),
+                                                 self._ring.data_ptr(), _stream()), "mcq_param_stats_finish_f32")
+
+    @torch.no_grad()
+    def warm(self) -> None:
+        """One throw-away pass, so that the kernels' first launch happens outside any capture; count, blame words, ring and shadow keep
+        their bits."""
+        self.prepare()
+        self._table.tensor_first_blk                          # (uploaded on first use: not inside a capture)
+        keep = self._buf.clone()
+        shadow = None if self._shadow is None else self._shadow.clone()
+        self.before()
+        self.after()
+        self._buf.copy_(keep)
+        if shadow is not None:
+            self._shadow.copy_(shadow)
+
+    # ---- the host side ---------------------------------------------------------------------------------------------------------
+    def read(self) -> dict:
+        """The rows recorded since the last `read()` (at most the last `capacity`), in step order: `steps` [rows], `names`, one [rows, T]
+        numpy array per column, `update_ratio`; `dropped` rows were overwritten before they were read; `count`, `first_bad_step` and
+        `first_bad_tensor` as of this copy.  One device-to-host copy of the buffer (a host synchronisation: call it when you want to look)."""
+        host = self._buf.cpu().numpy()
+        count, bad_step, bad_tensor, made = (int(v) for v in host[:_STATE])
+        first = max(self._last_read, made - self.capacity)
+        dropped = max(0, first - self._last_read)
+        slots = np.arange(first, max(first, made)) % self.capacity
+        cells = self.capacity * self.tensors * self.columns
+        ring = host[_STATE + self.capacity:].view(np.float32)[:cells].reshape(self.capacity, self.tensors, self.columns)[slots]
+        out = {"steps": host[_STATE: _STATE + self.capacity][slots].copy(), "names": list(self.names), "dropped": dropped, "count": count,
+               "first_bad_step": bad_step, "first_bad_tensor": bad_tensor}
+        for i, name in enumerate(STAT_COLUMNS):
+            out[name] = ring[:, :, i].copy()
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out["update_ratio"] = out["update_norm"] / out["weight_norm"]
+        self._last_read = max(self._last_read, made)
+        return out
+
+    def blame(self):
+        """None, or (step, parameter name) of the first recorded non-finite gradient (reads the two blame words back)."""
+        step, tensor = (int(v) for v in self._buf[1:3].cpu())
+        return None if step < 0 else (step, self.names[tensor])
+
+    def state_dict(self) -> dict:
+        """Count, rows, blame words, ring and step numbers (device copies: nothing is read back), and the host's read position.  The shadow
+        is not part of it: every sampled step rewrites it."""
+        return {"count": self._count.clone(), "rows": self._rows.clone(), "first_bad_step": self.first_bad_step.clone(),
+                "first_bad_tensor": self.first_bad_tensor.clone(), "ring": self._ring.clone(), "steps": self._steps.clone(),
+                "last_read": self._last_read}
+
+    @torch.no_grad()
+    def load_state_dict(self, sd) -> None:
+        """Into the buffer this object already has (the addresses a captured step holds): a resumed run continues its numbering."""
+        if tuple(sd["ring"].shape) != tuple(self._ring.shape):
+            raise RuntimeError(f"mcquic_amd.monitor.ParamStats: the checkpoint's ring is {tuple(sd['ring'].shape)}, this object's "
+                               f"{tuple(self._ring.shape)} (capacity, tensors, 5)")
+        dev = self._buf.device
+        for name, word in (("count", self._count), ("rows", self._rows), ("first_bad_step", self.first_bad_step),
+                           ("first_bad_tensor", self.first_bad_tensor), ("steps", self._steps)):
+            word.copy_(sd[name].to(dev, torch.int64))
+        self._ring.copy_(sd["ring"].to(dev, torch.float32))
+        self._last_read = int(sd.get("last_read", 0))

@@ -273,6 +273,13 @@ class GraphedTrainStep:
     on the device at every replay when it is a device tensor, as it is now when it is a host number) and the optimizer's `skipped`
     count where it has one.  The constructor leaves the meter's count, shadow and ring bit for bit as they were.  Without a meter
     not one launch changes.
+    `stats` (a `mcquic_amd.monitor.ParamStats` of this model): per-parameter weight, gradient and update norms and the count of non-finite
+    gradient elements, recorded on the device -- `stats.before()` directly in front of the optimizer's step (the clip, if any, has run: the
+    gradient is the one the optimizer consumes), `stats.after(skip=flag)` directly behind it and before the EMA, inside the post graph when
+    that is captured (three launches; on a step its `every` does not sample they read the decision and return).  With `skip_nonfinite` a
+    skipped step always leaves a row, so `stats.blame()` names the tensor the guard cannot.  It only reads: parameters and every other state
+    keep the bits they have without it; the constructor leaves its count, blame words, ring and shadow as they were.  Works with every
+    optimizer the step accepts.  Without it not one launch changes.
     `scheduler` (a `mcquic_amd.schedule` scheduler of this optimizer): `scheduler.step()` follows the optimizer, the EMA and the frequency
     EMA and precedes the meter -- the reference steps its scheduler after every batch and logs `get_last_lr()` afterwards
     (mcquic/train/trainer.py `_stepFinish`) --, inside the post graph when that is captured: one more launch of one workgroup that
@@ -319,8 +326,9 @@ class GraphedTrainStep:
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
                  broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None, scheduler=None,
-                 skip_nonfinite: bool = False, keep_outputs: bool = False, accumulate: int = 1):
+                 skip_nonfinite: bool = False, keep_outputs: bool = False, accumulate: int = 1, stats=None):
         self.model, self.optimizer, self.group, self.ema, self.meter, self.scheduler = model, optimizer, group, ema, meter, scheduler
+        self.stats = stats
         self.accumulate, self.max_grad_norm, self.kwargs = accumulate, max_grad_norm, dict(forward_kwargs or {})
         self.keep_outputs, self.outputs = bool(keep_outputs), None      # (xHat, codes, level-0 logits) of the last replay, for `snapshot`
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -501,7 +509,7 @@ class GraphedTrainStep:
     def _prepare_update(self):
         """Everything the update needs before it can be captured: who runs the guard, then every participant's device tables and its
         kernels' first launch -- a throw-away update after which its state has its bits back (the EMA's averages and count; the meter's
-        count, shadow and ring; the schedule's last_epoch, state and rates)."""
+        count, shadow and ring; the schedule's last_epoch, state and rates; the statistics' count, blame words, ring and shadow)."""
         if self.guard is not None:
             # who runs the guard: the step from its clip's sum of squares; else the optimizer from the partials of its own norm (Lamb,
             # SGD with max_grad_norm); else the step over the flat buffer
@@ -512,7 +520,7 @@ class GraphedTrainStep:
             self.grad_norm = self.guard.grad_norm
         if hasattr(self.optimizer, "prepare"):                # (mcquic_amd.optim.Adam / Lamb / SGD: device tables for the flat gradient views)
             self.optimizer.prepare()
-        for h in (self.ema, self.meter, self.scheduler):
+        for h in (self.ema, self.meter, self.scheduler, self.stats):
             if h is not None:
                 h.prepare()
                 h.warm()
@@ -742,7 +750,7 @@ class GraphedTrainStep:
 
     def _update(self, guard=None, decides: bool = True):
         """The update, written once -- captured as the post graph, or run eagerly after the exchange: `/ world`, clip, optimizer, EMA,
-        frequency EMA, scheduler, meter.  `guard`: the `StepGuard` whose flag every launch takes, or None: the launches are the ones
+        frequency EMA, scheduler, meter (`stats` around the optimizer).  `guard`: the `StepGuard` whose flag every launch takes, or None: the launches are the ones
         they have always been (every entry point selects its plain kernel for a flag that is None).  `decides`: the guard's own launches
         run here, on the all-reduced, averaged gradient (not in `_warm_guard`, whose scratch flag is set by hand)."""
         from . import ops
@@ -758,7 +766,11 @@ class GraphedTrainStep:
                 self.grad_norm = norm
         elif guard is not None and decides and self._guard_lender == "flat":
             guard.run_flat(self.flat)
+        if self.stats is not None:                            # (the clip has run: the gradient is the one the optimizer consumes)
+            self.stats.before()
         self.optimizer.step()                                 # (`attach_guard`: every launch obeys; the "optimizer" lender runs the guard here)
+        if self.stats is not None:
+            self.stats.after(skip=flag)
         if self.ema is not None:
             self.ema.update(skip=flag)
         self._apply_counts(flag)
@@ -787,10 +799,11 @@ class GraphedTrainStep:
         scratch.record[0] = 1                                 # (the int32 `skip` is the low word)
         self.optimizer.attach_guard(scratch, decided=True)
         meter, self.meter = self.meter, None                  # (it has warmed itself and obeys no flag: a row of the warm-up would stay)
+        stats, self.stats = self.stats, None                  # (likewise: a set flag FORCES a row)
         try:
             self._update(scratch, decides=False)
         finally:
-            self.meter = meter
+            self.meter, self.stats = meter, stats
             self.optimizer.attach_guard(self.guard, decided=self._guard_lender != "optimizer")
         torch.cuda.synchronize()
 
