@@ -317,6 +317,13 @@ int mcq_vq_soft_bwd_f32(const float* ddist, const float* rowsum, const float* x,
                         const int64_t* sample_index, const float* sample_hot, const float* codebook, float* dx,
                         float* dcodebook, int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, void* stream);
 
+/* Read-only: which kernel forms mcq_vq_soft_bwd_f32 runs for a shape.  out[3] = {dx_form, dc_form, dx_split}: the form of the latent
+ * and of the codebook contraction -- 0 lane-per-channel (any shape), 1 tiled, 2 MFMA -- and the workgroups per 32-row tile of the
+ * MFMA dx form (2: the codewords are halved and the parts added onto a zeroed dx; 1 otherwise and for forms 0 / 1).  Host code
+ * only; the routing the entry point itself launches by.  Returns 1, or 0 (out untouched) for a shape the entry point refuses
+ * (MCQ_EINVAL / MCQ_ETOOLARGE) and for a NULL out. */
+int mcq_vq_soft_bwd_plan(int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, int32_t* out);
+
 /* ---- per-step bookkeeping of the training quantizer (round 5; csrc/step_ops.hip) ------------------------------ */
 #define MCQ_VQ_MAX_LEVELS 32   /* (8 until ABI 9; the reference's generator configs run 17 levels) */
 /* the cap a binding chunks by (returns MCQ_VQ_MAX_LEVELS of the library it loaded) */

@@ -16,7 +16,8 @@ struct VqBwdK {
     int N, m, d, hw, k, rows;
 };
 
-bool mcq_vq_dc_mfma_ok(const VqBwdK& p);
-bool mcq_vq_dx_mfma_ok(const VqBwdK& p);
+// Which form takes a shape is decided once, by mcq_vq_soft_bwd_plan (vq_train.hip; include/mcquic_hip.h): the launches below run what
+// it says and decide nothing.  VQ_DC_MFMA_WAVES: the vector slices of the d-codebook form -- the plan grants whole vector pairs per slice.
+constexpr int VQ_DC_MFMA_WAVES = 8;
 void mcq_vq_dc_mfma_launch(const VqBwdK& p, void* stream);
-void mcq_vq_dx_mfma_launch(const VqBwdK& p, void* stream);
+void mcq_vq_dx_mfma_launch(const VqBwdK& p, int split /* workgroups per 32-row tile: 1 or 2 (the plan's dx_split) */, void* stream);

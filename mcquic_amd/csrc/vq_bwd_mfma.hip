@@ -23,7 +23,7 @@ __device__ __forceinline__ f32x4v load4_s(__amdgpu_buffer_rsrc_t r, unsigned vof
 // ddist rides along on the VALU (one add per step); the straight-through term -- hot_v dDeq_v into the row of v's sampled
 // codeword -- is sparse (one row per vector): every wave scans the indices of its slice, 64 at a time, and adds the hits in
 // vector order.
-constexpr int DC_PF = 16, DC_WAVES = 8;
+constexpr int DC_PF = 16, DC_WAVES = VQ_DC_MFMA_WAVES;
 __global__ __launch_bounds__(64 * DC_WAVES) void vq_dc_mfma_kernel(VqBwdK p) {
     __shared__ float part[DC_WAVES - 1][2][16][64];
     __shared__ float part_cs[DC_WAVES - 1][64];
@@ -236,21 +236,12 @@ __global__ __launch_bounds__(256) void vq_zero_kernel(float4* __restrict__ out, 
 
 }  // namespace
 
-bool mcq_vq_dc_mfma_ok(const VqBwdK& p) {
-    const long long V = (long long)p.N * p.hw;
-    return p.d <= 64 && p.k % 32 == 0 && p.hw % 2 == 0 && V % (2 * DC_WAVES) == 0 && (unsigned long long)p.rows * p.k * 4ull < 0x80000000ull &&
-           (unsigned long long)V * p.m * p.d * 4ull < 0x80000000ull;
-}
-bool mcq_vq_dx_mfma_ok(const VqBwdK& p) {
-    return p.d <= 64 && p.hw % 32 == 0 && p.k % 128 == 0 && (unsigned long long)p.rows * p.k * 4ull < 0x80000000ull &&
-           (unsigned long long)p.m * p.k * p.d * 4ull < 0x80000000ull;
-}
 void mcq_vq_dc_mfma_launch(const VqBwdK& p, void* stream) {
     hipLaunchKernelGGL(vq_dc_mfma_kernel, dim3((unsigned)(p.k / 32), (unsigned)p.m), dim3(64 * DC_WAVES), 0, (hipStream_t)stream, p);
 }
-void mcq_vq_dx_mfma_launch(const VqBwdK& p, void* stream) {
-    // fewer tiles than CUs (rows / 32 = 128 at the first training level): the codewords are halved over two workgroups per tile
-    const unsigned zs = (p.rows / 32 < 256 && p.k % 256 == 0) ? 2u : 1u;
+void mcq_vq_dx_mfma_launch(const VqBwdK& p, int split, void* stream) {
+    // split 2 -- fewer tiles than CUs (rows / 32 = 128 at the first training level): the codewords are halved over two workgroups per tile
+    const unsigned zs = (unsigned)split;
     if (zs == 2) {                                       // rows % 32 == 0: a whole number of float4
         const size_t n4 = (size_t)p.rows * p.d / 4;
         hipLaunchKernelGGL(vq_zero_kernel, dim3((unsigned)((n4 + 255) / 256 < 1024 ? (n4 + 255) / 256 : 1024)), dim3(256), 0, (hipStream_t)stream,

@@ -907,7 +907,36 @@ __global__ __launch_bounds__(256) void vq_dc_tiled_kernel(const float* __restric
     }
 }
 
+// THE routing of mcq_vq_soft_bwd_f32, pure host arithmetic: which of the three forms of each contraction takes a shape -- 0 the
+// lane-per-channel kernels (vq_dx_kernel / vq_dc_kernel: any shape), 1 the tiled ones above, 2 the MFMA forms of vq_bwd_mfma.hip -- and
+// how many workgroups share a 32-row tile of the MFMA dx form.  What the kernels read without a check is granted here: whole 32-row
+// tiles of one (image, group) and wave slices of whole 8-codeword chunks (dx, form 2); whole vector pairs per wave slice within one
+// image row pair (dC, form 2); byte offsets into ddist / the codebook / the channel-major copies below 2^31 (both: buffer resources).
+// Returns MCQ_OK, or the status the entry point refuses the shape with.
+int vq_soft_bwd_route(int N, int m, int d, int h, int w, int k, int32_t plan[3]) {
+    if (N <= 0 || m <= 0 || d <= 0 || h <= 0 || w <= 0 || k <= 0) return MCQ_EINVAL;
+    const long long rows = (long long)N * m * h * w;
+    if (rows > 0x7fffffffLL) return MCQ_ETOOLARGE;
+    const long long hw = (long long)h * w, V = (long long)N * hw;
+    const bool ddist_fits = (unsigned long long)rows * k * 4ull < 0x80000000ull;
+    const bool dx_mfma = d <= 64 && hw % 32 == 0 && k % 128 == 0 && ddist_fits && (unsigned long long)m * k * d * 4ull < 0x80000000ull;
+    const bool dc_mfma = d <= 64 && k % 32 == 0 && hw % 2 == 0 && V % (2 * VQ_DC_MFMA_WAVES) == 0 && ddist_fits &&
+                         (unsigned long long)V * m * d * 4ull < 0x80000000ull;
+    plan[0] = dx_mfma ? 2 : (d <= 64 && hw % DX_R == 0 && k % 16 == 0) ? 1 : 0;
+    plan[1] = dc_mfma ? 2 : (d <= 64 && k % DC_W == 0) ? 1 : 0;
+    // fewer tiles than CUs (rows / 32 = 128 at the first training level): the codewords are halved over two workgroups per tile
+    plan[2] = (dx_mfma && rows / 32 < 256 && k % 256 == 0) ? 2 : 1;
+    return MCQ_OK;
+}
+
 }  // namespace
+
+extern "C" int mcq_vq_soft_bwd_plan(int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, int32_t* out) {
+    int32_t plan[3];
+    if (!out || vq_soft_bwd_route(N, m, d, h, w, k, plan) != MCQ_OK) return 0;
+    for (int i = 0; i < 3; ++i) out[i] = plan[i];
+    return 1;
+}
 
 extern "C" int mcq_vq_soft_bwd_f32(const float* ddist, const float* rowsum, const float* x, const float* x_nhwc,
                                    const float* ddeq_nhwc, const int64_t* sample_index, const float* sample_hot,
@@ -915,26 +944,27 @@ extern "C" int mcq_vq_soft_bwd_f32(const float* ddist, const float* rowsum, cons
                                    int32_t w, int32_t k, void* stream) {
     if (!ddist || !rowsum || !x || !x_nhwc || !ddeq_nhwc || !sample_index || !sample_hot || !codebook || !dx || !dcodebook)
         return MCQ_EINVAL;
-    if (N <= 0 || m <= 0 || d <= 0 || h <= 0 || w <= 0 || k <= 0) return MCQ_EINVAL;
+    int32_t plan[3];                                     // {dx form, dC form, workgroups per dx tile}: vq_soft_bwd_route decides, nothing below does
+    const int status = vq_soft_bwd_route(N, m, d, h, w, k, plan);
+    if (status != MCQ_OK) return status;
     const long long rows = (long long)N * m * h * w;
-    if (rows > 0x7fffffffLL) return MCQ_ETOOLARGE;
     hipStream_t s = (hipStream_t)stream;
     const int hw = h * w;
     VqBwdK q;
     q.ddist = ddist; q.rowsum = rowsum; q.x = x; q.xt = x_nhwc; q.dqt = ddeq_nhwc; q.index = sample_index; q.hot = sample_hot;
     q.cb = codebook; q.dx = dx; q.dcb = dcodebook; q.N = N; q.m = m; q.d = d; q.hw = hw; q.k = k; q.rows = (int)rows;
     // the MFMA forms (vq_bwd_mfma.hip) wherever their tiling fits; the lane-per-channel forms below for the rest
-    if (mcq_vq_dx_mfma_ok(q))
-        mcq_vq_dx_mfma_launch(q, stream);
-    else if (d <= 64 && hw % DX_R == 0 && k % 16 == 0)
+    if (plan[0] == 2)
+        mcq_vq_dx_mfma_launch(q, plan[2], stream);
+    else if (plan[0] == 1)
         hipLaunchKernelGGL(vq_dx_tiled_kernel, dim3((unsigned)(rows / DX_R)), dim3(256), 0, s, ddist, rowsum, x, codebook, dx,
                            (int)rows, m, d, hw, k);
     else
         hipLaunchKernelGGL(vq_dx_kernel, dim3((unsigned)((rows + 3) / 4)), dim3(256), 0, s, ddist, rowsum, x, codebook, dx, (int)rows, m, d,
                            hw, k);
-    if (mcq_vq_dc_mfma_ok(q))
+    if (plan[1] == 2)
         mcq_vq_dc_mfma_launch(q, stream);
-    else if (d <= 64 && k % DC_W == 0)
+    else if (plan[1] == 1)
         hipLaunchKernelGGL(vq_dc_tiled_kernel, dim3((unsigned)(k / DC_W), (unsigned)m), dim3(256), 0, s, ddist, x_nhwc, ddeq_nhwc,
                            sample_index, sample_hot, codebook, dcodebook, N, m, d, hw, k);
     else

@@ -636,7 +636,7 @@ def test_winograd_input_gradient_pack(dev):
                                   (8, 2, 64, 4, 4, 512),        # third level: dC on the MFMA form, dx on the lane-per-channel one
                                   (2, 3, 24, 4, 16, 512),       # d < 32: one channel block empty, the other partly
                                   (1, 2, 40, 8, 8, 1024),       # d between the blocks
-                                  (3, 2, 16, 3, 5, 48)])        # nothing fits: both lane-per-channel forms
+                                  (3, 2, 16, 3, 5, 48)])        # no MFMA form fits: dx lane-per-channel (hw = 15), dC tiled (k % 16 == 0)
 def test_soft_assignment_backward_contractions(dev, case):
     """mcq_vq_soft_bwd_f32 (the MFMA forms of csrc/vq_bwd_mfma.hip and the forms they replace) against the two contractions
     written out in float64: dx = 2 x rowsum - 2 ddist C, dC = 2 C colsum - 2 ddist^T x + scatter(hot dDeq)."""
@@ -879,8 +879,8 @@ def test_conv_backward_random_shapes(dev):
 def test_soft_assignment_backward_random_shapes(dev):
     """40 seeded random (batch, codebooks, vector length, map, codewords) shapes through mcq_vq_soft_bwd_f32 against the two
     contractions in float64: which of the MFMA / tiled / lane-per-channel forms takes a shape depends on d, k, the map and the row
-    count (csrc/vq_bwd_mfma.hip: mcq_vq_dc_mfma_ok / mcq_vq_dx_mfma_ok) -- the fixed cases pin one shape per form, this sweeps
-    their borders."""
+    count (csrc/vq_train.hip: vq_soft_bwd_route, queried through mcq_vq_soft_bwd_plan) -- this sweeps their borders at the whole-tensor
+    bar; tests/test_gpu_soft_bwd_leaf.py pins every form, by name and per element, to exact and float64 references."""
     import random
     import numpy as np
     from mcquic_amd import ops
