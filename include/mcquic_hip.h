@@ -615,6 +615,43 @@ int mcq_ema_update_skip_f32(const void* ptr_tables, int32_t ntensors, const int6
 int mcq_freq_ema_update_skip_f32(float* const* freq_ema /* [levels] device pointers */, const int32_t* m, const int32_t* k, int32_t levels,
                                  const int64_t* counts, double ema, const int32_t* skip /* or NULL */, void* stream);
 
+/* Codebook reassignment inside the step (csrc/vq_reassign.hip; host mirror mcquic_amd.reassign.CodebookReassign): every `every` updates
+ * the dead codewords (normalised frequency < 1e-6) of every level and group are overwritten by the most used ones, by the rule of
+ * mcquic/modules/quantizer.py:111-136 -- TWO launches per step for all levels and groups, which on a step that does not fire read the
+ * decision and return.  Level tables as for mcq_freq_ema_update_f32 (host arrays of `levels` <= MCQ_VQ_MAX_LEVELS entries; a binding
+ * chunks beyond: every plan launch of a step first, then every apply launch).
+ *   `state`   int64 [MCQ_REASSIGN_STATE_WORDS] on the device:
+ *               0 count       completed updates; advanced by the plan launch with `advance` (the first table of a step)
+ *               1 seen        the count the last apply launch with `last` committed (what the plan launch decides from)
+ *               2 fired       steps that fired
+ *               3 moved       codewords that moved by more than 1e-4 in squared distance on the last step that fired
+ *               4 proportion  moved / step_codewords of that step, a float32 in the low word (the reference's return value)
+ *               5 seed, 6 offset   the generator state of the drawn priorities; offset += step_levels on a step that fires
+ *   decision  with *skip set (the step's guard flag, see mcq_step_guard_list_f32; NULL = never) nothing moves and nothing is written,
+ *             the count included.  Otherwise s = seen + 1 is the completed count after this update and the step fires when
+ *             s >= start and (s + 1) % every == 0 (the reference increments its step and then tests (step + 1) % freq).
+ *   plan      one workgroup per (level, group): from the RAW frequency row f [k] and the priority row (priority[l], or with priority
+ *             or priority[l] NULL the generator's draws for stream MCQ_RNG_STREAM_REASSIGN under {seed, offset + level0 + l}, element
+ *             g k + i: what mcq_hash_uniform_f32 returns for it) `source` [m, k] (donor index per codeword, its own where nothing moves)
+ *             and `refill` [m, k] (0 / 1).  The row sum is formed in double in a fixed order and rounded once to float32.  Ranks are
+ *             counted over the row held in LDS (k^2 compares per ordering), stable with ties by index; k > mcq_vq_reassign_max_k()
+ *             is MCQ_EINVAL.
+ *   apply     ONE workgroup: per group the donor rows are gathered into `scratch` (max k_l d_l floats) before any row of the group is
+ *             written (a donor can itself be refilled), `changed` [m, k] (0 / 1) = squared distance > 1e-4 in float32 summed over d
+ *             in index order; `first` starts `moved` at 0, `last` forms proportion from step_codewords (the sum of m_l k_l over the
+ *             step) and commits seen, fired and the generator's offset. */
+#define MCQ_REASSIGN_MAX_K 8192
+#define MCQ_REASSIGN_STATE_WORDS 7
+#define MCQ_RNG_STREAM_REASSIGN 3u
+int32_t mcq_vq_reassign_max_k(void);
+int mcq_vq_reassign_plan(const float* const* freq_ema /* [levels] device pointers */, const float* const* priority /* or NULL; entries or NULL */,
+                         const int32_t* m, const int32_t* k, int32_t levels, int32_t level0, int32_t advance, int32_t* const* source,
+                         uint8_t* const* refill, int64_t* state, int64_t every, int64_t start, const int32_t* skip /* or NULL */, void* stream);
+int mcq_vq_reassign_apply(float* const* codebook /* [levels] device pointers to [m_l, k_l, d_l] */, const int32_t* const* source,
+                          const uint8_t* const* refill, uint8_t* const* changed, const int32_t* m, const int32_t* k, const int32_t* d,
+                          int32_t levels, int32_t first, int32_t last, int32_t step_levels, int64_t step_codewords, float* scratch,
+                          int64_t* state, int64_t every, int64_t start, const int32_t* skip /* or NULL */, void* stream);
+
 /* Per-step training telemetry kept on the device (csrc/step_meter.hip; host mirror mcquic_amd.monitor.StepMeter): what the
  * reference's trainer reports after an update (mcquic/train/trainer.py:423-441, 463-491) as one float32 row per step in a ring
  * buffer, written by two launches that read every per-step value through a device pointer.  Level tables as for

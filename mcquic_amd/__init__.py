@@ -19,6 +19,7 @@ _os.environ.setdefault("DEBUG_CLR_GRAPH_PACKET_CAPTURE", "0")
 from .modules.compressor import BaseCompressor, Compressor, Neon  # noqa: E402
 from . import loss  # noqa: E402,F401  (training losses: MsSSIM, PSNR, step_loss)
 from . import kmeans  # noqa: E402,F401  (fit_codebooks: data-dependent codebooks by k-means on the device)
+from .reassign import CodebookReassign  # noqa: E402  (the reference's training hook: dead codewords refilled inside the step)
 
-__all__ = ["BaseCompressor", "Compressor", "Neon", "loss", "kmeans"]
+__all__ = ["BaseCompressor", "Compressor", "Neon", "loss", "kmeans", "CodebookReassign"]
 __version__ = "0.1.0"

@@ -181,6 +181,11 @@ SYMBOLS = {
     "mcq_ema_update_skip_f32": (c_int32, [c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_double, c_int32, c_void_p,
                                           c_void_p, c_void_p]),
     "mcq_freq_ema_update_skip_f32": (c_int32, [c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_double, c_void_p, c_void_p]),
+    "mcq_vq_reassign_max_k": (c_int32, []),
+    "mcq_vq_reassign_plan": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_int64, c_void_p, c_void_p]),
+    "mcq_vq_reassign_apply": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32,
+                                        c_int32, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
     "mcq_lr_schedule_host": (c_int32, [POINTER(LrSchedule), c_int32, c_void_p, c_void_p, c_void_p]),
     "mcq_step_meter_workspace_bytes": (c_size_t, [c_void_p, c_void_p, c_int32]),
     "mcq_step_meter_columns": (c_int32, [c_int32]),

@@ -902,6 +902,131 @@ def freq_ema_update_(freqs: Sequence[torch.Tensor], counts: torch.Tensor, ema: f
             off += size
 
 
+REASSIGN_STATE_WORDS = 7          # MCQ_REASSIGN_STATE_WORDS: count, seen, fired, moved, proportion (float32, low word), seed, offset
+REASSIGN_STREAM = 3               # MCQ_RNG_STREAM_REASSIGN: the generator stream of the drawn priorities
+
+
+def _reassign_state(state: torch.Tensor, who: str) -> torch.Tensor:
+    s = _dev(state, "state", torch.int64)
+    if s.data_ptr() != state.data_ptr() or s.numel() != REASSIGN_STATE_WORDS:
+        raise ValueError(f"{who}: `state` must be {REASSIGN_STATE_WORDS} contiguous int64 words (it is updated in place)")
+    return s
+
+
+def _reassign_rows(ts, shapes, dtype, dev, name: str, who: str):
+    """Per-level [m_l, k_l] buffers of `dtype`: the caller's (checked, written in place) or fresh ones."""
+    if ts is None:
+        return [torch.empty(s, dtype=dtype, device=dev) for s in shapes]
+    ts = list(ts)
+    if len(ts) != len(shapes):
+        raise ValueError(f"{who}: `{name}` needs one tensor per level")
+    for t, s in zip(ts, shapes):
+        if not (t.is_cuda and t.device == dev and t.dtype == dtype and tuple(t.shape) == tuple(s) and t.is_contiguous()):
+            raise ValueError(f"{who}: `{name}` must be contiguous {dtype} {tuple(s)} tensors on {dev} (they are written in place)")
+    return ts
+
+
+def vq_reassign_plan(freqs: Sequence[torch.Tensor], state: torch.Tensor, every: int, start: int = 0, priorities=None, skip=None,
+                     source=None, refill=None):
+    """The first of codebook reassignment's two launches (mcq_vq_reassign_plan), for all levels at once: from every level's RAW frequency
+    EMA `freqs[l]` [m_l, k_l] the donor index per codeword `source[l]` (int32 [m_l, k_l]; a codeword's own index where nothing moves) and
+    the mask `refill[l]` (bool [m_l, k_l]), by the rule of `_multiCodebookQuantization.reAssignCodebook`.  `priorities`: None, or per level
+    a float32 [m_l, k_l] tensor or None -- a missing row is drawn under the generator state inside `state` (level l under {seed, offset +
+    l}, stream `REASSIGN_STREAM`: `hash_uniform` of that snapshot).  `state`: the int64 [REASSIGN_STATE_WORDS] record (include/mcquic_hip.h);
+    this launch advances its count and decides from it, `every` and `start` whether the step fires -- when it does not, or when `skip` (a
+    step's guard flag) is set on the device, nothing else is written.  Returns (source, refill): the caller's buffers, or fresh ones."""
+    who = "vq_reassign_plan"
+    fs = [_dev(f.detach(), "freq_ema") for f in freqs]
+    levels = len(fs)
+    if levels == 0 or any(f.dim() != 2 for f in fs):
+        raise ValueError(f"{who}: one [m, k] frequency tensor per level")
+    dev = fs[0].device
+    state = _reassign_state(state, who)
+    if int(every) < 1 or int(start) < 0:
+        raise ValueError(f"{who}: every >= 1 and start >= 0 are required")
+    lib = _lib.load()
+    kmax = int(lib.mcq_vq_reassign_max_k())
+    if any(int(f.shape[1]) > kmax for f in fs):
+        raise ValueError(f"{who}: a row of {max(int(f.shape[1]) for f in fs)} codewords does not fit the kernel's LDS arrays (at most {kmax})")
+    shapes = [tuple(f.shape) for f in fs]
+    source = _reassign_rows(source, shapes, torch.int32, dev, "source", who)
+    refill = _reassign_rows(refill, shapes, torch.bool, dev, "refill", who)
+    prios = [None] * levels if priorities is None else [None if p is None else _dev(p.detach(), "priority") for p in priorities]
+    if len(prios) != levels or any(p is not None and tuple(p.shape) != s for p, s in zip(prios, shapes)):
+        raise ValueError(f"{who}: `priorities` needs one [m, k] tensor (or None) per level")
+    from .guard import skip_pointer
+    flag = skip_pointer(skip, dev, who)
+    cap = int(lib.mcq_vq_max_levels())
+    with _guard(dev):
+        for l0 in range(0, levels, cap):                     # (a launch's tables hold `cap` levels; see vq_step_prologue)
+            sl = slice(l0, min(levels, l0 + cap))
+            nl = sl.stop - l0
+            check(lib.mcq_vq_reassign_plan((ctypes.c_void_p * nl)(*[f.data_ptr() for f in fs[sl]]),
+                                           (ctypes.c_void_p * nl)(*[_ptr(p) for p in prios[sl]]),
+                                           (ctypes.c_int32 * nl)(*[s[0] for s in shapes[sl]]), (ctypes.c_int32 * nl)(*[s[1] for s in shapes[sl]]),
+                                           nl, l0, int(l0 == 0), (ctypes.c_void_p * nl)(*[t.data_ptr() for t in source[sl]]),
+                                           (ctypes.c_void_p * nl)(*[t.data_ptr() for t in refill[sl]]), _ptr(state), int(every), int(start),
+                                           flag, _stream()), "mcq_vq_reassign_plan")
+    return source, refill
+
+
+def vq_reassign_scratch_floats(codebooks: Sequence[torch.Tensor]) -> int:
+    """Floats of scratch `vq_reassign_apply` needs for these codebooks: the largest group, k_l * d_l."""
+    return max(int(c.shape[1]) * int(c.shape[2]) for c in codebooks)
+
+
+def vq_reassign_apply(codebooks: Sequence[torch.Tensor], source, refill, state: torch.Tensor, every: int, start: int = 0, skip=None,
+                      changed=None, scratch: Optional[torch.Tensor] = None):
+    """The second launch (mcq_vq_reassign_apply): on a step that fires -- the same decision, from the same words -- codebook[l][g, i] =
+    the OLD codebook[l][g, source[l][g, i]] wherever refill[l][g, i], in place on the contiguous `codebooks[l]` [m_l, k_l, d_l]; donors are
+    read as they were before any move of this call (a scratch copy per group: `scratch`, `vq_reassign_scratch_floats` float32, or a
+    fresh one).  `changed[l]` (bool [m_l, k_l]) = moved by more than 1e-4 in squared distance; `state` takes moved, proportion, fired and the
+    generator's advance.  Returns `changed`: the caller's buffers, or fresh ones."""
+    who = "vq_reassign_apply"
+    cbs = [_dev(c.detach(), "codebook") for c in codebooks]
+    for c, given in zip(cbs, codebooks):
+        if c.data_ptr() != given.data_ptr() or c.dim() != 3:
+            raise ValueError(f"{who}: the codebooks must be contiguous [m, k, d] tensors (they are moved in place)")
+    levels = len(cbs)
+    if levels == 0:
+        raise ValueError(f"{who}: one codebook per level")
+    dev = cbs[0].device
+    state = _reassign_state(state, who)
+    if int(every) < 1 or int(start) < 0:
+        raise ValueError(f"{who}: every >= 1 and start >= 0 are required")
+    lib = _lib.load()
+    kmax = int(lib.mcq_vq_reassign_max_k())
+    if any(int(c.shape[1]) > kmax for c in cbs):
+        raise ValueError(f"{who}: a row of {max(int(c.shape[1]) for c in cbs)} codewords does not fit the kernel's LDS arrays (at most {kmax})")
+    shapes = [tuple(c.shape[:2]) for c in cbs]
+    source = _reassign_rows(source, shapes, torch.int32, dev, "source", who)
+    refill = _reassign_rows(refill, shapes, torch.bool, dev, "refill", who)
+    changed = _reassign_rows(changed, shapes, torch.bool, dev, "changed", who)
+    need = vq_reassign_scratch_floats(cbs)
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.float32, device=dev)
+    scratch = _dev(scratch, "scratch")
+    if scratch.numel() < need or scratch.device != dev:
+        raise ValueError(f"{who}: `scratch` must hold {need} float32 on {dev}")
+    from .guard import skip_pointer
+    flag = skip_pointer(skip, dev, who)
+    cap = int(lib.mcq_vq_max_levels())
+    codewords = sum(s[0] * s[1] for s in shapes)
+    with _guard(dev):
+        for l0 in range(0, levels, cap):
+            sl = slice(l0, min(levels, l0 + cap))
+            nl = sl.stop - l0
+            check(lib.mcq_vq_reassign_apply((ctypes.c_void_p * nl)(*[c.data_ptr() for c in cbs[sl]]),
+                                            (ctypes.c_void_p * nl)(*[t.data_ptr() for t in source[sl]]),
+                                            (ctypes.c_void_p * nl)(*[t.data_ptr() for t in refill[sl]]),
+                                            (ctypes.c_void_p * nl)(*[t.data_ptr() for t in changed[sl]]),
+                                            (ctypes.c_int32 * nl)(*[int(c.shape[0]) for c in cbs[sl]]), (ctypes.c_int32 * nl)(*[int(c.shape[1]) for c in cbs[sl]]),
+                                            (ctypes.c_int32 * nl)(*[int(c.shape[2]) for c in cbs[sl]]), nl, int(l0 == 0), int(sl.stop == levels),
+                                            levels, codewords, _ptr(scratch), _ptr(state), int(every), int(start), flag, _stream()),
+                  "mcq_vq_reassign_apply")
+    return changed
+
+
 def hash_uniform(rng: torch.Tensor, stream_id: int, shape) -> torch.Tensor:
     """The generator's draws for a tensor of `shape` (stream 0 = random drop, 1 = Gumbel noise) under the snapshot `rng`:
     exactly what the kernels use in place of a missing u_drop / u_gumbel (mcq_hash_uniform_f32)."""

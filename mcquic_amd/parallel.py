@@ -280,6 +280,18 @@ class GraphedTrainStep:
     skipped step always leaves a row, so `stats.blame()` names the tensor the guard cannot.  It only reads: parameters and every other state
     keep the bits they have without it; the constructor leaves its count, blame words, ring and shadow as they were.  Works with every
     optimizer the step accepts.  Without it not one launch changes.
+    `reassign` (a `mcquic_amd.CodebookReassign` of this model; the reference's one training hook, mcquic/train/hooks.py:100-121):
+    `reassign.step(skip=flag)` follows the frequency EMA -- the reference's forward updates the EMA and its hook runs at step finish, so
+    the NEW frequencies are the ones consulted -- and precedes the scheduler and the meter, inside the post graph when that is captured:
+    two more launches, which on a step that does not fire read the decision words and return.  On a firing step (the completed count s
+    with (s + 1) % freq == 0) the dead codewords of every level are overwritten by the most used ones, in place; the re-pack at the head
+    of the next replay packs the moved codebooks like any other update's (the packed copy and the clone its backward reads are made
+    there: no other cached operand of a codebook outlives a replay), and `invalidate()` covers eager use as it does for the optimizer's
+    update.  A step the guard skips neither fires nor counts.  Under more than one rank nothing is exchanged for it: the ranks hold the
+    same frequencies (the all-reduced counts), the same codebooks and the same generator state, so they make the same moves.  With
+    `accumulate=k` one call is one update and one count.  The constructor leaves the object's count, generator state and scalars bit for
+    bit as they were (its warm-up launches run under a set flag: nothing fires, no draw is consumed).  Without it not one launch or
+    buffer changes.
     `scheduler` (a `mcquic_amd.schedule` scheduler of this optimizer): `scheduler.step()` follows the optimizer, the EMA and the frequency
     EMA and precedes the meter -- the reference steps its scheduler after every batch and logs `get_last_lr()` afterwards
     (mcquic/train/trainer.py `_stepFinish`) --, inside the post graph when that is captured: one more launch of one workgroup that
@@ -326,9 +338,9 @@ class GraphedTrainStep:
     def __init__(self, model: torch.nn.Module, optimizer, example_x: torch.Tensor, loss_fn=None, group=None,
                  forward_kwargs: dict | None = None, warmup: int = 2, capture_post: bool = True, segments: int | None = None,
                  broadcast: bool = True, max_grad_norm: float | None = None, transform=None, ema=None, meter=None, scheduler=None,
-                 skip_nonfinite: bool = False, keep_outputs: bool = False, accumulate: int = 1, stats=None):
+                 skip_nonfinite: bool = False, keep_outputs: bool = False, accumulate: int = 1, stats=None, reassign=None):
         self.model, self.optimizer, self.group, self.ema, self.meter, self.scheduler = model, optimizer, group, ema, meter, scheduler
-        self.stats = stats
+        self.stats, self.reassign = stats, reassign
         self.accumulate, self.max_grad_norm, self.kwargs = accumulate, max_grad_norm, dict(forward_kwargs or {})
         self.keep_outputs, self.outputs = bool(keep_outputs), None      # (xHat, codes, level-0 logits) of the last replay, for `snapshot`
         self.world = dist.get_world_size(group) if dist.is_available() and dist.is_initialized() else 1
@@ -386,6 +398,8 @@ class GraphedTrainStep:
             raise ValueError(f"accumulate must be an int >= 1 (micro-batches per update), got {self.accumulate!r}")
         if self.scheduler is not None and getattr(self.scheduler, "optimizer", None) is not optimizer:
             raise ValueError("GraphedTrainStep: `scheduler` steps another optimizer's learning rates than `optimizer`'s")
+        if self.reassign is not None and not all(any(c is p for p in self.model.parameters()) for c in self.reassign.codebooks):
+            raise ValueError("GraphedTrainStep: `reassign` refills another model's codebooks than `model`'s")
         staged = all(hasattr(self.model, a) for a in ("_encoder", "_quantizer", "_decoder", "_repackStale")) and set(self.kwargs) <= {"uniforms"}
         if segments is None:
             segments = 3 if (self.world > 1 and staged) else 1
@@ -509,7 +523,8 @@ class GraphedTrainStep:
     def _prepare_update(self):
         """Everything the update needs before it can be captured: who runs the guard, then every participant's device tables and its
         kernels' first launch -- a throw-away update after which its state has its bits back (the EMA's averages and count; the meter's
-        count, shadow and ring; the schedule's last_epoch, state and rates; the statistics' count, blame words, ring and shadow)."""
+        count, shadow and ring; the schedule's last_epoch, state and rates; the statistics' count, blame words, ring and shadow; the
+        reassignment's count, generator state and scalars)."""
         if self.guard is not None:
             # who runs the guard: the step from its clip's sum of squares; else the optimizer from the partials of its own norm (Lamb,
             # SGD with max_grad_norm); else the step over the flat buffer
@@ -520,7 +535,7 @@ class GraphedTrainStep:
             self.grad_norm = self.guard.grad_norm
         if hasattr(self.optimizer, "prepare"):                # (mcquic_amd.optim.Adam / Lamb / SGD: device tables for the flat gradient views)
             self.optimizer.prepare()
-        for h in (self.ema, self.meter, self.scheduler, self.stats):
+        for h in (self.ema, self.meter, self.scheduler, self.stats, self.reassign):
             if h is not None:
                 h.prepare()
                 h.warm()
@@ -750,7 +765,7 @@ class GraphedTrainStep:
 
     def _update(self, guard=None, decides: bool = True):
         """The update, written once -- captured as the post graph, or run eagerly after the exchange: `/ world`, clip, optimizer, EMA,
-        frequency EMA, scheduler, meter (`stats` around the optimizer).  `guard`: the `StepGuard` whose flag every launch takes, or None: the launches are the ones
+        frequency EMA, codebook reassignment, scheduler, meter (`stats` around the optimizer).  `guard`: the `StepGuard` whose flag every launch takes, or None: the launches are the ones
         they have always been (every entry point selects its plain kernel for a flag that is None).  `decides`: the guard's own launches
         run here, on the all-reduced, averaged gradient (not in `_warm_guard`, whose scratch flag is set by hand)."""
         from . import ops
@@ -774,6 +789,8 @@ class GraphedTrainStep:
         if self.ema is not None:
             self.ema.update(skip=flag)
         self._apply_counts(flag)
+        if self.reassign is not None:                         # (the reference's hook runs at step finish: the NEW frequencies are consulted)
+            self.reassign.step(skip=flag)
         if self.scheduler is not None:                        # (the reference's order, trainer.py `_stepFinish`: step the scheduler, then log
             self.scheduler.step(skip=flag)                    #  get_last_lr(): the meter's `lr` column is the rate of the NEXT update)
         if self.meter is not None:
