@@ -652,6 +652,33 @@ int mcq_vq_reassign_apply(float* const* codebook /* [levels] device pointers to 
                           int32_t levels, int32_t first, int32_t last, int32_t step_levels, int64_t step_codewords, float* scratch,
                           int64_t* state, int64_t every, int64_t start, const int32_t* skip /* or NULL */, void* stream);
 
+/* The entropy coder's tables and code lengths on the device (csrc/vq_cdf.hip; callers: mcquic_amd.ops.pmf_to_quantized_cdf_dev /
+ * code_bits, EntropyCoder.deviceCDFs / codeBits).  Level tables as for mcq_freq_ema_update_f32 (host arrays of `levels` <=
+ * MCQ_VQ_MAX_LEVELS entries; a binding chunks beyond).  No atomics, no host read: equal inputs give equal bits, and both capture.
+ *   mcq_pmf_to_quantized_cdf_dev   ONE launch, one workgroup per (level, group) row: pmf[l] float32 [m_l, k_l] -> cdf[l] uint32
+ *             [m_l, k_l + 1], entry for entry what mcq_pmf_to_quantized_cdf (below) writes at precision 16 -- the same rounding, uint32
+ *             total, 64-bit division, scan, cdf[k] = 65536 and steal loop (first index among the least widths > 1), the loop evaluated
+ *             in closed form (the file's head has the argument).  `normalize`: each row is first divided by its sum, formed in double in
+ *             a fixed order and rounded once to float32 (the rule of mcq_vq_reassign_plan's row sum); else the rows are taken as given.
+ *             `status` int32 [sum m_l], (level, group) order: 0 valid; 1 a negative or non-finite element, or a scaled element or total
+ *             beyond 32 bits; 2 a zero total (with `normalize`: a row sum of zero, tested before the division); 3 no donor left -- the
+ *             host function's MCQ_EINVAL cases; that row's table is unspecified.
+ *             k_l > mcq_cdf_max_k() is MCQ_EINVAL (the row is held in LDS).
+ *   mcq_code_bits   ONE launch, one workgroup per (image, level): bits[i, level0 + l] = sum over groups g and positions of
+ *             16 - log2(cdf_g[c + 1] - cdf_g[c]) for codes[l] int64 [n, m_l, h_l, w_l] (hw[l] = h_l w_l), accumulated in double in a
+ *             fixed order; `bits` double and `error` int32 are [n, row_levels], both written by every launch: error = 1 where a code
+ *             lay outside [0, k_l) or met a bin of width 0 (such a code adds nothing), else 0.  What the single-state rANS coder
+ *             below spends beyond this sum is its 64-bit flush and its 32-bit renormalisation steps; bypass symbols are not modelled.
+ *             n <= 65535 and m_l h_l w_l <= MCQ_CODE_BITS_MAX_SYMBOLS per image and level, else MCQ_ETOOLARGE. */
+#define MCQ_CDF_MAX_K 8192
+#define MCQ_CODE_BITS_MAX_SYMBOLS 0x40000000LL
+int32_t mcq_cdf_max_k(void);
+int mcq_pmf_to_quantized_cdf_dev(const float* const* pmf /* [levels] device pointers */, uint32_t* const* cdf /* [levels] device pointers */,
+                                 const int32_t* m, const int32_t* k, int32_t levels, int32_t normalize, int32_t* status, void* stream);
+int mcq_code_bits(const int64_t* const* codes /* [levels] device pointers */, const uint32_t* const* cdf /* [levels] device pointers */,
+                  const int32_t* m, const int32_t* k, const int32_t* hw, int32_t levels, int32_t n, int32_t level0, int32_t row_levels,
+                  double* bits, int32_t* error, void* stream);
+
 /* Per-step training telemetry kept on the device (csrc/step_meter.hip; host mirror mcquic_amd.monitor.StepMeter): what the
  * reference's trainer reports after an update (mcquic/train/trainer.py:423-441, 463-491) as one float32 row per step in a ring
  * buffer, written by two launches that read every per-step value through a device pointer.  Level tables as for

@@ -207,6 +207,14 @@ class BaseCompressor(nn.Module):
     def NormalizedFreq(self):
         return self._quantizer.NormalizedFreq
 
+    def deviceCDFs(self, normalize: bool = False) -> List[torch.Tensor]:
+        """The entropy coder's tables as uint32 tensors on the device (`EntropyCoder.deviceCDFs`)."""
+        return self._quantizer._entropyCoder.deviceCDFs(normalize)
+
+    def codeBits(self, codes: List[torch.Tensor], **kwargs) -> torch.Tensor:
+        """double [n, levels]: what the coder's tables charge for `codes`, computed on the device (`EntropyCoder.codeBits`)."""
+        return self._quantizer._entropyCoder.codeBits(codes, **kwargs)
+
     @property
     def CodeUsage(self):
         return torch.cat(list((freq > 1e-6).flatten() for freq in self._quantizer.NormalizedFreq)).float().mean()

@@ -237,6 +237,7 @@ class EntropyCoder(nn.Module):
         self._normalizedFreq = None
         self._cdfs = None
         self._tables = None
+        self.__dict__["_devEpoch"] = self.__dict__.get("_devEpoch", 0) + 1      # (the device tables keep their buffers, not their stamp)
 
     def _stale(self) -> bool:
         key = tuple((tensor_version(f), f.data_ptr()) for f in self._freqEMA)
@@ -281,6 +282,65 @@ class EntropyCoder(nn.Module):
             if n != newN:
                 raise RuntimeError(info + "Now `n` is inconsisitent.")
         return n, m
+
+    # ---- the same tables, and what they charge for a batch of codes, on the device (csrc/vq_cdf.hip) --------------------------------
+    @torch.no_grad()
+    def deviceCDFs(self, normalize: bool = False) -> List[torch.Tensor]:
+        """The tables of `CDFs` as uint32 [m_l, k_l + 1] tensors on the coder's device, built there in ONE launch for all levels and
+        groups (`ops.pmf_to_quantized_cdf_dev`) -- no host loop, no host read.  normalize=False: from the rows `CDFs` uses (`_freqEMA`
+        divided by its ATen float32 row sum), so the tables equal `CDFs` entry for entry.  normalize=True: the kernel divides the raw
+        `_freqEMA` rows itself (row sum in double, rounded once to float32), so the call is a single launch and captures into a graph;
+        that sum can differ from ATen's in its last place, and the tables with it.  Cached, and stale when `CDFs` is: after an EMA
+        update, `resetFreqAndCDF`, or a write to `_freqEMA`.  The buffers are kept across rebuilds; while a stream is capturing the
+        launch is always issued.  Invalid rows do not raise here: `deviceCDFStatus` holds one int32 per (level, group) row."""
+        from .. import ops
+        # the stamp the tables were built under is kept with them and compared here, apart from `_key`: `_stale` (CDFs, NormalizedFreq,
+        # compress) consumes that one, and a write to `_freqEMA` that the host side has seen first must still be seen here
+        stamp = (tuple((tensor_version(f), f.data_ptr()) for f in self._freqEMA), self.__dict__.get("_devEpoch", 0))
+        normalize = bool(normalize)
+        device = self._freqEMA[0].device
+        capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+        slots = self.__dict__.setdefault("_devCDF", {})
+        slot = slots.get(normalize)
+        if slot is not None and slot[1].device != device:
+            slot = None
+        if slot is not None and not capturing and slot[2] == stamp:
+            return slot[0]
+        rows = [f.detach() for f in self._freqEMA] if normalize else [f / f.sum(-1, keepdim=True) for f in self._freqEMA]
+        tables, status = ops.pmf_to_quantized_cdf_dev(rows, normalize, *(slot[:2] if slot else (None, None)))
+        slots[normalize] = (tables, status, None if capturing else stamp)       # (a captured launch has not run yet)
+        return tables
+
+    def deviceCDFStatus(self, normalize: bool = False) -> torch.Tensor:
+        """int32 [sum m_l] on the device, (level, group) order, for the tables `deviceCDFs(normalize)` last built: 0 = valid; non-zero = the
+        rows `pmfToQuantizedCDF` rejects (`ops.CDF_BAD_ELEMENT`, `ops.CDF_ZERO_TOTAL`, `ops.CDF_NO_DONOR`)."""
+        self.deviceCDFs(normalize)
+        return self.__dict__["_devCDF"][bool(normalize)][1]
+
+    @torch.no_grad()
+    def codeBits(self, codes: List[torch.Tensor], normalize: bool = False, cdfs: Optional[List[torch.Tensor]] = None,
+                 out: Optional[torch.Tensor] = None, error: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """codes: level-length list of int64 [n, m, h, w] on the device -> double [n, levels]: per image and level the sum over groups and
+        positions of 16 - log2(cdf[c + 1] - cdf[c]) under `deviceCDFs(normalize)` (or the tables given as `cdfs`), in ONE launch with
+        nothing copied to the host (`ops.code_bits`).  This is what the coder's 16-bit tables charge for the codes; the byte stream of
+        `compress` is longer by the rANS state's flush and renormalisation granularity only (tests/test_gpu_code_bits_vs_coder.py
+        derives the interval).  The coder's bypass path (a symbol at or beyond a table's sentinel slot, which no code index in [0, k)
+        reaches) is NOT modelled: a code outside [0, k) adds nothing and sets `codeBitsError()`.  Same shape checks and errors as
+        `compress`."""
+        from .. import ops
+        self._checkShape(codes)
+        if len(codes) != len(self._freqEMA):
+            raise RuntimeError(f"expected {len(self._freqEMA)} code levels, got {len(codes)}")
+        bits, err = ops.code_bits(codes, self.deviceCDFs(normalize) if cdfs is None else cdfs, out, error)
+        self.__dict__["_codeBitsErr"] = err
+        return bits
+
+    def codeBitsError(self) -> torch.Tensor:
+        """int32 [n, levels] on the device, from the last `codeBits` call: 1 where an image's level held a code outside [0, k)."""
+        err = self.__dict__.get("_codeBitsErr")
+        if err is None:
+            raise RuntimeError("codeBitsError: no `codeBits` call has run yet")
+        return err
 
     # ---- byte streams (entropyCoder.py:95-154) ----------------------------------------------------------------
     @torch.inference_mode()
@@ -494,6 +554,12 @@ class VariousMCoder(nn.Module):
     def resetFreqAndCDF(self):
         self._normalizedFreq = None
         self._cdfs = None
+        self.__dict__["_devEpoch"] = self.__dict__.get("_devEpoch", 0) + 1
+
+    deviceCDFs = EntropyCoder.deviceCDFs
+    deviceCDFStatus = EntropyCoder.deviceCDFStatus
+    codeBits = EntropyCoder.codeBits
+    codeBitsError = EntropyCoder.codeBitsError
 
     def updateFreqAndCDF(self):
         freq = [(f / f.sum(-1, keepdim=True)).detach().clone() for f in self._freqEMA]

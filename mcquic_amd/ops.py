@@ -1027,6 +1027,97 @@ def vq_reassign_apply(codebooks: Sequence[torch.Tensor], source, refill, state: 
     return changed
 
 
+CDF_OK, CDF_BAD_ELEMENT, CDF_ZERO_TOTAL, CDF_NO_DONOR = 0, 1, 2, 3      # the status words of mcq_pmf_to_quantized_cdf_dev
+
+
+def cdf_max_k() -> int:
+    """The longest row `pmf_to_quantized_cdf_dev` takes (mcq_cdf_max_k: the kernel holds a row in LDS)."""
+    return int(_lib.load().mcq_cdf_max_k())
+
+
+def pmf_to_quantized_cdf_dev(pmfs: Sequence[torch.Tensor], normalize: bool = False, out=None, status: Optional[torch.Tensor] = None):
+    """The 16-bit quantized CDF tables of every level and group in ONE launch (mcq_pmf_to_quantized_cdf_dev): `pmfs[l]` float32 [m_l, k_l]
+    -> uint32 [m_l, k_l + 1], entry for entry what the host function `pmfToQuantizedCDF(row, 16)` returns for each row.  `normalize`:
+    each row is first divided by its sum (formed in double in a fixed order, rounded once to float32); else the rows are taken as given.
+    Returns (tables, status): `status` int32 [sum m_l] in (level, group) order stays on the device -- 0 valid, CDF_BAD_ELEMENT a negative
+    or non-finite element, CDF_ZERO_TOTAL (with `normalize`: a row sum of zero), CDF_NO_DONOR; a row with a non-zero status leaves its table unspecified.  `out` / `status`: the
+    caller's buffers (written in place: a captured launch keeps their addresses), or fresh ones.  Rows longer than `cdf_max_k()` are a
+    ValueError."""
+    who = "pmf_to_quantized_cdf_dev"
+    ps = [_dev(p.detach(), "pmf") for p in pmfs]
+    levels = len(ps)
+    if levels == 0 or any(p.dim() != 2 or p.numel() == 0 for p in ps):
+        raise ValueError(f"{who}: one non-empty [m, k] probability tensor per level")
+    dev = ps[0].device
+    lib = _lib.load()
+    kmax = int(lib.mcq_cdf_max_k())
+    if any(int(p.shape[1]) > kmax for p in ps):
+        raise ValueError(f"{who}: a row of {max(int(p.shape[1]) for p in ps)} symbols does not fit the kernel's LDS array (at most {kmax})")
+    shapes = [(int(p.shape[0]), int(p.shape[1]) + 1) for p in ps]
+    out = _reassign_rows(out, shapes, torch.uint32, dev, "out", who)
+    rows = sum(s[0] for s in shapes)
+    if status is None:
+        status = torch.empty(rows, dtype=torch.int32, device=dev)
+    elif not (status.is_cuda and status.device == dev and status.dtype == torch.int32 and status.numel() == rows and status.is_contiguous()):
+        raise ValueError(f"{who}: `status` must be {rows} contiguous int32 words on {dev} (one per row, written in place)")
+    cap = int(lib.mcq_vq_max_levels())
+    with _guard(dev):
+        row0 = 0
+        for l0 in range(0, levels, cap):                     # (a launch's tables hold `cap` levels; see vq_step_prologue)
+            sl = slice(l0, min(levels, l0 + cap))
+            nl = sl.stop - l0
+            check(lib.mcq_pmf_to_quantized_cdf_dev((ctypes.c_void_p * nl)(*[p.data_ptr() for p in ps[sl]]),
+                                                   (ctypes.c_void_p * nl)(*[t.data_ptr() for t in out[sl]]),
+                                                   (ctypes.c_int32 * nl)(*[s[0] for s in shapes[sl]]),
+                                                   (ctypes.c_int32 * nl)(*[s[1] - 1 for s in shapes[sl]]), nl, int(bool(normalize)),
+                                                   status.data_ptr() + 4 * row0, _stream()), "mcq_pmf_to_quantized_cdf_dev")
+            row0 += sum(s[0] for s in shapes[sl])
+    return out, status
+
+
+def code_bits(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor], out: Optional[torch.Tensor] = None,
+              error: Optional[torch.Tensor] = None):
+    """What the tables charge for the codes, per image and level, in ONE launch (mcq_code_bits): bits[i, l] = the sum over groups and
+    positions of 16 - log2(cdf[c + 1] - cdf[c]) for `codes[l]` int64 [n, m_l, h_l, w_l] under `cdfs[l]` uint32 [m_l, k_l + 1], in double
+    in a fixed order (equal inputs give equal bits).  Returns (bits double [n, levels], error int32 [n, levels]), both on the device:
+    error[i, l] = 1 where a code lay outside [0, k_l) or met an empty bin -- such a code adds nothing.  `out` / `error`: the caller's
+    buffers, or fresh ones."""
+    who = "code_bits"
+    cs = [_dev(c.detach(), "codes", torch.int64) for c in codes]
+    ts = [_dev(t, "cdf", torch.uint32) for t in cdfs]
+    levels = len(cs)
+    if levels == 0 or len(ts) != levels:
+        raise ValueError(f"{who}: one code tensor and one table per level")
+    n = int(cs[0].shape[0])
+    for c, t in zip(cs, ts):
+        if c.dim() != 4 or t.dim() != 2 or int(c.shape[0]) != n or int(c.shape[1]) != int(t.shape[0]) or int(t.shape[1]) < 2 or c.numel() == 0:
+            raise ValueError(f"{who}: codes [n, m, h, w] need a table [m, k + 1] per level (got {tuple(c.shape)} and {tuple(t.shape)})")
+        if c.device != cs[0].device or t.device != cs[0].device:
+            raise ValueError(f"{who}: codes and tables must live on one device")
+        if c[0].numel() > 1 << 30:                              # MCQ_CODE_BITS_MAX_SYMBOLS
+            raise ValueError(f"{who}: more than 2^30 codes per image and level")
+    dev = cs[0].device
+    if out is None:
+        out = torch.empty((n, levels), dtype=torch.float64, device=dev)
+    if error is None:
+        error = torch.empty((n, levels), dtype=torch.int32, device=dev)
+    for t, dt, name in ((out, torch.float64, "out"), (error, torch.int32, "error")):
+        if not (t.is_cuda and t.device == dev and t.dtype == dt and tuple(t.shape) == (n, levels) and t.is_contiguous()):
+            raise ValueError(f"{who}: `{name}` must be a contiguous {dt} [{n}, {levels}] tensor on {dev} (it is written in place)")
+    lib = _lib.load()
+    cap = int(lib.mcq_vq_max_levels())
+    with _guard(dev):
+        for l0 in range(0, levels, cap):
+            sl = slice(l0, min(levels, l0 + cap))
+            nl = sl.stop - l0
+            check(lib.mcq_code_bits((ctypes.c_void_p * nl)(*[c.data_ptr() for c in cs[sl]]), (ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts[sl]]),
+                                    (ctypes.c_int32 * nl)(*[int(c.shape[1]) for c in cs[sl]]),
+                                    (ctypes.c_int32 * nl)(*[int(t.shape[1]) - 1 for t in ts[sl]]),
+                                    (ctypes.c_int32 * nl)(*[int(c.shape[2]) * int(c.shape[3]) for c in cs[sl]]), nl, n, l0, levels,
+                                    _ptr(out), _ptr(error), _stream()), "mcq_code_bits")
+    return out, error
+
+
 def hash_uniform(rng: torch.Tensor, stream_id: int, shape) -> torch.Tensor:
     """The generator's draws for a tensor of `shape` (stream 0 = random drop, 1 = Gumbel noise) under the snapshot `rng`:
     exactly what the kernels use in place of a missing u_drop / u_gumbel (mcq_hash_uniform_f32)."""

@@ -70,14 +70,21 @@ def ideal_bpp(histograms: Sequence[torch.Tensor], total_pixels: int) -> float:
 
 
 @torch.inference_mode()
-def validate(model, images: torch.Tensor, group=None, msssim: bool = True, gather: bool = True) -> torch.Tensor:
+def validate(model, images: torch.Tensor, group=None, msssim: bool = True, gather: bool = True, bits: str = "coded") -> torch.Tensor:
     """images: this rank's shard, fp32 [n, 3, h, w] in [-1, 1].  Returns float64 rows [psnr_db, ms_ssim_db, bpp] for ALL
     images (rank order) -- the [psnr, ms_ssim, bits] statistics of the reference's validator (validator.py:40-58).
     `msssim=False` fills the MS-SSIM column with NaN (the metric is undefined for sides <= 160 pixels); `gather=False`
-    returns this rank's rows only."""
+    returns this rank's rows only.  `bits`: "coded" takes bpp from the byte streams of `compress` (codes to the host, the rANS coder,
+    and back through `decompress`); "estimated" runs `encode` / `decode` and takes bpp from `codeBits`, what the coder's tables charge
+    for the codes (lower than the coded figure by the streams' flush and renormalisation words only) -- nothing leaves the device
+    but the result rows."""
+    if bits not in ("coded", "estimated"):
+        raise ValueError(f"validate: bits must be 'coded' or 'estimated', got {bits!r}")
     if images.shape[0] == 0:                                  # an empty shard still takes part in the gather
         rows = torch.empty((0, 3), dtype=torch.float64, device=images.device)
         return parallel.gather_image_stats(rows, group) if gather else rows
+    if bits == "estimated":
+        return _validate_estimated(model, images, group, msssim, gather)
     codes, binaries, headers = model.compress(images)
     restored = model.decompress(binaries, headers)
     a, b = ops.detransform(images.contiguous()), ops.detransform(restored.contiguous())
@@ -85,5 +92,21 @@ def validate(model, images: torch.Tensor, group=None, msssim: bool = True, gathe
     s = ms_ssim_db(a, b).double() if msssim else torch.full_like(p, float("nan"))
     pixels = images.shape[-2] * images.shape[-1]
     bpp = torch.tensor([sum(len(s_) for s_ in bi) * 8 / pixels for bi in binaries], dtype=torch.float64, device=images.device)
+    rows = torch.stack([p, s, bpp], 1)
+    return parallel.gather_image_stats(rows, group) if gather else rows
+
+
+def _validate_estimated(model, images: torch.Tensor, group, msssim: bool, gather: bool) -> torch.Tensor:
+    """`validate` with the size of the codes taken from the coder's tables on the device.  The restored images are those of the coded path
+    (the coder is lossless: `decompress` decodes to these codes), cropped from the padded reconstruction as `decompress` crops."""
+    codes = model.encode(images)
+    restored = model.decode(codes)
+    h, w = images.shape[-2], images.shape[-1]
+    top, left = (restored.shape[-2] - h) // 2, (restored.shape[-1] - w) // 2
+    restored = restored[..., top:top + h, left:left + w]
+    a, b = ops.detransform(images.contiguous()), ops.detransform(restored.contiguous())
+    p = psnr(a, b)
+    s = ms_ssim_db(a, b).double() if msssim else torch.full_like(p, float("nan"))
+    bpp = model.codeBits(codes).sum(-1) / float(h * w)
     rows = torch.stack([p, s, bpp], 1)
     return parallel.gather_image_stats(rows, group) if gather else rows
