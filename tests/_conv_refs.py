@@ -14,7 +14,18 @@ A launch computes  out = epilogue(v, sides),  v = conv(prologue(x)) + bias.  The
 
 An epilogue is the keyword set `ops._conv_desc` takes, split into `ep` (its flags and res_scale) and `sides` (its tensors), or one of
 the three backward pairs ep = {"bwd": "gdn" | "igdn" | "gate"} with sides {"m", "g"} (the factor and the incoming gradient).
-Every function returns the pair (y, second output or None): the second output is the SiLU twin or the backward pair's d s."""
+Every function returns the pair (y, second output or None): the second output is the SiLU twin or the backward pair's d s.
+
+The fused 1x1 layer behind a 3x3 convolution (the POST section of conv_mfma_kernel: MCQ_CONV_POST_GDN / _IGDN / _GATE) is a second
+contraction on top of v and has references of its own at the end of this file:
+
+  post64 / post_f32 / post_scale64       the close on a given v: s = b1 + w1 @ v^2 (GDN / IGDN) or b1 + w1 @ (v + res_scale res) (gate) and
+                                         out = v / sqrt(s) | v sqrt(s) | mul sigmoid(s) + id; the float32 form sums s as ONE chain from
+                                         the bias over all 128 channels in the kernel's channel order (POST_ORDER)
+  to_subpixel_rows / from_subpixel_rows  the row order of a [512, Cin, 3, 3] layer whose four 128-row tiles are the four sub-pixels of
+                                         a PixelShuffle(2) store, and the way back from such a layer's output to the shuffled map
+  POST_GEOMS / post_problem / post_layer the seeded inputs of tests/test_gpu_conv_post_epilogues.py (tests/test_conv_refs.py checks
+                                         the same ones on the CPU)"""
 import torch
 import torch.nn.functional as F
 
@@ -201,3 +212,171 @@ def rel_err(got, want64, scale64) -> float:
     """max |got - want| / scale; a scale of exactly zero (an output whose every term is zero) counts as the smallest normal."""
     assert torch.isfinite(got).all(), "non-finite result"
     return float(((got.double() - want64).abs() / scale64.clamp_min(R.TINY)).max())
+
+
+# ---- the fused 1x1 layer behind a 3x3 convolution (MCQ_CONV_POST_*) ------------------------------------------------------------------------
+POST_C = 128
+# the kernel contracts over the accumulator registers in THEIR order: k-step t = 16 mb + r takes the channels c = 32 mb + (r & 3) + 8 (r >> 2)
+# and c + 4 (the two k-slots of a 32x32x2 MFMA)
+POST_ORDER = tuple(ch for mb in range(4) for r in range(16) for ch in (32 * mb + (r & 3) + 8 * (r >> 2), 32 * mb + (r & 3) + 8 * (r >> 2) + 4))
+assert sorted(POST_ORDER) == list(range(POST_C))
+
+
+def _post_w(w1):
+    assert w1.numel() == POST_C * POST_C and tuple(w1.shape[:2]) == (POST_C, POST_C)
+    return w1.reshape(POST_C, POST_C)
+
+
+def _mix64(w, b1, u):
+    """b1 + w @ u over the channel axis of u [n, 128, h, w] in float64 (a plain contraction, no convolution routine)."""
+    s = torch.einsum("oc,nchw->nohw", w, u)
+    return s if b1 is None else s + b1.double().reshape(1, POST_C, 1, 1)
+
+
+def post64(v, kind, w1, b1, sides=None, res_scale=1.0):
+    """The definition in float64 on the producing convolution's value `v` [n, 128, h, w] (bias included, residual not yet added; any
+    dtype, taken as exact) -> (out, twin or None): the twin, silu(out), belongs to the gate only."""
+    v, w = v.double(), _post_w(w1).double()
+    sd = {k: t.double() for k, t in (sides or {}).items()}
+    if kind in ("gdn", "igdn"):
+        s = _mix64(w, b1, v * v)
+        return (v * torch.sqrt(s) if kind == "igdn" else v / torch.sqrt(s)), None
+    assert kind == "gate"
+    if "res" in sd:
+        v = v + R.f32(res_scale).double() * sd["res"]
+    out = sd["gate_mul"] * torch.sigmoid(_mix64(w, b1, v)) + sd["gate_id"]
+    return out, R.silu64(out)
+
+
+def post_f32(v, kind, w1, b1, sides=None, res_scale=1.0, chunk=8192):
+    """The same with one float32 rounding per operation, in the kernel's order: + res_scale * res, then s as ONE chain that starts
+    from the 1x1 layer's bias (0 without one) and adds the rounded products w1[o, c] u[c] one by one in POST_ORDER, then the close
+    (correctly rounded square root and quotient; the gate and the twin as R.gate_f32 / R.silu_f32)."""
+    sides = sides or {}
+    assert v.dtype == F32 and w1.dtype == F32 and all(t.dtype == F32 for t in sides.values())
+    w = _post_w(w1)
+    n, c, h, wd = v.shape
+    assert c == POST_C
+    if kind == "gate" and "res" in sides:
+        v = v + R.f32(res_scale) * sides["res"]
+    u = (v * v if kind in ("gdn", "igdn") else v).permute(1, 0, 2, 3).reshape(POST_C, -1)          # [channel, pixel]
+    s = torch.empty_like(u)
+    start = torch.zeros(POST_C, dtype=F32) if b1 is None else b1.to(F32)
+    for lo in range(0, u.shape[1], chunk):                          # (pixel chunks that stay in the cache; the chain is per element)
+        uc = u[:, lo:lo + chunk]
+        acc = start.reshape(POST_C, 1).repeat(1, uc.shape[1])
+        tmp = torch.empty_like(acc)
+        for ch in POST_ORDER:
+            torch.mul(w[:, ch:ch + 1], uc[ch:ch + 1, :], out=tmp)
+            acc.add_(tmp)
+        s[:, lo:lo + chunk] = acc
+    s = s.reshape(POST_C, n, h, wd).permute(1, 0, 2, 3).contiguous()
+    if kind == "gdn":
+        return v * R.div_f32(1.0, R.sqrt_f32(s)), None
+    if kind == "igdn":
+        return v * R.sqrt_f32(s), None
+    out = R.gate_f32(sides["gate_mul"], s, sides["gate_id"])
+    return out, R.silu_f32(out)
+
+
+def post_scale64(v64, vscale64, kind, w1, b1, sides=None, res_scale=1.0):
+    """What the two outputs are accurate relative to when v is accurate relative to `vscale64` (never below |v|): s carries the
+    magnitude sum of its chain, |b1| + |w1| @ |v|^p, and what v's own error does to it (|w1| @ 2 |v| vscale for the squares,
+    |w1| @ vscale for the gate, whose v first takes |res_scale res| into its scale); the close carries that through its derivative
+    in s, adds v's own scale through its derivative in v (GDN / IGDN) or the magnitudes of the gate's two addends, and is never
+    accurate beyond its own magnitude.  The twin: the output's scale through |silu'|, never below |silu(out)|."""
+    v, w = v64.double(), _post_w(w1).double().abs()
+    vs = torch.maximum(vscale64.double(), v.abs())
+    sd = {k: t.double() for k, t in (sides or {}).items()}
+    ab = None if b1 is None else b1.double().abs()
+    out, _ = post64(v, kind, w1, b1, sides, res_scale)
+    if kind in ("gdn", "igdn"):
+        s = _mix64(_post_w(w1).double(), b1, v * v)
+        ss = _mix64(w, ab, v * v) + _mix64(w, None, 2.0 * v.abs() * vs)
+        if kind == "gdn":                                   # v s^-1/2
+            sc = vs * s ** -0.5 + 0.5 * v.abs() * s ** -1.5 * ss
+        else:                                               # v s^1/2
+            sc = vs * s ** 0.5 + 0.5 * v.abs() * s ** -0.5 * ss
+        return torch.maximum(sc, out.abs()), None
+    if "res" in sd:
+        add = R.f32(res_scale).double() * sd["res"]
+        v, vs = v + add, vs + add.abs()
+        vs = torch.maximum(vs, v.abs())
+    sg = torch.sigmoid(_mix64(_post_w(w1).double(), b1, v))
+    ss = _mix64(w, ab, vs)
+    m = sd["gate_mul"]
+    sc = torch.maximum(ss * m.abs() * sg * (1 - sg) + (m * sg).abs() + sd["gate_id"].abs(), out.abs())
+    return sc, torch.maximum(sc * _dsilu64(out).abs(), R.silu64(out).abs())
+
+
+# ---- the sub-pixel form: MCQ_CONV_POST_IGDN through the PixelShuffle store ---------------------------------------------------------------------
+def to_subpixel_rows(w, b):
+    """A [512, Cin, 3, 3] layer (+ bias) in sub-pixel-major row order: row 128 T + c = channel 4 c + T, so that row tile T holds the
+    128 channels PixelShuffle(2) sends to sub-pixel T = 2 dy + dx of every 2 x 2 cell."""
+    assert w.shape[0] == 4 * POST_C
+    rows = torch.tensor([4 * c + t for t in range(4) for c in range(POST_C)])
+    return w[rows].contiguous(), (None if b is None else b[rows].contiguous())
+
+
+def from_subpixel_rows(v):
+    """The output [n, 512, h, w] of a layer in sub-pixel-major row order as the shuffled map [n, 128, 2 h, 2 w]:
+    out[n, c, 2 y + dy, 2 x + dx] = v[n, 128 (2 dy + dx) + c, y, x]."""
+    n, c4, h, wd = v.shape
+    assert c4 == 4 * POST_C
+    out = torch.empty((n, POST_C, 2 * h, 2 * wd), dtype=v.dtype)
+    for t in range(4):
+        out[:, :, (t >> 1)::2, (t & 1)::2] = v[:, POST_C * t:POST_C * (t + 1)]
+    return out
+
+
+# ---- the inputs of tests/test_gpu_conv_post_epilogues.py -----------------------------------------------------------------------------------------
+# the smallest geometries at which each index of the POST section can go wrong; N = 2 (the second image's slab is addressed); `sub`: the
+# 3x3 layer has 512 rows and stores through the PixelShuffle.  The last two fill the chip (2048 wave tiles of 128 channels x 32
+# pixels: the launcher takes the fused form by its own choice there); Cin = 8 keeps their CPU references at about a second each.
+POST_GEOMS = {
+    "odd7x9": dict(n=2, cin=20, h=7, w=9, stride=1, sub=False),          # 63 pixels: two pixel blocks, the second ragged; odd width; Cin % 8 = 4
+    "s2_7x10": dict(n=2, cin=20, h=7, w=10, stride=2, sub=False),        # stride 2 from an odd and an even input side -> 4 x 5
+    "tiny3x3": dict(n=2, cin=128, h=3, w=3, stride=1, sub=False),        # smaller than one pixel block: most lanes carry the out-of-range marker
+    "sub5x7": dict(n=2, cin=20, h=5, w=7, stride=1, sub=True),           # -> 10 x 14
+    "sub3x3": dict(n=2, cin=128, h=3, w=3, stride=1, sub=True),          # -> 6 x 6
+    "chip128x256": dict(n=2, cin=8, h=128, w=256, stride=1, sub=False),
+    "chip_sub128x128": dict(n=1, cin=8, h=128, w=128, stride=1, sub=True),
+}
+POST_EXACT = ("shift1", "shift4", "shift32", "perm")
+
+
+def post_problem(gname, bias3=True):
+    """(x, w, b) of the producing 3x3 layer at geometry `gname`: seeded normal values, the weights scaled to a unit-variance v."""
+    g = POST_GEOMS[gname]
+    seed = 3000 + 11 * sum(ord(ch) for ch in gname)
+    cout = 4 * POST_C if g["sub"] else POST_C
+    x = R.randn((g["n"], g["cin"], g["h"], g["w"]), seed)
+    w = R.randn((cout, g["cin"], 3, 3), seed + 1, (g["cin"] * 9) ** -0.5)
+    return x, w, (R.randn((cout,), seed + 2, 0.1) if bias3 else None)
+
+
+def post_layer(kind, variant="dense", bias1=True):
+    """(w1 [128, 128], b1 or None) of the fused 1x1 layer.  dense: GDN / IGDN positive with b1 >= 1 (s >= 1: no bar divides by a
+    vanishing scale), the gate signed at scale 1 / sqrt(128).  One of POST_EXACT: a permutation matrix times powers of two (a cyclic
+    shift by 1, 4 or 32, or a seeded permutation) with b1 = 1 (GDN / IGDN) or 0 (gate): s has ONE non-zero term next to its bias, so
+    it is the same in any summation order, and a weight packed into the wrong lane or k-step is an O(1) error."""
+    seed = 4000 + 17 * ("gdn", "igdn", "gate").index(kind)
+    if variant == "dense":
+        if kind == "gate":
+            return R.randn((POST_C, POST_C), seed, POST_C ** -0.5), (R.randn((POST_C,), seed + 1, 0.1) if bias1 else None)
+        return R.randn((POST_C, POST_C), seed).abs() / POST_C, (R.randn((POST_C,), seed + 1, 0.5).abs() + 1.0 if bias1 else None)
+    assert variant in POST_EXACT and bias1
+    g = torch.Generator().manual_seed(seed + 5 + POST_EXACT.index(variant))
+    if variant == "perm":
+        src = torch.randperm(POST_C, generator=g)
+    else:
+        src = (torch.arange(POST_C) + int(variant[5:])) % POST_C
+    w1 = torch.zeros((POST_C, POST_C), dtype=F32)
+    w1[torch.arange(POST_C), src] = torch.exp2(torch.randint(-2, 3, (POST_C,), generator=g).float())
+    return w1, torch.full((POST_C,), 0.0 if kind == "gate" else 1.0, dtype=F32)
+
+
+def post_sides(names, shape, seed=5000):
+    """The gate's output-shaped side tensors (res, gate_mul, gate_id), seeded."""
+    scale = dict(res=1.0, gate_mul=2.0, gate_id=0.5)
+    return {k: R.randn(shape, seed + 13 * ("res", "gate_mul", "gate_id").index(k), scale[k]) for k in names}

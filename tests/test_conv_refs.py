@@ -6,7 +6,10 @@ them cannot bless a kernel with a reference that is wrong the same way.
   * out_f32 stays within a few float32 roundings of out64 in out_scale64's scale (a restatement with a wrong constant or a dropped
     res_scale would be off by far more);
   * conv_seq_f32 agrees with conv64 within the chain's standard bound (K + 1) 2^-24 conv_scale64;
-  * dgrad2_weight's filter, stored through PixelShuffle(2), is autograd's input gradient of the stride-2 convolution."""
+  * dgrad2_weight's filter, stored through PixelShuffle(2), is autograd's input gradient of the stride-2 convolution;
+  * the fused 1x1 layer's references (post64 / post_f32 / post_scale64, the sub-pixel row order) on the very inputs
+    tests/test_gpu_conv_post_epilogues.py launches: post64 is the oracle's GDN / IGDN and F.conv2d + sigmoid composed in float64,
+    post_f32 restates it, the row order reproduces F.pixel_shuffle, and every GDN / IGDN case has s >= 1."""
 import os
 
 import pytest
@@ -166,3 +169,151 @@ def test_library_is_built_without_contraction():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     with open(os.path.join(root, "mcquic_amd", "build.py")) as f:
         assert '"-ffp-contract=off"' in f.read()
+
+
+# ---- the fused 1x1 layer behind a 3x3 convolution (MCQ_CONV_POST_*) ------------------------------------------------------------------------
+POST_SMALL = ("odd7x9", "s2_7x10", "tiny3x3", "sub5x7", "sub3x3")
+POST_VARIANTS = ("dense",) + C.POST_EXACT
+
+
+def _post_v(gname, pro=None, bias3=True):
+    """(v64, its scale, the one-chain float32 v) of the GPU test's 3x3 layer at `gname`, shuffled where the geometry is."""
+    g = C.POST_GEOMS[gname]
+    x, w, b = C.post_problem(gname, bias3)
+    vs = (C.conv64(x, w, b, g["stride"], pro), C.conv_scale64(x, w, b, g["stride"], pro), C.conv_seq_f32(x, w, b, g["stride"], pro))
+    return tuple(F.pixel_shuffle(t, 2) for t in vs) if g["sub"] else vs
+
+
+def _rel64(a, b):
+    return float(((a - b).abs() / b.abs().clamp_min(1e-300)).max())
+
+
+@pytest.mark.parametrize("gname", POST_SMALL)
+@pytest.mark.parametrize("inverse", [False, True], ids=["gdn", "igdn"])
+def test_post64_is_the_oracles_gdn(gname, inverse):
+    """post64 against oracle.mcquic_ref.gdn on the GPU test's own v, w1 and b1 (the oracle's reparametrisation max(p, 0)^2 - 0 fed
+    with float64 square roots: one float64 rounding), both directions, to 1e-12 relative; s >= 1 in every case."""
+    from oracle import mcquic_ref as O
+    kind = "igdn" if inverse else "gdn"
+    v = _post_v(gname)[0]
+    zero = torch.zeros(1, dtype=torch.float64)
+    for variant in POST_VARIANTS:
+        w1, b1 = C.post_layer(kind, variant)
+        sd = {"g.gamma": torch.sqrt(w1.double()), "g.beta": torch.sqrt(b1.double()), "g.beta_reparam.eps": zero, "g.gamma_reparam.eps": zero,
+              "g.beta_reparam.lowerBound.bound": zero, "g.gamma_reparam.lowerBound.bound": zero}
+        got, twin = C.post64(v, kind, w1, b1)
+        assert twin is None and _rel64(got, O.gdn(sd, "g.", v, inverse)) <= 1e-12, f"{variant}"
+        s = F.conv2d(v * v, w1.double()[..., None, None], b1.double())
+        assert float(s.min()) >= 1.0, f"{variant}: s = {float(s.min())}"
+    w1, _ = C.post_layer(kind, "dense", bias1=False)             # (no GPU row runs GDN without its bias; the reference takes None all the same)
+    assert _rel64(C.post64(v, kind, w1, None)[0], v * F.conv2d(v * v, w1.double()[..., None, None]) ** (0.5 if inverse else -0.5)) <= 1e-12
+
+
+@pytest.mark.parametrize("gname", ["odd7x9", "tiny3x3"])
+def test_post64_gate_is_conv2d_sigmoid_composed(gname):
+    """a * sigmoid(F.conv2d(v + res_scale res, w1, b1)) + x in float64, with and without the residual and the 1x1 bias; the twin is
+    F.silu of it."""
+    v = _post_v(gname)[0]
+    sd = C.post_sides(("res", "gate_mul", "gate_id"), v.shape)
+    a, xid, res = sd["gate_mul"].double(), sd["gate_id"].double(), sd["res"].double()
+    for variant in POST_VARIANTS:
+        for bias1 in ((True, False) if variant == "dense" else (True,)):
+            w1, b1 = C.post_layer("gate", variant, bias1)
+            b1d = None if b1 is None else b1.double()
+            for scale in (None, 1.0, -1.0, 0.5):
+                sides = {k: t for k, t in sd.items() if k != "res" or scale is not None}
+                vv = v if scale is None else v + scale * res
+                want = a * torch.sigmoid(F.conv2d(vv, w1.double()[..., None, None], b1d)) + xid
+                got, twin = C.post64(v, "gate", w1, b1, sides, 1.0 if scale is None else scale)
+                assert _rel64(got, want) <= 1e-12 and _rel64(twin, F.silu(want)) <= 1e-12, f"{variant} bias1={bias1} res_scale={scale}"
+
+
+def test_post_order_is_the_accumulator_order():
+    """k-step t = 16 mb + r holds the channels 32 mb + (r & 3) + 8 (r >> 2) and that + 4: written out for the first steps of two bands."""
+    assert C.POST_ORDER[:10] == (0, 4, 1, 5, 2, 6, 3, 7, 8, 12) and C.POST_ORDER[30:34] == (27, 31, 32, 36)
+    assert sorted(C.POST_ORDER) == list(range(128))
+
+
+POST_CPU_CASES = [(k, g) for k in ("gdn", "igdn", "gate") for g in POST_SMALL if not (k == "gate" and C.POST_GEOMS[g]["stride"] == 2)]
+
+
+@pytest.mark.parametrize("kind,gname", POST_CPU_CASES, ids=[f"{k}-{g}" for k, g in POST_CPU_CASES])
+def test_post_f32_restates_post64(kind, gname):
+    """The same sanity tie as test_out_f32_restates_out64, same 64 units of roundoff: post_f32 against post64 in post_scale64's
+    scale, on the close alone (v exact) and on the whole launch (the one-chain v against conv64), at every res_scale the GPU rows
+    use.  A chain of 129 additions is bounded by 129 u of its magnitude sum and lands at 2 - 6 u; a dropped res_scale, bias or
+    square is off by a fraction of the result.  The restatement must also differ from float64 (else it is no yardstick)."""
+    v64, vscale, vseq = _post_v(gname)
+    v32 = v64.float()
+    names = ("res", "gate_mul", "gate_id") if kind == "gate" else ()
+    sd = C.post_sides(names, v64.shape)
+    for variant, scales in (("dense", (1.0, -1.0, 0.5)), ("perm", (1.0,))):
+        w1, b1 = C.post_layer(kind, variant)
+        for rs in scales if kind == "gate" else (1.0,):
+            for v_in, v_ref, sc_in in ((v32, v32, v32.abs()), (vseq, v64, vscale)):
+                want, got, scale = C.post64(v_ref, kind, w1, b1, sd, rs), C.post_f32(v_in, kind, w1, b1, sd, rs), C.post_scale64(v_ref, sc_in, kind, w1, b1, sd, rs)
+                for w, g, s in zip(want, got, scale):
+                    assert (w is None) == (g is None) == (s is None)
+                    if w is not None:
+                        assert g.dtype == torch.float32 and g.shape == w.shape == s.shape and bool((s >= w.abs()).all())
+                        assert 0.0 < C.rel_err(g, w, s) <= 64 * U, f"{variant} res_scale={rs}: {C.rel_err(g, w, s) / U:.1f} u"
+
+
+def test_post_f32_chain_is_exact_on_integers():
+    """The chain starts from the bias, squares for GDN / IGDN and takes every channel once: on integers small enough for float32 to
+    hold every partial sum, s is the float64 sum, so the result is the float32 close of that s bit for bit (a chunk boundary inside
+    the pixels included)."""
+    gen = lambda seed: torch.Generator().manual_seed(seed)          # noqa: E731
+    vi = torch.randint(1, 4, (2, 128, 3, 5), generator=gen(7)).float() * (2 * torch.randint(0, 2, (2, 128, 3, 5), generator=gen(6)).float() - 1)
+    wi, bi = torch.randint(0, 3, (128, 128), generator=gen(8)).float(), torch.randint(1, 6, (128,), generator=gen(9)).float()
+    s = (torch.einsum("oc,nchw->nohw", wi.double(), vi.double() ** 2) + bi.double().reshape(1, 128, 1, 1)).float()
+    assert torch.equal(C.post_f32(vi, "igdn", wi, bi, chunk=7)[0], vi * R.sqrt_f32(s))
+    assert torch.equal(C.post_f32(vi, "gdn", wi, None)[0], vi * R.div_f32(1.0, R.sqrt_f32(s - bi.reshape(1, 128, 1, 1))))
+    one = dict(gate_mul=torch.ones_like(vi), gate_id=torch.zeros_like(vi), res=torch.ones_like(vi))
+    wg = torch.randint(-2, 3, (128, 128), generator=gen(10)).float()
+    sg = (torch.einsum("oc,nchw->nohw", wg.double(), vi.double() - 2.0) + bi.double().reshape(1, 128, 1, 1)).float()
+    assert torch.equal(C.post_f32(vi, "gate", wg, bi, one, -2.0)[0], R.gate_f32(one["gate_mul"], sg, one["gate_id"]))
+
+
+def test_post_res_scale_and_bias_are_live():
+    """A reference that ignored res_scale, the residual or either bias would tie the GPU test to nothing: each changes post64."""
+    v = _post_v("odd7x9")[0]
+    sd = C.post_sides(("res", "gate_mul", "gate_id"), v.shape)
+    w1, b1 = C.post_layer("gate")
+    base = C.post64(v, "gate", w1, b1, sd, 1.0)[0]
+    for other in (C.post64(v, "gate", w1, b1, sd, 0.5)[0], C.post64(v, "gate", w1, b1, sd, -1.0)[0], C.post64(v, "gate", w1, None, sd, 1.0)[0],
+                  C.post64(v, "gate", w1, b1, {k: t for k, t in sd.items() if k != "res"})[0]):
+        assert float((other - base).abs().max()) > 1e-3
+
+
+@pytest.mark.parametrize("gname", ["sub5x7", "sub3x3"])
+def test_subpixel_rows_reproduce_pixel_shuffle(gname):
+    """The layer in sub-pixel-major row order, read back through from_subpixel_rows, is F.pixel_shuffle of the layer as given: in
+    float64 to the last bit (the rows are the same sums), and row 128 T + c is channel 4 c + T."""
+    x, w, b = C.post_problem(gname)
+    ws, bs = C.to_subpixel_rows(w, b)
+    assert ws.shape == w.shape and bs.shape == b.shape
+    for t, c in ((0, 0), (1, 0), (2, 5), (3, 127)):
+        assert torch.equal(ws[128 * t + c], w[4 * c + t]) and bs[128 * t + c] == b[4 * c + t]
+    want = F.pixel_shuffle(C.conv64(x, w, b), 2)
+    assert torch.equal(C.from_subpixel_rows(C.conv64(x, ws, bs)), want)
+    assert C.to_subpixel_rows(w, None)[1] is None
+    v = R.randn((2, 512, 3, 5), 3)
+    rows = C.to_subpixel_rows(v.transpose(0, 1), None)[0].transpose(0, 1)
+    assert torch.equal(C.from_subpixel_rows(rows), F.pixel_shuffle(v, 2))
+
+
+def test_post_exact_layers_are_permutations_times_powers_of_two():
+    for kind in ("gdn", "igdn", "gate"):
+        seen = []
+        for variant in C.POST_EXACT:
+            w1, b1 = C.post_layer(kind, variant)
+            nz = w1 != 0
+            assert bool((nz.sum(0) == 1).all()) and bool((nz.sum(1) == 1).all())
+            mant, _ = torch.frexp(w1[nz])
+            assert bool((mant == 0.5).all()) and bool((b1 == (0.0 if kind == "gate" else 1.0)).all())
+            src = nz.float().argmax(1)
+            if variant.startswith("shift"):
+                assert torch.equal(src, (torch.arange(128) + int(variant[5:])) % 128)
+            seen.append(src)
+        assert not any(torch.equal(seen[3], s) for s in seen[:3])

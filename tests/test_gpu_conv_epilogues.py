@@ -3,7 +3,8 @@ torch / autograd on the CPU by tests/test_conv_refs.py).
 
 conv_mfma_kernel's epilogue is six separately written paths (three-phase band epilogue, pixel-pair epilogues, the run-time-flag path
 with plain and with PixelShuffle stores, the three backward pairs, all of them again behind the split-K reduction) and conv_t16_kernel
-carries a seventh.  The tests elsewhere hold them at `max |err| <= 2e-6 max |ref|` on the launcher's own tile, which a wrong operand
+carries a seventh.  (An eighth, the POST section of conv_mfma_kernel -- the fused 1x1 layer behind a 3x3 convolution, MCQ_CONV_POST_* --
+is pinned by the same method in tests/test_gpu_conv_post_epilogues.py, which imports this file's launch and guard helpers.)  The tests elsewhere hold them at `max |err| <= 2e-6 max |ref|` on the launcher's own tile, which a wrong operand
 in one register, a side tensor read at the unshuffled address or a dropped res_scale on one path passes.  Here every row of ROWS
 (one epilogue = one keyword set of ops._conv_desc) runs on every tile of TILES at every geometry of GEOMS, and every launch is held
 to two assertions:
