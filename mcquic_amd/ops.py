@@ -15,6 +15,9 @@ import torch
 from . import _lib
 from ._lib import (CONV_DSILU_MUL, CONV_DUAL_SILU, CONV_MUL, CONV_GATE, CONV_GDN, CONV_IGDN, CONV_RESIDUAL, CONV_SHUFFLE2, CONV_SILU_IN,
                    CONV_SILU_OUT, CONV_SQUARE_IN, CONV_WINOGRAD, CONV_WINOGRAD2D, CONV_WINOGRAD2D16, CONV_GDN_BWD, CONV_IGDN_BWD, CONV_GATE_BWD, CONV_TAPS_LR, CONV_POST_GDN, CONV_POST_IGDN, CONV_POST_GATE, ConvDesc, check)
+from ._lib import (AUG_COLUMNS, AUG_TOP, AUG_LEFT, AUG_H, AUG_W, AUG_GAMMA_MODE, AUG_GAMMA, AUG_GAIN0, AUG_GAIN2, AUG_HFLIP, AUG_VFLIP,     # noqa: F401
+                   AUG_GAIN_ROW, AUG_FALLBACK, AUG_OUTPUT, AUG_GAMMA_SRGB_TO_LINEAR, AUG_GAMMA_LINEAR_TO_SRGB, AUG_GAMMA_POWER,
+                   AUG_GAMMA_IDENTITY, AUG_OUT_NORMALIZED, AUG_OUT_CLAMPED, AUG_OUT_RAW)
 
 # OPT-IN fast path, never the default and never the headline bench: large 3x3 stride-1 layers in the Winograd F(2, 3) form
 # along x (mcq_pack_conv_weight_winograd_f32 + MCQ_CONV_WINOGRAD): 2/3 of the multiplications, float32 throughout, but not
@@ -902,8 +905,8 @@ def freq_ema_update_(freqs: Sequence[torch.Tensor], counts: torch.Tensor, ema: f
             off += size
 
 
-REASSIGN_STATE_WORDS = 7          # MCQ_REASSIGN_STATE_WORDS: count, seen, fired, moved, proportion (float32, low word), seed, offset
-REASSIGN_STREAM = 3               # MCQ_RNG_STREAM_REASSIGN: the generator stream of the drawn priorities
+REASSIGN_STATE_WORDS = _lib.MCQ_REASSIGN_STATE_WORDS    # count, seen, fired, moved, proportion (float32, low word), seed, offset
+REASSIGN_STREAM = _lib.MCQ_RNG_STREAM_REASSIGN          # the generator stream of the drawn priorities
 
 
 def _reassign_state(state: torch.Tensor, who: str) -> torch.Tensor:
@@ -1094,7 +1097,7 @@ def code_bits(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor], out: 
             raise ValueError(f"{who}: codes [n, m, h, w] need a table [m, k + 1] per level (got {tuple(c.shape)} and {tuple(t.shape)})")
         if c.device != cs[0].device or t.device != cs[0].device:
             raise ValueError(f"{who}: codes and tables must live on one device")
-        if c[0].numel() > 1 << 30:                              # MCQ_CODE_BITS_MAX_SYMBOLS
+        if c[0].numel() > _lib.MCQ_CODE_BITS_MAX_SYMBOLS:
             raise ValueError(f"{who}: more than 2^30 codes per image and level")
     dev = cs[0].device
     if out is None:
@@ -1532,11 +1535,8 @@ def code_image(codes: torch.Tensor, keep: Optional[int] = None, out: Optional[to
 
 
 # ---- the training input transform (csrc/augment.hip) -----------------------------------------------------------------------------
-AUG_COLUMNS = 16
-(AUG_TOP, AUG_LEFT, AUG_H, AUG_W, AUG_GAMMA_MODE, AUG_GAMMA, AUG_GAIN0, AUG_GAIN2, AUG_HFLIP, AUG_VFLIP, AUG_GAIN_ROW,
- AUG_FALLBACK, AUG_OUTPUT) = range(13)                                 # the MCQ_AUG_* columns of include/mcquic_hip.h
-AUG_GAMMA_SRGB_TO_LINEAR, AUG_GAMMA_LINEAR_TO_SRGB, AUG_GAMMA_POWER, AUG_GAMMA_IDENTITY = range(4)
-AUG_OUT_NORMALIZED, AUG_OUT_CLAMPED, AUG_OUT_RAW = range(3)     # what follows the gains: clamp + (v - 0.5) / 0.5, the clamp alone, neither
+# (the AUG_* columns, gamma modes and outputs of the decision table are the header's MCQ_AUG_*, imported from _lib above;
+#  AUG_OUT_*: what follows the gains -- clamp + (v - 0.5) / 0.5, the clamp alone, neither)
 
 
 def augment_identity_params(n: int, src_size, device=None) -> torch.Tensor:
