@@ -679,6 +679,46 @@ int mcq_code_bits(const int64_t* const* codes /* [levels] device pointers */, co
                   const int32_t* m, const int32_t* k, const int32_t* hw, int32_t levels, int32_t n, int32_t level0, int32_t row_levels,
                   double* bits, int32_t* error, void* stream);
 
+/* The rANS coder itself on the device (csrc/rans_dev.hip; callers: mcquic_amd.ops.rans_encode_dev / rans_decode_dev,
+ * EntropyCoder.compressDevice / decompressDevice): the byte streams of mcq_rans_encode_with_indexes (below), bit for bit -- 64-bit
+ * state, L = 2^31, 16-bit precision, symbols in reverse, 32-bit words backwards, two flush words -- in integer arithmetic only.  Level
+ * tables as for mcq_code_bits: codes[l] int64 [n, m_l, h_l, w_l] (hw[l] = h_l w_l), cdf[l] uint32 [m_l, k_l + 1] (the tables of
+ * mcq_pmf_to_quantized_cdf_dev), host arrays of `levels` <= MCQ_VQ_MAX_LEVELS entries; a binding chunks beyond, naming its first
+ * level among the `row_levels` levels of the batch as `level0`.  One stream per (image, level): the symbols are codes[l][i] flattened,
+ * [m, h, w] order, the group index selecting the table.  Stream s = i * row_levels + level0 + l: image-major, the order of
+ * `binaries[n][level]`.  No kernel reads back to the host, uses atomics or allocates: equal inputs give equal bytes, and all capture.
+ *   mcq_rans_encode_dev   ONE launch, one workgroup per stream, into its slot of `scratch` [n row_levels, cap_bytes], filled from the
+ *             slot's END: `sizes` int64 [n row_levels] = the stream's bytes (a multiple of 4), `status` int32 [n row_levels].  A code
+ *             outside [0, k_l) or a bin of width 0 (as a uint16: the host's `Sym`) is MCQ_RANS_BAD_SYMBOL -- the host coder's
+ *             MCQ_EINVAL -- found before anything is indexed with it; that stream's size is 0.  cap_bytes: a multiple of 4, at least
+ *             4 (m_l h_l w_l + 2) for every level (a symbol emits at most one word, the flush two), else MCQ_EINVAL.
+ *   mcq_rans_pack_dev     two launches: offsets int64 [streams + 1] = the exclusive scan of `sizes` (one workgroup), then every stream
+ *             copied from its slot to blob + offsets[s] (one workgroup per stream).  `offsets` and `blob` are what leaves the device.
+ *             A stream that would pass blob_bytes is not copied: give the blob the sum of the worst cases, 4 (m_l h_l w_l + 2) per stream.
+ *   mcq_rans_decode_dev   ONE launch, one wave per stream: stream s is blob[offsets[s], offsets[s + 1]) and decodes straight into
+ *             codes[l][i] as int64.  The stream is untrusted input: a size below 8 bytes or not a multiple of 4, offsets that decrease
+ *             or reach beyond blob_bytes, running out of words, and a table whose bins do not increase are
+ *             MCQ_RANS_BAD_STREAM for that stream only, which leaves its outputs ZEROED; every read of a stream word is bounded by
+ *             the stream's own extent, itself checked against blob_bytes first.
+ * NOT on the device: the 4-bit bypass digits (a value at or beyond the table's sentinel slot).  With cdf_sizes = k + 2 over k + 1
+ * entries, as the product passes them, no code in [0, k) reaches the sentinel; such a code is the status word here.
+ * k_l <= MCQ_CDF_MAX_K (the decoder holds a table in LDS; MCQ_EINVAL), n <= 65535 and m_l h_l w_l <= MCQ_RANS_DEV_MAX_SYMBOLS per
+ * stream, else MCQ_ETOOLARGE.  MCQ_RANS_DEV_CHUNK: symbols (and words) the kernels hold in LDS at a time -- what tests place their
+ * stream lengths around. */
+#define MCQ_RANS_DEV_CHUNK 1024
+#define MCQ_RANS_DEV_MAX_SYMBOLS 0x10000000LL
+#define MCQ_RANS_OK 0
+#define MCQ_RANS_BAD_SYMBOL 1
+#define MCQ_RANS_BAD_STREAM 2
+int mcq_rans_encode_dev(const int64_t* const* codes /* [levels] device pointers */, const uint32_t* const* cdf /* [levels] device pointers */,
+                        const int32_t* m, const int32_t* k, const int32_t* hw, int32_t levels, int32_t n, int32_t level0, int32_t row_levels,
+                        uint8_t* scratch, int64_t cap_bytes, int64_t* sizes, int32_t* status, void* stream);
+int mcq_rans_pack_dev(const uint8_t* scratch, int64_t cap_bytes, const int64_t* sizes, int64_t streams, uint8_t* blob, int64_t blob_bytes,
+                      int64_t* offsets, void* stream);
+int mcq_rans_decode_dev(const uint8_t* blob, int64_t blob_bytes, const int64_t* offsets, const uint32_t* const* cdf /* [levels] device pointers */,
+                        const int32_t* m, const int32_t* k, const int32_t* hw, int32_t levels, int32_t n, int32_t level0, int32_t row_levels,
+                        int64_t* const* codes /* [levels] device pointers */, int32_t* status, void* stream);
+
 /* Per-step training telemetry kept on the device (csrc/step_meter.hip; host mirror mcquic_amd.monitor.StepMeter): what the
  * reference's trainer reports after an update (mcquic/train/trainer.py:423-441, 463-491) as one float32 row per step in a ring
  * buffer, written by two launches that read every per-step value through a device pointer.  Level tables as for

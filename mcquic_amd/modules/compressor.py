@@ -249,13 +249,16 @@ class BaseCompressor(nn.Module):
                 return self._graphed("decode", lambda *c: self._decoder(self._quantizer.decode(list(c))), [c.contiguous() for c in codes])
             return self._decoder(self._quantizer.decode(codes))
 
-    def compress(self, x: torch.Tensor) -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
+    def compress(self, x: torch.Tensor, coder: str = "host") -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
+        """`coder`: "host" (the default) codes the streams with csrc/rans.cpp on host threads, "device" with csrc/rans_dev.hip where
+        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same."""
+        self._quantizer._checkCoder(coder)
         self._check(x)
         n, c, h, w = x.shape
         if n == 0:                                            # (empty shard: no streams, no headers)
             return self.encode(x), [], []
         with torch.no_grad():
-            codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x))
+            codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder)
         header = [FileHeader(__version__, self._qp, codeSize, ImageSize(height=h, width=w, channel=c)) for codeSize in codeSizes]
         return codes, binaries, header
 
@@ -272,11 +275,13 @@ class BaseCompressor(nn.Module):
                 raise RuntimeError(f"The header's code size {list(code.heights)} x {list(code.widths)} does not belong to a "
                                    f"{size.height} x {size.width} image.")
 
-    def decompress(self, binaries: List[List[bytes]], headers: List[FileHeader]) -> torch.Tensor:
+    def decompress(self, binaries: List[List[bytes]], headers: List[FileHeader], coder: str = "host") -> torch.Tensor:
+        """`coder`: "host" (the default) or "device" (`EntropyCoder.decompressDevice`), as for `compress`; the same image either way."""
+        self._quantizer._checkCoder(coder)
         if type(self)._encode_latent is BaseCompressor._encode_latent:       # (Compressor's 16x stem; Neon's geometry differs)
             self._checkHeaderGeometry(headers)
         with torch.no_grad():
-            restored = self._decoder(self._quantizer.decompress(binaries, [header.CodeSize for header in headers]))
+            restored = self._decoder(self._quantizer.decompress(binaries, [header.CodeSize for header in headers], coder))
         imageSize = headers[0].ImageSize
         H, W = restored.shape[-2], restored.shape[-1]
         h, w = imageSize.height, imageSize.width

@@ -342,6 +342,67 @@ class EntropyCoder(nn.Module):
             raise RuntimeError("codeBitsError: no `codeBits` call has run yet")
         return err
 
+    # ---- byte streams made and read on the device (csrc/rans_dev.hip) ---------------------------------------------------------------
+    @torch.no_grad()
+    def compressDevice(self, codes: List[torch.Tensor], normalize: bool = False, cdfs: Optional[List[torch.Tensor]] = None,
+                       out: Optional["DeviceStreams"] = None) -> "DeviceStreams":
+        """codes: level-length list of int64 [n, m, h, w] on the device -> the streams of `compress`, byte for byte, coded there under
+        `deviceCDFs(normalize)`, or the tables given as `cdfs` (`ops.rans_encode_dev`: three launches for all levels and images, nothing copied to the host and nothing
+        waited for, so the call captures into a graph together with `deviceCDFs(normalize=True)`).  With normalize=False the tables are
+        those of `CDFs` and the bytes those of `compress`; with normalize=True they are the bytes the host coder gives under THOSE tables.
+        A code outside [0, k) does not raise here: it sets the stream's status, which `DeviceStreams.check()` / `.tobytes()` turn into
+        `compress`'s RuntimeError.  The host coder's bypass digits are not implemented on the device (no code in [0, k) reaches them).
+        `out`: the DeviceStreams of an earlier call with codes of these shapes, whose buffers are then written in place.  Same shape
+        checks and errors as `compress`."""
+        from .. import ops
+        n, m = self._checkShape(codes)
+        if len(codes) != len(self._freqEMA):
+            raise RuntimeError(f"expected {len(self._freqEMA)} code levels, got {len(codes)}")
+        encoded = ops.rans_encode_dev(codes, self.deviceCDFs(normalize) if cdfs is None else cdfs, None if out is None else out.encoded)
+        heights, widths = [int(c.shape[2]) for c in codes], [int(c.shape[3]) for c in codes]
+        return DeviceStreams(encoded, n, len(codes), [CodeSize([m] * len(codes), heights, widths, list(self._k)) for _ in range(n)])
+
+    @torch.no_grad()
+    def decompressDevice(self, binaries, codeSizes: List[CodeSize], check: bool = True) -> List[torch.Tensor]:
+        """`decompress` with the decoder on the device (`ops.rans_decode_dev`, ONE launch): `binaries` is binaries[n][level] of host
+        `bytes` -- uploaded as one blob plus offsets -- or a `DeviceStreams`, which never leaves the device.  Returns the level-length
+        list of int64 [n, m, h, w], written by the kernel as int64.  The headers pass `_checkHeaders` first, as in `decompress`; the
+        streams are untrusted too, and one that is truncated or malformed leaves its codes zero and sets its word of `decodeStatus()`.
+        `check`: read that status back (one synchronisation) and raise `decompress`'s RuntimeError if any is set; never while a
+        stream is capturing."""
+        from .. import ops
+        onDevice = isinstance(binaries, DeviceStreams)
+        if onDevice:
+            first = self._checkHeaders([[None] * binaries.levels for _ in range(binaries.n)], codeSizes)
+            blob, offsets = binaries.blob, binaries.offsets
+        else:
+            first = self._checkHeaders(binaries, codeSizes)
+        levels = len(self._freqEMA)
+        n = len(codeSizes)
+        device = self._freqEMA[0].device
+        if device.type != "cuda":
+            raise RuntimeError(f"mcquic_amd: decompressDevice decodes with HIP kernels (the coder is on {device}); there is no CPU fallback")
+        if not onDevice:
+            flat = [bytes(b) for binary in binaries for b in binary]                # image-major: stream i * levels + l
+            lengths = torch.tensor([0] + [len(b) for b in flat], dtype=torch.int64)
+            data = b"".join(flat)
+            host = torch.frombuffer(bytearray(data), dtype=torch.uint8) if data else torch.empty(0, dtype=torch.uint8)
+            blob = host.pin_memory().to(device, non_blocking=True)
+            offsets = lengths.cumsum(0).pin_memory().to(device, non_blocking=True)
+        shapes = [(n, self._m, int(first.heights[lv]), int(first.widths[lv])) for lv in range(levels)]
+        codes, status = ops.rans_decode_dev(blob, offsets, self.deviceCDFs(), shapes)
+        self.__dict__["_decodeStatus"] = status
+        if check and not torch.cuda.is_current_stream_capturing() and bool(status.any()):
+            raise RuntimeError("Got a truncated or malformed rANS stream.")
+        return codes
+
+    def decodeStatus(self) -> torch.Tensor:
+        """int32 [n * levels] on the device, image-major, from the last `decompressDevice` call: non-zero where a stream was refused."""
+        status = self.__dict__.get("_decodeStatus")
+        if status is None:
+            raise RuntimeError("decodeStatus: no `decompressDevice` call has run yet")
+        return status
+
     # ---- byte streams (entropyCoder.py:95-154) ----------------------------------------------------------------
     @torch.inference_mode()
     def compress(self, codes: List[torch.Tensor]) -> Tuple[List[List[bytes]], List[CodeSize]]:
@@ -447,6 +508,47 @@ class EntropyCoder(nn.Module):
             out.append(host.to(device, non_blocking=True).to(torch.int64).reshape(n, self._m, h, w))
         return out
 
+
+
+class DeviceStreams:
+    """The streams of one `EntropyCoder.compressDevice` call, still on the device: `blob` (uint8; stream i * levels + l, image-major, is
+    blob[offsets[s] : offsets[s + 1]]), `offsets` (int64 [n * levels + 1]), `status` (int32 [n * levels], non-zero where a code lay
+    outside [0, k)), and `n`, `levels`, `codeSizes` (one CodeSize per image, as `compress` returns them).  `encoded` is the
+    `ops.RansEncoded` behind them, whose buffers a later `compressDevice(..., out=this)` writes in place."""
+
+    def __init__(self, encoded, n: int, levels: int, codeSizes: List[CodeSize]):
+        self.encoded = encoded
+        self.blob, self.offsets, self.status = encoded
+        self.n, self.levels, self.codeSizes = n, levels, codeSizes
+
+    def sizes(self) -> torch.Tensor:
+        """int64 [n, levels] on the device: the exact coded bytes per image and level, with nothing brought to the host."""
+        return self.encoded.sizes.view(self.n, self.levels)
+
+    def _raise(self, status: np.ndarray) -> None:
+        if status.any():
+            raise RuntimeError(f"rANS encode failed ({_lib.MCQ_EINVAL}): a code index outside [0, k), or a malformed table")
+
+    def check(self) -> None:
+        """Raises `compress`'s RuntimeError if any stream's status is set (one small copy to the host, one synchronisation)."""
+        self._raise(self.status.cpu().numpy())
+
+    def tobytes(self) -> List[List[bytes]]:
+        """binaries[n][level], as `compress` returns them: two device-to-host copies (offsets with sizes and status in one, the blob in
+        the other, both into pinned memory in stream order) and ONE synchronisation behind them.  The blob travels at its allocated,
+        worst-case length -- its used length is not known on the host until the same synchronisation.  Raises like `check()`."""
+        meta, blob = self.encoded.meta, self.blob
+        hostMeta = torch.empty(meta.shape, dtype=meta.dtype, pin_memory=True)
+        hostBlob = torch.empty(blob.shape, dtype=blob.dtype, pin_memory=True)
+        hostMeta.copy_(meta, non_blocking=True)
+        hostBlob.copy_(blob, non_blocking=True)
+        torch.cuda.current_stream(blob.device).synchronize()
+        offsets, _, status = type(self.encoded).split(hostMeta, self.n * self.levels)
+        self._raise(status.numpy())
+        offs = offsets.numpy()
+        data = hostBlob.numpy()
+        return [[data[offs[i * self.levels + lv]:offs[i * self.levels + lv + 1]].tobytes() for lv in range(self.levels)]
+                for i in range(self.n)]
 
 
 class _CompressJob:

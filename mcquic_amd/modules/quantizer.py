@@ -324,12 +324,26 @@ class BaseQuantizer(nn.Module):
         want_rng = uniforms is None and not _TORCH_RAND
         return ops.vq_step_prologue(list(coder._freqEMA), EPS, want_rng, coder.countBuffer(x.device))
 
-    def compress(self, x: torch.Tensor):
+    def _checkCoder(self, coder: str) -> bool:
+        """True for the device coder (csrc/rans_dev.hip), False for the host coder (csrc/rans.cpp), the default; same bytes either way."""
+        if coder not in ("host", "device"):
+            raise ValueError(f"coder must be 'host' or 'device', got {coder!r}")
+        if coder == "device" and not hasattr(self._entropyCoder, "compressDevice"):
+            raise NotImplementedError(f"{type(self._entropyCoder).__name__} writes raw codes, not rANS streams: it has no device coder")
+        return coder == "device"
+
+    def compress(self, x: torch.Tensor, coder: str = "host"):
+        device = self._checkCoder(coder)
         codes = self.encode(x)
+        if device:
+            streams = self._entropyCoder.compressDevice(codes)
+            return codes, streams.tobytes(), streams.codeSizes
         binaries, codeSize = self._entropyCoder.compress(codes)
         return codes, binaries, codeSize
 
-    def decompress(self, binaries, codeSize) -> torch.Tensor:
+    def decompress(self, binaries, codeSize, coder: str = "host") -> torch.Tensor:
+        if self._checkCoder(coder):
+            return self.decode(self._entropyCoder.decompressDevice(binaries, codeSize))
         return self.decode(self._entropyCoder.decompress(binaries, codeSize))
 
 
@@ -377,13 +391,13 @@ class UMGMQuantizer(BaseQuantizer):
             inputs.append(qin)
         return inputs
 
-    def compress(self, x: torch.Tensor):
+    def compress(self, x: torch.Tensor, coder: str = "host"):
         """`encode` + the entropy coder (mcquic/modules/entropyCoder.py:108-126) with the coder taken level by level: a level's codes
         leave for the host (a copy in stream order, then a host thread) as soon as they are enqueued, while the GPU computes the levels below it --
         level 0 holds three quarters of the symbols and is ready first.  Same codes, same bytes as encode() + coder.compress()."""
         from .entropyCoder import CODER_OVERLAP
-        if not (CODER_OVERLAP and x.is_cuda):
-            return super().compress(x)
+        if self._checkCoder(coder) or not (CODER_OVERLAP and x.is_cuda):     # (the device coder takes all levels in one launch)
+            return super().compress(x, coder)
         job = self._entropyCoder.beginCompress(len(self._encoders))
         codes = []
         for lv, encoder in enumerate(self._encoders):
@@ -393,13 +407,13 @@ class UMGMQuantizer(BaseQuantizer):
         binaries, codeSize = job.finish()
         return codes, binaries, codeSize
 
-    def decompress(self, binaries, codeSize) -> torch.Tensor:
+    def decompress(self, binaries, codeSize, coder: str = "host") -> torch.Tensor:
         """The coder's streams -> `decode` (entropyCoder.py:141-154) with the levels decoded on a host thread in the order the decoder
         cascade consumes them -- the last (smallest) level first: its kernels are enqueued while the larger levels are still being
         decoded."""
         from .entropyCoder import CODER_OVERLAP
-        if not (CODER_OVERLAP and self._entropyCoder._freqEMA[0].is_cuda):
-            return super().decompress(binaries, codeSize)
+        if self._checkCoder(coder) or not (CODER_OVERLAP and self._entropyCoder._freqEMA[0].is_cuda):
+            return super().decompress(binaries, codeSize, coder)
         job = self._entropyCoder.beginDecompress(binaries, codeSize)
         formerLevel = None
         for lv in reversed(range(len(self._decoders))):

@@ -1121,6 +1121,142 @@ def code_bits(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor], out: 
     return out, error
 
 
+# ---- the rANS coder on the device (csrc/rans_dev.hip): byte streams from codes and back, nothing through the host -------------------
+RANS_OK, RANS_BAD_SYMBOL, RANS_BAD_STREAM = _lib.MCQ_RANS_OK, _lib.MCQ_RANS_BAD_SYMBOL, _lib.MCQ_RANS_BAD_STREAM      # the status words
+RANS_DEV_CHUNK = _lib.MCQ_RANS_DEV_CHUNK                # symbols (and stream words) the kernels hold in LDS at a time
+
+
+class RansEncoded(tuple):
+    """What `rans_encode_dev` returns: the tuple (blob, offsets, status), and behind it the buffers a later call reuses when it is
+    handed back as `out` -- `sizes` (int64 [n * levels], the coded bytes per stream, image-major), `scratch` (the kernels' [streams, cap]
+    slots) and `meta`, the ONE allocation that `offsets`, `sizes` and `status` are views of (so one copy takes all three to the host)."""
+
+    def __new__(cls, blob, offsets, status, sizes, scratch, meta, key):
+        self = super().__new__(cls, (blob, offsets, status))
+        self.sizes, self.scratch, self.meta, self.key = sizes, scratch, meta, key
+        return self
+
+    blob = property(lambda self: self[0])
+    offsets = property(lambda self: self[1])
+    status = property(lambda self: self[2])
+
+    @staticmethod
+    def meta_words(streams: int) -> int:
+        return 2 * streams + 1 + (streams + 1) // 2
+
+    @staticmethod
+    def split(meta: torch.Tensor, streams: int):
+        """(offsets int64 [streams + 1], sizes int64 [streams], status int32 [streams]) as views of `meta` (int64 [meta_words(streams)]),
+        on whichever side it lives."""
+        return meta[:streams + 1], meta[streams + 1:2 * streams + 1], meta[2 * streams + 1:].view(torch.int32)[:streams]
+
+
+def _rans_levels(codes_shapes, ts, who: str):
+    """(n, [m_l], [k_l], [h_l w_l]) of a batch's levels against their tables, checked as the launchers check them."""
+    n = int(codes_shapes[0][0])
+    kmax = _lib.MCQ_CDF_MAX_K
+    for shp, t in zip(codes_shapes, ts):
+        if len(shp) != 4 or t.dim() != 2 or int(shp[0]) != n or int(shp[1]) != int(t.shape[0]) or int(t.shape[1]) < 2 or min(int(v) for v in shp) < 1:
+            raise ValueError(f"{who}: codes [n, m, h, w] need a table [m, k + 1] per level (got {tuple(shp)} and {tuple(t.shape)})")
+        if t.device != ts[0].device:
+            raise ValueError(f"{who}: codes and tables must live on one device")
+        if int(t.shape[1]) - 1 > kmax:
+            raise ValueError(f"{who}: a table of {int(t.shape[1]) - 1} symbols does not fit the decoder's LDS array (at most {kmax})")
+        if int(shp[1]) * int(shp[2]) * int(shp[3]) > _lib.MCQ_RANS_DEV_MAX_SYMBOLS:
+            raise ValueError(f"{who}: more than 2^28 codes per image and level")
+    if n > 65535:
+        raise ValueError(f"{who}: more than 65535 images per call")
+    return (n, [int(s[1]) for s in codes_shapes], [int(t.shape[1]) - 1 for t in ts], [int(s[2]) * int(s[3]) for s in codes_shapes])
+
+
+def rans_encode_dev(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor], out: Optional[RansEncoded] = None) -> RansEncoded:
+    """The coder's byte streams made on the device (mcq_rans_encode_dev + mcq_rans_pack_dev: three launches for all levels and images,
+    nothing read by the host, so the call captures): `codes[l]` int64 [n, m_l, h_l, w_l] under `cdfs[l]` uint32 [m_l, k_l + 1] (the
+    tables of `pmf_to_quantized_cdf_dev`) -> (blob, offsets, status).  Stream s = i * levels + l (image-major) is
+    blob[offsets[s] : offsets[s + 1]], byte for byte what the host coder writes for `codes[l][i].flatten()` with the group index
+    selecting the table; `blob` uint8 is allocated at the worst case, 4 (symbols + 2) bytes per stream, and only offsets[-1] bytes
+    of it mean anything.  `status` int32 [n * levels]: RANS_OK, or RANS_BAD_SYMBOL where a code lay outside [0, k_l) or met an empty
+    bin -- the host coder's RuntimeError -- and then the stream's size is 0.  The bypass digits of the host coder are not implemented:
+    no code in [0, k) reaches them.  `out`: the result of an earlier call with codes of these shapes (its buffers are written in place:
+    a captured launch keeps their addresses), or None for fresh ones."""
+    who = "rans_encode_dev"
+    cs = [_dev(c.detach(), "codes", torch.int64) for c in codes]
+    ts = [_dev(t, "cdf", torch.uint32) for t in cdfs]
+    levels = len(cs)
+    if levels == 0 or len(ts) != levels:
+        raise ValueError(f"{who}: one code tensor and one table per level")
+    dev = cs[0].device
+    if any(c.device != dev for c in cs) or ts[0].device != dev:
+        raise ValueError(f"{who}: codes and tables must live on one device")
+    n, ms, ks, hws = _rans_levels([tuple(c.shape) for c in cs], ts, who)
+    counts = [m * hw for m, hw in zip(ms, hws)]
+    streams = n * levels
+    cap = 4 * max(counts) + 64                               # per-stream slot, the host coder's own allowance (4 (count + 2) is the bound)
+    key = (n, tuple(tuple(c.shape[1:]) for c in cs), dev)
+    if out is None:
+        meta = torch.empty(RansEncoded.meta_words(streams), dtype=torch.int64, device=dev)
+        offsets, sizes, status = RansEncoded.split(meta, streams)
+        out = RansEncoded(torch.empty(n * sum(4 * c + 8 for c in counts), dtype=torch.uint8, device=dev), offsets, status, sizes,
+                          torch.empty(streams * cap, dtype=torch.uint8, device=dev), meta, key)
+    elif not isinstance(out, RansEncoded) or out.key != key:
+        raise ValueError(f"{who}: `out` must be the result of an earlier call with codes of these shapes on {dev} (it is written in place)")
+    lib = _lib.load()
+    limit = int(lib.mcq_vq_max_levels())
+    with _guard(dev):
+        for l0 in range(0, levels, limit):
+            sl = slice(l0, min(levels, l0 + limit))
+            nl = sl.stop - l0
+            check(lib.mcq_rans_encode_dev((ctypes.c_void_p * nl)(*[c.data_ptr() for c in cs[sl]]), (ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts[sl]]),
+                                          (ctypes.c_int32 * nl)(*ms[sl]), (ctypes.c_int32 * nl)(*ks[sl]), (ctypes.c_int32 * nl)(*hws[sl]), nl, n, l0,
+                                          levels, _ptr(out.scratch), cap, _ptr(out.sizes), _ptr(out.status), _stream()), "mcq_rans_encode_dev")
+        check(lib.mcq_rans_pack_dev(_ptr(out.scratch), cap, _ptr(out.sizes), streams, _ptr(out.blob), out.blob.numel(), _ptr(out.offsets),
+                                    _stream()), "mcq_rans_pack_dev")
+    return out
+
+
+def rans_decode_dev(blob: torch.Tensor, offsets: torch.Tensor, cdfs: Sequence[torch.Tensor], shapes: Sequence[Sequence[int]], out=None):
+    """The inverse, in ONE launch (mcq_rans_decode_dev): stream s = i * levels + l is blob[offsets[s] : offsets[s + 1]] (`blob` uint8,
+    `offsets` int64 [n * levels + 1], both on the device) and decodes under `cdfs[l]` straight into int64 [n, m_l, h_l, w_l] --
+    `shapes[l]`.  Returns (codes, status): `status` int32 [n * levels] is RANS_OK, or RANS_BAD_STREAM for a stream that is shorter than 8
+    bytes, not a multiple of 4 long, lies outside the blob, or runs out of words -- the host coder's "truncated or malformed" -- and
+    that stream's codes are ZERO; the others decode.  The streams are untrusted input and no content of `blob` or `offsets` leads to a
+    read outside them.  `out`: the (codes, status) of an earlier call with these shapes, written in place, or None for fresh ones."""
+    who = "rans_decode_dev"
+    blob = _dev(blob, "blob", torch.uint8)
+    offsets = _dev(offsets, "offsets", torch.int64)
+    ts = [_dev(t, "cdf", torch.uint32) for t in cdfs]
+    shapes = [tuple(int(v) for v in s) for s in shapes]
+    levels = len(shapes)
+    if levels == 0 or len(ts) != levels:
+        raise ValueError(f"{who}: one shape and one table per level")
+    dev = blob.device
+    if offsets.device != dev or ts[0].device != dev:
+        raise ValueError(f"{who}: the blob, its offsets and the tables must live on one device")
+    n, ms, ks, hws = _rans_levels(shapes, ts, who)
+    streams = n * levels
+    if blob.dim() != 1 or offsets.dim() != 1 or offsets.numel() != streams + 1:
+        raise ValueError(f"{who}: a flat uint8 blob and {streams + 1} int64 offsets (n * levels + 1) expected")
+    nbytes = blob.numel()
+    if nbytes == 0:                                          # (an empty blob still needs an address; every stream is refused)
+        blob = blob.new_zeros(4)
+    if out is None:
+        out = ([torch.empty(s, dtype=torch.int64, device=dev) for s in shapes], torch.empty(streams, dtype=torch.int32, device=dev))
+    codes, status = _reassign_rows(out[0], shapes, torch.int64, dev, "out", who), out[1]
+    if not (status.is_cuda and status.device == dev and status.dtype == torch.int32 and status.numel() == streams and status.is_contiguous()):
+        raise ValueError(f"{who}: `out`'s status must be {streams} contiguous int32 words on {dev} (written in place)")
+    lib = _lib.load()
+    limit = int(lib.mcq_vq_max_levels())
+    with _guard(dev):
+        for l0 in range(0, levels, limit):
+            sl = slice(l0, min(levels, l0 + limit))
+            nl = sl.stop - l0
+            check(lib.mcq_rans_decode_dev(_ptr(blob), nbytes, _ptr(offsets), (ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts[sl]]),
+                                          (ctypes.c_int32 * nl)(*ms[sl]), (ctypes.c_int32 * nl)(*ks[sl]), (ctypes.c_int32 * nl)(*hws[sl]), nl, n, l0,
+                                          levels, (ctypes.c_void_p * nl)(*[c.data_ptr() for c in codes[sl]]), _ptr(status), _stream()),
+                  "mcq_rans_decode_dev")
+    return codes, status
+
+
 def hash_uniform(rng: torch.Tensor, stream_id: int, shape) -> torch.Tensor:
     """The generator's draws for a tensor of `shape` (stream 0 = random drop, 1 = Gumbel noise) under the snapshot `rng`:
     exactly what the kernels use in place of a missing u_drop / u_gumbel (mcq_hash_uniform_f32)."""

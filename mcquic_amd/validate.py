@@ -77,14 +77,15 @@ def validate(model, images: torch.Tensor, group=None, msssim: bool = True, gathe
     returns this rank's rows only.  `bits`: "coded" takes bpp from the byte streams of `compress` (codes to the host, the rANS coder,
     and back through `decompress`); "estimated" runs `encode` / `decode` and takes bpp from `codeBits`, what the coder's tables charge
     for the codes (lower than the coded figure by the streams' flush and renormalisation words only) -- nothing leaves the device
-    but the result rows."""
-    if bits not in ("coded", "estimated"):
-        raise ValueError(f"validate: bits must be 'coded' or 'estimated', got {bits!r}")
+    but the result rows; "exact" runs `encode` / `decode` too and takes bpp from the sizes of the streams the device coder makes
+    (`EntropyCoder.compressDevice(...).sizes()`): the figure of "coded" exactly, with nothing coded on the host."""
+    if bits not in ("coded", "estimated", "exact"):
+        raise ValueError(f"validate: bits must be 'coded', 'estimated' or 'exact', got {bits!r}")
     if images.shape[0] == 0:                                  # an empty shard still takes part in the gather
         rows = torch.empty((0, 3), dtype=torch.float64, device=images.device)
         return parallel.gather_image_stats(rows, group) if gather else rows
-    if bits == "estimated":
-        return _validate_estimated(model, images, group, msssim, gather)
+    if bits != "coded":
+        return _validate_on_device(model, images, group, msssim, gather, bits)
     codes, binaries, headers = model.compress(images)
     restored = model.decompress(binaries, headers)
     a, b = ops.detransform(images.contiguous()), ops.detransform(restored.contiguous())
@@ -96,8 +97,9 @@ def validate(model, images: torch.Tensor, group=None, msssim: bool = True, gathe
     return parallel.gather_image_stats(rows, group) if gather else rows
 
 
-def _validate_estimated(model, images: torch.Tensor, group, msssim: bool, gather: bool) -> torch.Tensor:
-    """`validate` with the size of the codes taken from the coder's tables on the device.  The restored images are those of the coded path
+def _validate_on_device(model, images: torch.Tensor, group, msssim: bool, gather: bool, bits: str) -> torch.Tensor:
+    """`validate` with the size of the codes taken on the device: from the coder's tables ("estimated") or from the device coder's
+    streams ("exact": bytes * 8 / pixels in float64, the one division of the coded path).  The restored images are those of the coded path
     (the coder is lossless: `decompress` decodes to these codes), cropped from the padded reconstruction as `decompress` crops."""
     codes = model.encode(images)
     restored = model.decode(codes)
@@ -107,6 +109,11 @@ def _validate_estimated(model, images: torch.Tensor, group, msssim: bool, gather
     a, b = ops.detransform(images.contiguous()), ops.detransform(restored.contiguous())
     p = psnr(a, b)
     s = ms_ssim_db(a, b).double() if msssim else torch.full_like(p, float("nan"))
-    bpp = model.codeBits(codes).sum(-1) / float(h * w)
+    if bits == "exact":
+        streams = model._quantizer._entropyCoder.compressDevice(codes)
+        bpp = (streams.sizes().sum(-1) * 8).double() / float(h * w)
+        streams.check()                                       # an out-of-range code raises, as `compress` does on the coded path
+    else:
+        bpp = model.codeBits(codes).sum(-1) / float(h * w)
     rows = torch.stack([p, s, bpp], 1)
     return parallel.gather_image_stats(rows, group) if gather else rows
