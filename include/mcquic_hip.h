@@ -128,7 +128,11 @@ int mcq_pack_conv_weight_f32(const float* w_oihw, int32_t Cout, int32_t Cin, int
  * per filter row (g0, g1, g2) the four transformed taps (g0, (g0 + g1 + g2) / 2, (g0 - g1 + g2) / 2, g2), formed in float64
  * and rounded once, in the same [Cout/128][Cin/2 x 12][64][4] (+ 64-row copy) order.  Used with MCQ_CONV_WINOGRAD, which
  * needs Cout % 64 == 0, ksize 3, stride 1 and no input prologue (SILU_IN / SQUARE_IN).  mcq_conv2d_winograd_ok tells
- * whether a geometry is taken (1) or would be refused (0). */
+ * whether mcq_conv2d_f32 takes a geometry AND flag set (1) or refuses it with MCQ_EINVAL (0), by the launcher's own rules: exactly
+ * one of MCQ_CONV_WINOGRAD / _WINOGRAD2D / _WINOGRAD2D16 (none = MCQ_CONV_WINOGRAD is meant), no MCQ_CONV_TAPS_LR, no POST_* or
+ * backward-pair epilogue, the PixelShuffle store with no other epilogue, WINOGRAD2D: Cout % 128 == 0 and Cin % 8 == 0,
+ * WINOGRAD2D16: Cout % 128 == 0, Cin % 16 == 0 and an epilogue within SiLU / residual / twin or the PixelShuffle store alone.
+ * (Null side pointers and the 2 GiB addressing limit, MCQ_ETOOLARGE, are not its subject.) */
 size_t mcq_packed_conv_winograd_floats(int32_t Cout, int32_t Cin);
 /* The same in both directions, F(2x2, 3x3) (MCQ_CONV_WINOGRAD2D; Cout % 128 == 0 and Cin % 8 == 0): G g G^T, sixteen transformed taps per filter,
  * [Cout/32][Cin/2 x 16][64 lanes]; 4/9 of the multiplications. */

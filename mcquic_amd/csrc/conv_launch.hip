@@ -27,6 +27,27 @@ bool wino_shape(int Cout, int ksize, int stride, unsigned fl) {
     return ksize == 3 && stride == 1 && Cout % 64 == 0 && !(fl & (MCQ_CONV_SILU_IN | MCQ_CONV_SQUARE_IN));
 }
 
+// Does mcq_conv2d_f32 take a Winograd launch of this geometry and flag set (pointers and the 2 GiB addressing limits aside)?  Every
+// rule conv_validate, conv_launch and mcq_wino16_launch apply to one, in one place: mcq_conv2d_winograd_ok answers with it and
+// conv_launch refuses by it, so the two cannot disagree.  Without a Winograd flag the question is about MCQ_CONV_WINOGRAD.
+bool wino_taken(int Cin, int Cout, int ksize, int stride, unsigned flags) {
+    const unsigned W3 = MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D | MCQ_CONV_WINOGRAD2D16;
+    const unsigned wf = (flags & W3) ? (flags & W3) : (unsigned)MCQ_CONV_WINOGRAD;
+    if (wf & (wf - 1)) return false;                                        // one form per launch
+    if (flags & MCQ_CONV_TAPS_LR) return false;                             // (the four-tap walk is the direct kernel's)
+    const unsigned fl = flags & ~(W3 | (unsigned)MCQ_CONV_TAPS_LR);         // the prologue / epilogue flags
+    if (!wino_shape(Cout, ksize, stride, fl)) return false;
+    if (fl & (MCQ_CONV_POST_MASK | MCQ_CONV_GDN_BWD | MCQ_CONV_IGDN_BWD | MCQ_CONV_GATE_BWD)) return false;      // epilogues of the direct form
+    if ((fl & MCQ_CONV_DUAL_SILU) && (fl & MCQ_CONV_SILU_OUT)) return false;
+    if ((fl & MCQ_CONV_SHUFFLE2) && fl != MCQ_CONV_SHUFFLE2) return false;  // the PixelShuffle store of a Winograd form carries nothing else
+    if (wf == MCQ_CONV_WINOGRAD2D && (Cout % 128 != 0 || Cin % 8 != 0)) return false;
+    if (wf == MCQ_CONV_WINOGRAD2D16) {
+        if (Cout % 128 != 0 || Cin % 16 != 0) return false;
+        if (fl != MCQ_CONV_SHUFFLE2 && (fl & ~(unsigned)(MCQ_CONV_SILU_OUT | MCQ_CONV_RESIDUAL | MCQ_CONV_DUAL_SILU))) return false;
+    }
+    return true;
+}
+
 // does mcq_conv2d_f32 take a MCQ_CONV_POST_* launch on its own (`row_tiles` 128-row tiles per pixel block)?  From two 128 x 32 wave tiles
 // per SIMD; below that the map's 3x3 layer is normally split over waves and the 1x1 layer stays a launch (unless the caller forces tile 0x41)
 inline bool post_fills_chip(long long tb, int row_tiles) { return tb * row_tiles >= 2048; }
@@ -122,6 +143,8 @@ int conv_launch(const mcq_conv_desc* descs, int nprob, void* stream) {
     k.post_w = d->post_w; k.post_b = d->post_bias; k.post_sub = 0;
     for (int c = 1; c < MCQ_CONV_MAX_MULTI; ++c) conv_ptrs(k.alt[c - 1], descs + (c < nprob ? c : 0), sec4, sec2);
 
+    if ((fl & (MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D | MCQ_CONV_WINOGRAD2D16)) && !wino_taken(d->Cin, d->Cout, d->ksize, d->stride, d->flags))
+        return MCQ_EINVAL;
     if (fl & MCQ_CONV_WINOGRAD2D16) {
         // F(2x2, 3x3) on the 16 x 16 x 4 instruction, two waves per SIMD (conv_wino16.hip)
         if ((fl & (MCQ_CONV_WINOGRAD | MCQ_CONV_WINOGRAD2D)) || !wino_shape(d->Cout, d->ksize, d->stride, fl)) return MCQ_EINVAL;
@@ -355,7 +378,7 @@ int conv_launch(const mcq_conv_desc* descs, int nprob, void* stream) {
 
 extern "C" int32_t mcq_conv2d_winograd_ok(int32_t N, int32_t Cin, int32_t H, int32_t W, int32_t Cout, int32_t ksize, int32_t stride,
                                           uint32_t flags) {
-    return (N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && wino_shape(Cout, ksize, stride, flags)) ? 1 : 0;
+    return (N > 0 && Cin > 0 && H > 0 && W > 0 && Cout > 0 && wino_taken(Cin, Cout, ksize, stride, flags)) ? 1 : 0;
 }
 
 extern "C" void mcq_conv_section_trace(int32_t on) {

@@ -25,7 +25,13 @@ contraction on top of v and has references of its own at the end of this file:
   to_subpixel_rows / from_subpixel_rows  the row order of a [512, Cin, 3, 3] layer whose four 128-row tiles are the four sub-pixels of
                                          a PixelShuffle(2) store, and the way back from such a layer's output to the shuffled map
   POST_GEOMS / post_problem / post_layer the seeded inputs of tests/test_gpu_conv_post_epilogues.py (tests/test_conv_refs.py checks
-                                         the same ones on the CPU)"""
+                                         the same ones on the CPU)
+
+The kernels beside the direct form -- conv_head16_kernel and the three Winograd forms -- have their references at the very end:
+
+  wino1d_f32 / wino2d_f32                F(2, 3) along x and F(2x2, 3x3) restated with one float32 (or float64) rounding per operation
+  exact_case                             integer inputs on which the direct and the Winograd arithmetic are exact, the bound asserted
+  OTHER_GEOMS / OTHER_CHANNELS / other_problem / other_yardstick   the inputs of tests/test_gpu_conv_other_kernels.py"""
 import torch
 import torch.nn.functional as F
 
@@ -380,3 +386,160 @@ def post_sides(names, shape, seed=5000):
     """The gate's output-shaped side tensors (res, gate_mul, gate_id), seeded."""
     scale = dict(res=1.0, gate_mul=2.0, gate_id=0.5)
     return {k: R.randn(shape, seed + 13 * ("res", "gate_mul", "gate_id").index(k), scale[k]) for k in names}
+
+
+# ---- the other convolution kernels: conv_head16_kernel and the three Winograd forms (tests/test_gpu_conv_other_kernels.py) ------------------
+# F(2, 3) / F(2x2, 3x3):  Y = A^T [ sum_c (G g G^T) . (B^T d B) ] A  with
+#   G = [[1, 0, 0], [.5, .5, .5], [.5, -.5, .5], [0, 0, 1]],  B^T d = (d0 - d2, d1 + d2, d2 - d1, d1 - d3),  A^T m = (m0 + m1 + m2, m1 - m2 - m3)
+WINO_G = ((1.0, 0.0, 0.0), (0.5, 0.5, 0.5), (0.5, -0.5, 0.5), (0.0, 0.0, 1.0))
+
+
+def _bt(d0, d1, d2, d3, bound):
+    """B^T along one axis: one subtraction or addition each (with `bound`: of magnitudes, every sign a plus)."""
+    if bound:
+        return d0 + d2, d1 + d2, d2 + d1, d1 + d3
+    return d0 - d2, d1 + d2, d2 - d1, d1 - d3
+
+
+def _at(m0, m1, m2, m3, bound):
+    """A^T along one axis in the kernels' order: (m0 + m1) + m2 and (m1 - m2) - m3."""
+    if bound:
+        return (m0 + m1) + m2, (m1 + m2) + m3
+    return (m0 + m1) + m2, (m1 - m2) - m3
+
+
+def _wino(form, x, w, b, dtype, bound=False):
+    """Both Winograd forms of the 3x3 stride-1 padding-1 convolution with one rounding of `dtype` per operation.  U is formed in
+    float64 and rounded once (as the pack kernels do), the input transform, the sum over channels (1-D: over channel and filter row)
+    as ONE sequential chain of separately rounded products, and the inverse transform run in `dtype`; the bias is added last.
+    `bound`: the same walk over magnitudes with every sign a plus -- an upper bound of every intermediate of the true walk
+    (returned as (result, largest input-transform value, largest |U|); the chain's partial sums are below its last one)."""
+    assert form in ("wino1d", "wino2d") and w.shape[-2:] == (3, 3) and x.dtype == w.dtype
+    n, cin, h, wd = x.shape
+    cout = w.shape[0]
+    g = torch.tensor(WINO_G, dtype=F64)
+    if form == "wino1d":
+        u = torch.einsum("pa,ocya->ocyp", g, w.double())                # [cout, cin, filter row, position]
+    else:
+        u = torch.einsum("pa,ocab,qb->ocpq", g, w.double(), g)          # [cout, cin, position y, position x]
+    u = u.to(dtype)
+    xx = x.to(dtype)
+    if bound:
+        u, xx = u.abs(), xx.abs()
+    wt = (wd + 1) // 2
+    if form == "wino1d":
+        xp = F.pad(xx, (1, 2 * wt + 1 - wd, 1, 1))                      # columns 2 xp - 1 .. 2 xp + 2 of pair xp, rows y - 1 .. y + 1
+        # v[pos]: [n, cin, filter row, h, wt]
+        rows = [[xp[:, :, dy:dy + h, j:j + 2 * wt:2] for j in range(4)] for dy in range(3)]
+        v = [torch.stack([_bt(*rows[dy], bound)[pos] for dy in range(3)], dim=2) for pos in range(4)]
+        acc = [torch.zeros((n, cout, h, wt), dtype=dtype) for _ in range(4)]
+        for c in range(cin):
+            for dy in range(3):
+                for pos in range(4):
+                    acc[pos] = acc[pos] + u[None, :, c, dy, pos, None, None] * v[pos][:, None, c, dy]
+        even, odd = _at(*acc, bound)
+        out = torch.stack((even, odd), dim=-1).reshape(n, cout, h, 2 * wt)[..., :wd]
+        vmax = max(float(t.max()) for t in v) if bound else None
+    else:
+        ht = (h + 1) // 2
+        xp = F.pad(xx, (1, 2 * wt + 1 - wd, 1, 2 * ht + 1 - h))
+        d = [[xp[:, :, i:i + 2 * ht:2, j:j + 2 * wt:2] for j in range(4)] for i in range(4)]          # the 4 x 4 patch under a tile
+        t = [_bt(*d[i], bound) for i in range(4)]                       # along x, row by row
+        v = [_bt(t[0][j], t[1][j], t[2][j], t[3][j], bound) for j in range(4)]      # along y: v[j][i] = V[i][j]
+        acc = [[torch.zeros((n, cout, ht, wt), dtype=dtype) for _ in range(4)] for _ in range(4)]
+        for c in range(cin):
+            for i in range(4):
+                for j in range(4):
+                    acc[i][j] = acc[i][j] + u[None, :, c, i, j, None, None] * v[j][i][:, None, c]
+        sx = [_at(*acc[i], bound) for i in range(4)]                    # sx[i][ox]
+        col = [_at(sx[0][ox], sx[1][ox], sx[2][ox], sx[3][ox], bound) for ox in range(2)]          # col[ox][oy]
+        out = torch.empty((n, cout, 2 * ht, 2 * wt), dtype=dtype)
+        for oy in range(2):
+            for ox in range(2):
+                out[:, :, oy::2, ox::2] = col[ox][oy]
+        out = out[:, :, :h, :wd]
+        vmax = max(float(e.max()) for r in v for e in r) if bound else None
+    if b is not None:
+        out = out + (b.abs() if bound else b).to(dtype).reshape(1, cout, 1, 1)
+    out = out.contiguous()
+    return (out, vmax, float(u.max())) if bound else out
+
+
+def wino1d_f32(x, w, b, dtype=F32):
+    """F(2, 3) along x (MCQ_CONV_WINOGRAD) restated with one `dtype` rounding per operation: see _wino."""
+    return _wino("wino1d", x, w, b, dtype)
+
+
+def wino2d_f32(x, w, b, dtype=F32):
+    """F(2x2, 3x3) (MCQ_CONV_WINOGRAD2D / _WINOGRAD2D16) restated with one `dtype` rounding per operation: see _wino."""
+    return _wino("wino2d", x, w, b, dtype)
+
+
+EXACT_LIMIT = float(1 << 24)            # integers below this magnitude are float32 values, and so are their sums and differences
+
+
+def exact_case(form, cin, cout, h, w, n=2, seed=0):
+    """Integer-valued float32 (x, weight, bias, res) for which every intermediate of the direct and of the `form` arithmetic
+    ("direct", "wino1d", "wino2d") is an integer below 2^24 in magnitude, whatever the order of summation: x in -3 .. 3, the bias and
+    the residual in -8 .. 8, the weights in -2 .. 2 times 1 (direct), 2 (1-D: U = G g is integral) or 4 (2-D: U = G g G^T is).
+    The bound is computed, not assumed: the direct sum of magnitudes sum |x| |w| + |b| + |res|, and for the Winograd forms the walk
+    of _wino over magnitudes (sum over channels of |U| |V|, through A^T with every sign a plus, + |b| + |res|), which bounds every
+    partial sum and every transform value of the true walk; U is checked to be integral."""
+    step = dict(direct=1, wino1d=2, wino2d=4)[form]
+    g = torch.Generator().manual_seed(9000 + seed)
+    ri = lambda lo, hi, shape: torch.randint(lo, hi + 1, shape, generator=g).to(F32)          # noqa: E731
+    x, wt, b = ri(-3, 3, (n, cin, h, w)), step * ri(-2, 2, (cout, cin, 3, 3)), ri(-8, 8, (cout,))
+    res = ri(-8, 8, (n, cout, h, w))
+    direct = conv_scale64(x, wt, b) + res.double().abs()
+    assert float(direct.max()) < EXACT_LIMIT, f"direct sum of magnitudes {float(direct.max()):.0f}"
+    if form != "direct":
+        gm = torch.tensor(WINO_G, dtype=F64)
+        u = torch.einsum("pa,ocya->ocyp", gm, wt.double()) if form == "wino1d" else torch.einsum("pa,ocab,qb->ocpq", gm, wt.double(), gm)
+        assert torch.equal(u, u.round()), "U is not integral"
+        top, vmax, umax = _wino(form, x, wt, b, F64, bound=True)
+        top = top + res.double().abs()
+        assert max(float(top.max()), vmax, umax) < EXACT_LIMIT, f"Winograd walk of magnitudes {float(top.max()):.0f}"
+    return x, wt, b, res
+
+
+# geometries (N = 2 everywhere: the second image's slab is addressed) and channel counts of tests/test_gpu_conv_other_kernels.py;
+# tests/test_conv_refs.py holds the restatements to conv64 on the same ones
+OTHER_GEOMS = {
+    "odd7x9": (7, 9),           # half-empty pairs / 2 x 2 tiles on both edges; no multiple of a block
+    "row1x9": (1, 9),           # a one-pixel-high map: every tile half empty along y
+    "col5x1": (5, 1),           # a one-pixel-wide map: every pair / tile half empty along x
+    "tiny2x2": (2, 2),          # one tile, one block
+    "wide9x35": (9, 35),        # 18 tiles per row: more than one 16-tile block (wino16); a second 16-pixel segment and a ragged third (head16)
+    "seg3x17": (3, 17),         # head16: the 4 segments of a wave straddle the row and the image boundary; the last wave's groups clamp
+}
+WINO_GEOMS = ("odd7x9", "row1x9", "col5x1", "tiny2x2", "wide9x35")
+HEAD_GEOMS = WINO_GEOMS + ("seg3x17",)
+# (cin, cout, forced tile).  head16: Cin 6 = no multiple of 4 (the last group's k lanes past Cin).  F(2, 3): Cin 20 = channel-pair
+# padding live; Cout 64 / 192 the 64-row instance, 128 the 128-row one, also forced to 64 rows (tile 0x22).  32x32x2: Cin 24 = the
+# smallest wino16 refuses.  16x16x4: Cin 16 = the peeled first body and one pass of the loop (a body is two 4-channel groups and the
+# launcher takes whole 16s: there is no smaller count), Cin 48 = six bodies.
+OTHER_CHANNELS = {
+    "head16": tuple((ci, co, 0) for ci in (6, 128) for co in (3, 12, 16)),
+    "wino1d": tuple((ci, co, t) for ci in (20, 128) for co, t in ((64, 0), (192, 0), (128, 0), (128, 0x22))),
+    "wino32": tuple((ci, co, 0) for ci in (24, 128) for co in (128, 256)),
+    "wino16": tuple((ci, co, 0) for ci in (16, 48) for co in (128, 256)),
+}
+OTHER_FORM = dict(head16="direct", wino1d="wino1d", wino32="wino2d", wino16="wino2d")
+
+
+def other_problem(kernel, gname, cin, cout, bias=True, variant=0):
+    """Seeded (x, w, b) of one (kernel, geometry, channel count): normal values, the weights scaled to a unit-variance result;
+    `variant` gives the problems of a multi-problem launch tensors of their own."""
+    h, w = OTHER_GEOMS[gname]
+    seed = 6000 + 31 * sum(ord(ch) for ch in kernel + gname) + 7 * cin + cout + 100000 * variant
+    return (R.randn((2, cin, h, w), seed), R.randn((cout, cin, 3, 3), seed + 1, (cin * 9) ** -0.5),
+            R.randn((cout,), seed + 2, 0.1) if bias else None)
+
+
+def other_yardstick(kernel, x, w, b, prologue=None):
+    """v as the float32 restatement of the kernel's OWN algorithm: the yardstick of the whole-launch bar."""
+    form = OTHER_FORM[kernel]
+    if form == "direct":
+        return conv_seq_f32(x, w, b, 1, prologue)
+    assert prologue is None
+    return _wino(form, x, w, b, F32)

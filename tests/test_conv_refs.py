@@ -9,7 +9,10 @@ them cannot bless a kernel with a reference that is wrong the same way.
   * dgrad2_weight's filter, stored through PixelShuffle(2), is autograd's input gradient of the stride-2 convolution;
   * the fused 1x1 layer's references (post64 / post_f32 / post_scale64, the sub-pixel row order) on the very inputs
     tests/test_gpu_conv_post_epilogues.py launches: post64 is the oracle's GDN / IGDN and F.conv2d + sigmoid composed in float64,
-    post_f32 restates it, the row order reproduces F.pixel_shuffle, and every GDN / IGDN case has s >= 1."""
+    post_f32 restates it, the row order reproduces F.pixel_shuffle, and every GDN / IGDN case has s >= 1;
+  * the Winograd restatements (wino1d_f32 / wino2d_f32) in float64 ARE the convolution at every geometry and channel count
+    tests/test_gpu_conv_other_kernels.py launches, and on the exact cases (exact_case) the float32 restatement, the float64 one,
+    conv64 and the int64 convolution are the same integers: the exact cases are exact for the reference alone."""
 import os
 
 import pytest
@@ -317,3 +320,95 @@ def test_post_exact_layers_are_permutations_times_powers_of_two():
                 assert torch.equal(src, (torch.arange(128) + int(variant[5:])) % 128)
             seen.append(src)
         assert not any(torch.equal(seen[3], s) for s in seen[:3])
+
+
+# ---- the other kernels' references: conv_head16_kernel and the Winograd forms ----------------------------------------------------------------
+OTHER_CASES = [(k, gn, ci, co) for k in ("wino1d", "wino32", "wino16") for gn in C.WINO_GEOMS
+               for ci, co in sorted({(ci, co) for ci, co, _ in C.OTHER_CHANNELS[k]})]
+
+
+@pytest.mark.parametrize("kernel", ("wino1d", "wino32", "wino16"))
+def test_winograd_restatements_in_float64_are_the_convolution(kernel):
+    """wino1d_f32 / wino2d_f32 with dtype=float64 against conv64 within 1e-12 of conv_scale64, with and without bias, on every
+    (geometry, Cin, Cout) of the GPU test: what makes them references.  The float32 form stays within the chain's standard bound
+    (the sum of the products' magnitudes is below the walk of _wino over magnitudes, a few times conv_scale64)."""
+    form = C.OTHER_FORM[kernel]
+    fn = C.wino1d_f32 if form == "wino1d" else C.wino2d_f32
+    ran = 0
+    for k, gn, ci, co in OTHER_CASES:
+        if k != kernel:
+            continue
+        for bias in (True, False):
+            x, w, b = C.other_problem(kernel, gn, ci, co, bias)
+            ref, scale = C.conv64(x, w, b), C.conv_scale64(x, w, b)
+            got = fn(x, w, b, dtype=torch.float64)
+            assert got.dtype == torch.float64 and got.shape == ref.shape
+            err = float(((got - ref).abs() / scale).max())
+            assert err <= 1e-12, f"{kernel} {gn} Cin={ci} Cout={co} bias={bias}: {err:.3e} of conv_scale64"
+            ran += 1
+        x, w, b = C.other_problem(kernel, gn, ci, co)
+        f32 = fn(x, w, b)
+        assert f32.dtype == torch.float32 and torch.equal(f32, C.other_yardstick(kernel, x, w, b))
+        top, _, _ = C._wino(form, x, w, b, torch.float64, bound=True)
+        assert float(((f32.double() - C.conv64(x, w, b)).abs() / top).max()) <= (3 * ci + 8) * U
+    assert ran == 2 * len(C.WINO_GEOMS) * len({(ci, co) for ci, co, _ in C.OTHER_CHANNELS[kernel]})
+
+
+def test_winograd_restatement_catches_a_wrong_transform_row():
+    """The restatement is not the convolution by accident: with two rows of G swapped it is off by more than 1e-2 of conv_scale64."""
+    x, w, b = C.other_problem("wino32", "odd7x9", 24, 128)
+    ref, scale = C.conv64(x, w, b), C.conv_scale64(x, w, b)
+    keep = C.WINO_G
+    try:
+        C.WINO_G = (keep[0], keep[2], keep[1], keep[3])
+        bad = C.wino2d_f32(x, w, b, dtype=torch.float64)
+    finally:
+        C.WINO_G = keep
+    assert float(((bad - ref).abs() / scale).max()) > 1e-2
+
+
+# (kernel, geometry, Cin, Cout, seed) exactly as tests/test_gpu_conv_other_kernels.py::test_exact builds them: the seed is the index
+# of the channel configuration, a forced tile being a configuration of its own
+EXACT_CASES = [(k, gn, ci, co, i) for k in ("head16", "wino1d", "wino32", "wino16") for gn in (C.HEAD_GEOMS if k == "head16" else C.WINO_GEOMS)
+               for i, (ci, co, _) in enumerate(C.OTHER_CHANNELS[k])]
+
+
+@pytest.mark.parametrize("kernel", ("head16", "wino1d", "wino32", "wino16"))
+def test_exact_cases_are_exact_for_the_references(kernel):
+    """On every exact case the GPU test launches: float32 restatement == float64 restatement == conv64 == F.conv2d in int64, all
+    with torch.equal (the builder has asserted its bound on every intermediate; this is the same statement by computation)."""
+    form = C.OTHER_FORM[kernel]
+    ran = 0
+    for k, gn, ci, co, seed in EXACT_CASES:
+        if k != kernel:
+            continue
+        h, wd = C.OTHER_GEOMS[gn]
+        x, w, b, res = C.exact_case(form, ci, co, h, wd, seed=seed)
+        for t in (x, w, b, res):
+            assert t.dtype == torch.float32 and torch.equal(t, t.round())
+        assert x.shape == (2, ci, h, wd) and res.shape == (2, co, h, wd)
+        if form == "wino1d":
+            assert torch.equal(w % 2, torch.zeros_like(w))
+        if form == "wino2d":
+            assert torch.equal(w % 4, torch.zeros_like(w))
+        want = F.conv2d(x.long(), w.long(), b.long(), padding=1)
+        v64 = C.conv64(x, w, b)
+        assert torch.equal(v64, want.double()), f"{kernel} {gn}: conv64 is not the integer convolution"
+        if form == "direct":
+            f32, f64 = C.conv_seq_f32(x, w, b), v64
+        else:
+            f32, f64 = C._wino(form, x, w, b, torch.float32), C._wino(form, x, w, b, torch.float64)
+        assert torch.equal(f32.double(), f64), f"{kernel} {gn}: the float32 restatement rounds"
+        assert torch.equal(f64, v64), f"{kernel} {gn}: the float64 restatement is not conv64"
+        # ... and the epilogues the exact launches carry stay integers below 2^24: - res, and the PixelShuffle store
+        assert float((v64.abs() + res.double().abs()).max()) < C.EXACT_LIMIT
+        y, _ = C.out_f32(f32, dict(res_scale=-1.0), dict(res=res))
+        assert torch.equal(y.long(), want - res.long())
+        ran += 1
+    assert ran == len([c for c in EXACT_CASES if c[0] == kernel])
+
+
+def test_exact_case_refuses_what_is_not_exact():
+    """The builder asserts its bound rather than trusting it: a centre pixel under nine taps of a million channels (mean |x| |w| about 2) passes 2^24."""
+    with pytest.raises(AssertionError):
+        C.exact_case("direct", 1000000, 1, 3, 3, n=1)

@@ -262,8 +262,8 @@ def _plain(case, tile):
 class _Worst:
     """Worst figures per tile class of one row; recorded, then asserted together so that one run leaves every figure."""
 
-    def __init__(self, name):
-        self.name, self.fig, self.fail = name, {}, []
+    def __init__(self, name, prefix="conv_epilogue", ulp_bar="(a)"):
+        self.name, self.fig, self.fail, self.prefix, self.ulp_bar = name, {}, [], prefix, ulp_bar
 
     def put(self, cls, **vals):
         f = self.fig.setdefault(cls, {})
@@ -272,11 +272,11 @@ class _Worst:
 
     def close(self):
         for cls, f in sorted(self.fig.items()):
-            record(f"conv_epilogue[{self.name}][{cls}]", **f)
-            print(f"conv_epilogue[{self.name}][{cls}]: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(f.items())))
+            record(f"{self.prefix}[{self.name}][{cls}]", **f)
+            print(f"{self.prefix}[{self.name}][{cls}]: " + ", ".join(f"{k} {v:.3g}" for k, v in sorted(f.items())))
             for out in ("y", "second"):
                 if f"{out}_gpu_ulp" in f and f[f"{out}_gpu_ulp"] > 4.0 * f[f"{out}_cpu_ulp"]:
-                    self.fail.append(f"(a) {cls} {out}: {f[out + '_gpu_ulp']:.2f} ulp > 4 x {f[out + '_cpu_ulp']:.2f} ulp of the float32 formula")
+                    self.fail.append(f"{self.ulp_bar} {cls} {out}: {f[out + '_gpu_ulp']:.2f} ulp > 4 x {f[out + '_cpu_ulp']:.2f} ulp of the float32 formula")
         assert not self.fail, f"{self.name}:\n  " + "\n  ".join(self.fail)
 
 
