@@ -946,12 +946,46 @@ int mcq_rans_decode_batch_with_indexes(const uint8_t* in, const int64_t* in_offs
  * window, K = (0.01, 0.03), data range 255, five levels with weights metrics.py:19).  out[N] receives the MS-SSIM VALUE
  * in [0, 1] (the reference module returns 1 - value and the handler prints -10 log10 of that).  H and W must exceed 160
  * (metrics.py:163-166), else MCQ_EINVAL.  `workspace` holds the pooled pyramids and partial sums:
- * mcq_ms_ssim_workspace_bytes(N, C, H, W) bytes (0 for an invalid shape), 8-byte aligned, contents undefined after. */
+ * mcq_ms_ssim_workspace_bytes(N, C, H, W) bytes (0 for an invalid shape), 8-byte aligned.  Where a call leaves its
+ * intermediate results in it is answered by mcq_ms_ssim_workspace_layout below and by nothing else: read no offset that
+ * function did not return; anything it does not name is undefined after a call. */
 size_t mcq_ms_ssim_workspace_bytes(int32_t N, int32_t C, int32_t H, int32_t W);
 int mcq_ms_ssim_u8(const uint8_t* x, const uint8_t* y, float* out, void* workspace, int32_t N, int32_t C, int32_t H,
                    int32_t W, void* stream);
 /* Host helper: the 11 float32 window taps the kernels use (metrics.py:22-37 for size 11, sigma 1.5). */
 void mcq_ms_ssim_window(float* out11);
+
+/* The stages of mcq_ms_ssim_u8 on their own, through the launch code mcq_ms_ssim_u8 itself runs (same kernels, same
+ * grids): what tests/test_gpu_metrics_leaf.py holds to references stage by stage.  Additive: ABI 18 stays.
+ *   mcq_ssim_tiles               host: the map of an H x W level ((H - 10) x (W - 10) positions) is cut into
+ *                                tiles_y x tiles_x tiles of 16 x 118 positions; H, W >= 11, else MCQ_EINVAL.
+ *   mcq_ssim_level_u8 / _f32     one level: X, Y [planes, H, W]; partial_out [planes][tiles_y * tiles_x][2] float64
+ *                                receives per tile (row-major) the sum of the SSIM map and the sum of the
+ *                                contrast-structure map over the tile's positions inside the map.  H, W >= 11;
+ *                                planes and tiles_y at most 65535, else MCQ_ETOOLARGE.
+ *   mcq_ms_ssim_halve_u8 / _f32  one pooling step of both images: Xo, Yo [planes, (H + 1) / 2, (W + 1) / 2] float32.
+ *   mcq_ms_ssim_combine_f32      levels [5][N * C][2] float32 ({SSIM mean, CS mean} per level and plane) -> out[N]:
+ *                                prod over levels of relu(CS)^w (relu(SSIM)^w on the last), mean over the C channels.
+ *   mcq_ms_ssim_workspace_layout host: where a mcq_ms_ssim_u8 call of this shape leaves its intermediate results in
+ *                                `workspace`.  out[MCQ_MS_SSIM_LAYOUT_WORDS] int64 (HOST memory): per level l six
+ *                                words at out[6 l] -- H, W, tiles_y, tiles_x, and the FLOAT offsets of the pooled x
+ *                                and y planes [N * C, H, W] (-1 at level 0, the caller's input) --, then out[30] the
+ *                                BYTE offset of the tile partials (those of the last level after a call), out[31]
+ *                                the BYTE offset of the float32 level table [5][N * C][2] that
+ *                                mcq_ms_ssim_combine_f32 reads, out[32] = mcq_ms_ssim_workspace_bytes.  MCQ_EINVAL
+ *                                where that is 0. */
+#define MCQ_MS_SSIM_LAYOUT_WORDS 33
+int mcq_ssim_tiles(int32_t H, int32_t W, int32_t* tiles_y, int32_t* tiles_x);
+int mcq_ssim_level_u8(const uint8_t* X, const uint8_t* Y, int32_t planes, int32_t H, int32_t W, double* partial_out,
+                      void* stream);
+int mcq_ssim_level_f32(const float* X, const float* Y, int32_t planes, int32_t H, int32_t W, double* partial_out,
+                       void* stream);
+int mcq_ms_ssim_halve_u8(const uint8_t* X, const uint8_t* Y, float* Xo, float* Yo, int32_t planes, int32_t H, int32_t W,
+                         void* stream);
+int mcq_ms_ssim_halve_f32(const float* X, const float* Y, float* Xo, float* Yo, int32_t planes, int32_t H, int32_t W,
+                          void* stream);
+int mcq_ms_ssim_combine_f32(const float* levels, int32_t N, int32_t C, float* out, void* stream);
+int mcq_ms_ssim_workspace_layout(int32_t N, int32_t C, int32_t H, int32_t W, int64_t* out);
 
 /* MS-SSIM as a float32 TRAINING LOSS (the distortion of the reference's training configs, `target: MsSSIM`:
  * mcquic/loss/__init__.py:47-55 -> metrics.py:69-104, 142-193 with MsSSIM(data_range=2.0, sizeAverage=True) on restored + 1,

@@ -14,7 +14,12 @@
 // moment planes back with lanes along the row (conflict-free).  Every fp32 operation follows the order of
 // oracle/metrics_ref.py (taps added in index order, multiply and add rounded separately: the library is built with
 // -ffp-contract=off); the map means are accumulated in float64 and reduced in a fixed order, so results are
-// deterministic and differ from the CPU restatement only in the rounding of those means.
+// deterministic and differ from the CPU restatement only in the rounding of those means
+// (tests/test_gpu_metrics_leaf.py holds this claim per tile).
+//
+//   mcq_ssim_level_* / mcq_ms_ssim_halve_* / mcq_ms_ssim_combine_f32 / mcq_ms_ssim_workspace_layout
+//                       the stages of mcq_ms_ssim_u8 one at a time, through the host helpers (launch_level,
+//                       launch_finish, launch_halve, launch_combine) that mcq_ms_ssim_u8 itself launches by.
 #include "mcq_common.h"
 #include "../../include/mcquic_hip.h"
 
@@ -236,18 +241,25 @@ struct Pyramid {
     int tiles_x[5], tiles_y[5];
 };
 
+// 16 x 118 tiles over the (H - 10) x (W - 10) map of one level
+inline void level_tiles(int H, int W, int& tiles_y, int& tiles_x) {
+    const int Ho = H - 10, Wo = W - 10;
+    tiles_x = (Wo + TW - 1) / TW;
+    tiles_y = (Ho + TH - 1) / TH;
+}
+
+// side of the next level: avg_pool2d(kernel 2, stride 2, padding = side % 2)
+inline int halved(int side) { return (side + 2 * (side & 1) - 2) / 2 + 1; }
+
 inline bool make_pyramid(int H, int W, Pyramid& p) {
     if (H <= 160 || W <= 160) return false;        // metrics.py:163-166
     for (int l = 0; l < 5; ++l) {
         p.H[l] = H;
         p.W[l] = W;
         p.plane_floats[l] = (size_t)H * W;
-        const int Ho = H - 10, Wo = W - 10;
-        p.tiles_x[l] = (Wo + TW - 1) / TW;
-        p.tiles_y[l] = (Ho + TH - 1) / TH;
-        const int ph = H & 1, pw = W & 1;
-        H = (H + 2 * ph - 2) / 2 + 1;
-        W = (W + 2 * pw - 2) / 2 + 1;
+        level_tiles(H, W, p.tiles_y[l], p.tiles_x[l]);
+        H = halved(H);
+        W = halved(W);
     }
     return true;
 }
@@ -279,6 +291,51 @@ inline Workspace layout(const Pyramid& p, size_t planes) {
     return w;
 }
 
+// ---- one host helper per stage: mcq_ms_ssim_u8 and the per-stage entry points below launch through these -----------
+template <typename T>
+inline void launch_level(const T* X, const T* Y, size_t planes, int H, int W, int tiles_y, int tiles_x, double* partial,
+                         hipStream_t s) {
+    const dim3 grid((unsigned)tiles_x, (unsigned)tiles_y, (unsigned)planes);
+    hipLaunchKernelGGL(ssim_level_kernel<T>, grid, dim3(256), 0, s, X, Y, H, W, H - 10, W - 10, partial);
+}
+
+inline void launch_finish(const double* partial, size_t planes, int ntile, int H, int W, float* level_out,
+                          hipStream_t s) {
+    hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)((planes + 63) / 64)), dim3(64), 0, s, partial, (int)planes,
+                       ntile, (double)(H - 10) * (double)(W - 10), level_out);
+}
+
+template <typename T>
+inline void launch_halve(const T* X, const T* Y, float* Xo, float* Yo, size_t planes, int H, int W, int Ho, int Wo,
+                         hipStream_t s) {
+    const size_t total = planes * (size_t)Ho * Wo;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    hipLaunchKernelGGL(halve_kernel<T>, grid, dim3(256), 0, s, X, Y, Xo, Yo, H, W, Ho, Wo, total);
+}
+
+inline void launch_combine(const float* levels, int N, int C, float* out, hipStream_t s) {
+    hipLaunchKernelGGL(ms_ssim_combine_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, levels, N, C, out);
+}
+
+template <typename T>
+int ssim_level_entry(const T* X, const T* Y, int32_t planes, int32_t H, int32_t W, double* partial_out, void* stream) {
+    if (!X || !Y || !partial_out || planes <= 0 || H < 11 || W < 11) return MCQ_EINVAL;
+    int ty, tx;
+    level_tiles(H, W, ty, tx);
+    if (planes > 65535 || ty > 65535) return MCQ_ETOOLARGE;      // grid.z, grid.y
+    launch_level<T>(X, Y, (size_t)planes, H, W, ty, tx, partial_out, (hipStream_t)stream);
+    return mcq_check_launch();
+}
+
+template <typename T>
+int halve_entry(const T* X, const T* Y, float* Xo, float* Yo, int32_t planes, int32_t H, int32_t W, void* stream) {
+    if (!X || !Y || !Xo || !Yo || planes <= 0 || H <= 0 || W <= 0) return MCQ_EINVAL;
+    const int Ho = halved(H), Wo = halved(W);
+    if (((size_t)planes * Ho * Wo + 255) / 256 > 0x7fffffffu) return MCQ_ETOOLARGE;      // grid.x
+    launch_halve<T>(X, Y, Xo, Yo, (size_t)planes, H, W, Ho, Wo, (hipStream_t)stream);
+    return mcq_check_launch();
+}
+
 }  // namespace
 
 extern "C" void mcq_ms_ssim_window(float* out11) {
@@ -305,26 +362,76 @@ extern "C" int mcq_ms_ssim_u8(const uint8_t* x, const uint8_t* y, float* out, vo
     double* partial = (double*)(base + ws.partial_off);
     float* levels = (float*)(base + ws.levels_off);
     for (int l = 0; l < 5; ++l) {
-        const int Hl = p.H[l], Wl = p.W[l], Ho = Hl - 10, Wo = Wl - 10;
-        const dim3 grid((unsigned)p.tiles_x[l], (unsigned)p.tiles_y[l], (unsigned)planes);
-        const int ntile = p.tiles_x[l] * p.tiles_y[l];
-        if (l == 0) hipLaunchKernelGGL(ssim_level_kernel<uint8_t>, grid, dim3(256), 0, s, x, y, Hl, Wl, Ho, Wo, partial);
-        else hipLaunchKernelGGL(ssim_level_kernel<float>, grid, dim3(256), 0, s, (const float*)(fbase + ws.x_off[l]),
-                                (const float*)(fbase + ws.y_off[l]), Hl, Wl, Ho, Wo, partial);
-        hipLaunchKernelGGL(ssim_finish_kernel, dim3((unsigned)((planes + 63) / 64)), dim3(64), 0, s, (const double*)partial,
-                           (int)planes, ntile, (double)Ho * (double)Wo, levels + (size_t)l * planes * 2);
+        const int Hl = p.H[l], Wl = p.W[l];
+        const float* xl = fbase + ws.x_off[l];
+        const float* yl = fbase + ws.y_off[l];
+        if (l == 0) launch_level<uint8_t>(x, y, planes, Hl, Wl, p.tiles_y[l], p.tiles_x[l], partial, s);
+        else launch_level<float>(xl, yl, planes, Hl, Wl, p.tiles_y[l], p.tiles_x[l], partial, s);
+        launch_finish(partial, planes, p.tiles_x[l] * p.tiles_y[l], Hl, Wl, levels + (size_t)l * planes * 2, s);
         if (l < 4) {
-            const size_t total = planes * p.plane_floats[l + 1];
-            const dim3 g((unsigned)((total + 255) / 256));
-            if (l == 0) hipLaunchKernelGGL(halve_kernel<uint8_t>, g, dim3(256), 0, s, x, y, fbase + ws.x_off[1], fbase + ws.y_off[1],
-                                           Hl, Wl, p.H[1], p.W[1], total);
-            else hipLaunchKernelGGL(halve_kernel<float>, g, dim3(256), 0, s, (const float*)(fbase + ws.x_off[l]),
-                                    (const float*)(fbase + ws.y_off[l]), fbase + ws.x_off[l + 1], fbase + ws.y_off[l + 1], Hl, Wl,
-                                    p.H[l + 1], p.W[l + 1], total);
+            float* xn = fbase + ws.x_off[l + 1];
+            float* yn = fbase + ws.y_off[l + 1];
+            if (l == 0) launch_halve<uint8_t>(x, y, xn, yn, planes, Hl, Wl, p.H[1], p.W[1], s);
+            else launch_halve<float>(xl, yl, xn, yn, planes, Hl, Wl, p.H[l + 1], p.W[l + 1], s);
         }
     }
-    hipLaunchKernelGGL(ms_ssim_combine_kernel, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, s, (const float*)levels, N, C, out);
+    launch_combine(levels, N, C, out, s);
     return mcq_check_launch();
+}
+
+// ---- the stages on their own (what tests/test_gpu_metrics_leaf.py holds to references): the launch code above ------
+extern "C" int mcq_ssim_tiles(int32_t H, int32_t W, int32_t* tiles_y, int32_t* tiles_x) {
+    if (!tiles_y || !tiles_x || H < 11 || W < 11) return MCQ_EINVAL;
+    int ty, tx;
+    level_tiles(H, W, ty, tx);
+    *tiles_y = ty;
+    *tiles_x = tx;
+    return MCQ_OK;
+}
+
+extern "C" int mcq_ssim_level_u8(const uint8_t* X, const uint8_t* Y, int32_t planes, int32_t H, int32_t W,
+                                 double* partial_out, void* stream) {
+    return ssim_level_entry<uint8_t>(X, Y, planes, H, W, partial_out, stream);
+}
+
+extern "C" int mcq_ssim_level_f32(const float* X, const float* Y, int32_t planes, int32_t H, int32_t W,
+                                  double* partial_out, void* stream) {
+    return ssim_level_entry<float>(X, Y, planes, H, W, partial_out, stream);
+}
+
+extern "C" int mcq_ms_ssim_halve_u8(const uint8_t* X, const uint8_t* Y, float* Xo, float* Yo, int32_t planes, int32_t H,
+                                    int32_t W, void* stream) {
+    return halve_entry<uint8_t>(X, Y, Xo, Yo, planes, H, W, stream);
+}
+
+extern "C" int mcq_ms_ssim_halve_f32(const float* X, const float* Y, float* Xo, float* Yo, int32_t planes, int32_t H,
+                                     int32_t W, void* stream) {
+    return halve_entry<float>(X, Y, Xo, Yo, planes, H, W, stream);
+}
+
+extern "C" int mcq_ms_ssim_combine_f32(const float* levels, int32_t N, int32_t C, float* out, void* stream) {
+    if (!levels || !out || N <= 0 || C <= 0) return MCQ_EINVAL;
+    launch_combine(levels, N, C, out, (hipStream_t)stream);
+    return mcq_check_launch();
+}
+
+extern "C" int mcq_ms_ssim_workspace_layout(int32_t N, int32_t C, int32_t H, int32_t W, int64_t* out) {
+    Pyramid p;
+    if (!out || N <= 0 || C <= 0 || !make_pyramid(H, W, p)) return MCQ_EINVAL;
+    const Workspace ws = layout(p, (size_t)N * C);
+    for (int l = 0; l < 5; ++l) {
+        int64_t* o = out + 6 * l;
+        o[0] = p.H[l];
+        o[1] = p.W[l];
+        o[2] = p.tiles_y[l];
+        o[3] = p.tiles_x[l];
+        o[4] = l ? (int64_t)ws.x_off[l] : -1;        // level 0 is the caller's uint8 input
+        o[5] = l ? (int64_t)ws.y_off[l] : -1;
+    }
+    out[30] = (int64_t)ws.partial_off;
+    out[31] = (int64_t)ws.levels_off;
+    out[32] = (int64_t)ws.bytes;
+    return MCQ_OK;
 }
 
 extern "C" int mcq_sqdiff_sum_u8(const uint8_t* x, const uint8_t* y, int64_t* out, int64_t per_image, int32_t N,

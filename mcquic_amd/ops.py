@@ -1778,6 +1778,92 @@ def ms_ssim(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# The stages of `ms_ssim` one launch at a time, through the launch code of mcq_ms_ssim_u8 (tests/test_gpu_metrics_leaf.py).
+def _plane_pair(x: torch.Tensor, y: torch.Tensor, what: str):
+    """Two [..., H, W] batches of one shape, both uint8 or both float32 -> (x, y, planes, H, W, "u8" | "f32")."""
+    if x.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"{what}: images must be uint8 or float32 (got {x.dtype})")
+    x, y = _dev(x, "x", x.dtype), _dev(y, "y", x.dtype)
+    if x.shape != y.shape or x.dim() < 2:
+        raise ValueError(f"{what}: expected two [..., H, W] batches of one shape, got {tuple(x.shape)} and {tuple(y.shape)}")
+    h, w = x.shape[-2:]
+    return x, y, x.numel() // max(h * w, 1), h, w, "u8" if x.dtype == torch.uint8 else "f32"
+
+
+def ssim_tiles(h: int, w: int):
+    """(tiles_y, tiles_x) of the 16 x 118 map tiles of an h x w level (mcq_ssim_tiles; host arithmetic)."""
+    ty, tx = ctypes.c_int32(), ctypes.c_int32()
+    if _lib.load().mcq_ssim_tiles(h, w, ctypes.byref(ty), ctypes.byref(tx)) != 0:
+        raise ValueError(f"an SSIM level needs sides of at least 11 pixels, got {h}x{w}")
+    return ty.value, tx.value
+
+
+def ssim_level(x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """One SSIM level of two uint8 or float32 [..., H, W] batches (data range 255): float64 [planes, tiles_y, tiles_x, 2], per map
+    tile the sums of the SSIM and of the contrast-structure map over the tile's valid positions (mcq_ssim_level_u8 / _f32)."""
+    x, y, planes, h, w, kind = _plane_pair(x, y, "ssim_level")
+    ty, tx = ssim_tiles(h, w)
+    lib = _lib.load()
+    out = torch.empty((planes, ty, tx, 2), dtype=torch.float64, device=x.device)
+    fn, name = (lib.mcq_ssim_level_u8, "mcq_ssim_level_u8") if kind == "u8" else (lib.mcq_ssim_level_f32, "mcq_ssim_level_f32")
+    with _guard(x.device):
+        check(fn(_ptr(x), _ptr(y), planes, h, w, _ptr(out), _stream()), name)
+    return out
+
+
+def ms_ssim_halve(x: torch.Tensor, y: torch.Tensor, out=None):
+    """One pooling step of the MS-SSIM pyramid on both images: float32 [..., (H + 1) // 2, (W + 1) // 2] each (mcq_ms_ssim_halve_u8 /
+    _f32).  `out`: a pair of contiguous float32 tensors of that size to write into."""
+    x, y, planes, h, w, kind = _plane_pair(x, y, "ms_ssim_halve")
+    if planes == 0 or h == 0 or w == 0:
+        raise ValueError(f"ms_ssim_halve: empty input {tuple(x.shape)}")
+    shape = tuple(x.shape[:-2]) + ((h + 1) // 2, (w + 1) // 2)
+    if out is None:
+        out = (torch.empty(shape, dtype=torch.float32, device=x.device), torch.empty(shape, dtype=torch.float32, device=x.device))
+    xo, yo = (_dev(t, "out") for t in out)
+    if xo.numel() != planes * shape[-2] * shape[-1] or yo.numel() != xo.numel() or not (out[0].is_contiguous() and out[1].is_contiguous()):
+        raise ValueError(f"ms_ssim_halve: `out` must be two contiguous float32 tensors of {shape}")
+    lib = _lib.load()
+    fn, name = (lib.mcq_ms_ssim_halve_u8, "mcq_ms_ssim_halve_u8") if kind == "u8" else (lib.mcq_ms_ssim_halve_f32, "mcq_ms_ssim_halve_f32")
+    with _guard(x.device):
+        check(fn(_ptr(x), _ptr(y), _ptr(xo), _ptr(yo), planes, h, w, _stream()), name)
+    return xo, yo
+
+
+def ms_ssim_combine(levels: torch.Tensor) -> torch.Tensor:
+    """float32 [5, N, C, 2] per-level {SSIM mean, CS mean} -> MS-SSIM value [N] (mcq_ms_ssim_combine_f32)."""
+    levels = _dev(levels, "levels")
+    if levels.dim() != 4 or levels.shape[0] != 5 or levels.shape[3] != 2 or levels.numel() == 0:
+        raise ValueError(f"ms_ssim_combine: expected a [5, N, C, 2] table, got {tuple(levels.shape)}")
+    n, c = levels.shape[1:3]
+    out = torch.empty(n, dtype=torch.float32, device=levels.device)
+    with _guard(levels.device):
+        check(_lib.load().mcq_ms_ssim_combine_f32(_ptr(levels), n, c, _ptr(out), _stream()), "mcq_ms_ssim_combine_f32")
+    return out
+
+
+def ms_ssim_stages(x: torch.Tensor, y: torch.Tensor):
+    """`ms_ssim(x, y)` with what the call left in its workspace (mcq_ms_ssim_workspace_layout): (value [N], level table
+    [5, N, C, 2] float32 {SSIM mean, CS mean}, [(x_l, y_l) for l = 1..4] pooled images [N, C, H_l, W_l] float32)."""
+    x, y = _u8_pair(x, y)
+    n, c, h, w = x.shape
+    lib = _lib.load()
+    lay = (ctypes.c_int64 * _lib.MCQ_MS_SSIM_LAYOUT_WORDS)()
+    if lib.mcq_ms_ssim_workspace_layout(n, c, h, w, lay) != 0:
+        raise ValueError(f"MS-SSIM needs image sides larger than 160 pixels, got {h}x{w}")
+    ws = torch.empty((lay[32] + 7) // 8, dtype=torch.float64, device=x.device)
+    out = torch.empty(n, dtype=torch.float32, device=x.device)
+    with _guard(x.device):
+        check(lib.mcq_ms_ssim_u8(_ptr(x), _ptr(y), _ptr(out), _ptr(ws), n, c, h, w, _stream()), "mcq_ms_ssim_u8")
+    floats = ws.view(torch.float32)
+    table = floats[lay[31] // 4: lay[31] // 4 + 5 * n * c * 2].view(5, n, c, 2).clone()
+    pooled = []
+    for l in range(1, 5):
+        hl, wl, xo, yo = lay[6 * l], lay[6 * l + 1], lay[6 * l + 4], lay[6 * l + 5]
+        pooled.append((floats[xo: xo + n * c * hl * wl].view(n, c, hl, wl).clone(), floats[yo: yo + n * c * hl * wl].view(n, c, hl, wl).clone()))
+    return out, table, pooled
+
+
 def _f32_pair(a: torch.Tensor, b: torch.Tensor):
     a, b = _dev(a, "a"), _dev(b, "b")
     if a.shape != b.shape or a.dim() != 4:

@@ -54,8 +54,8 @@ def _blur_valid(x: torch.Tensor, win: torch.Tensor) -> torch.Tensor:
     return out
 
 
-def ssim_and_cs(x: torch.Tensor, y: torch.Tensor, win: torch.Tensor, data_range: float = 255.0) -> Tuple[torch.Tensor, torch.Tensor]:
-    """metrics.py:69-104 `_ssim`: per-(image, channel) means of the SSIM map and of its contrast-structure factor."""
+def ssim_and_cs_maps(x: torch.Tensor, y: torch.Tensor, win: torch.Tensor, data_range: float = 255.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """metrics.py:69-101 `_ssim` up to its means: the SSIM map and its contrast-structure factor, [..., H - 10, W - 10]."""
     c1 = (K1 * data_range) ** 2
     c2 = (K2 * data_range) ** 2
     mu1, mu2 = _blur_valid(x, win), _blur_valid(y, win)
@@ -65,6 +65,12 @@ def ssim_and_cs(x: torch.Tensor, y: torch.Tensor, win: torch.Tensor, data_range:
     s12 = _blur_valid(x * y, win) - mu12
     cs_map = (2 * s12 + c2) / (s1 + s2 + c2)
     ssim_map = ((2 * mu12 + c1) / (mu1_sq + mu2_sq + c1)) * cs_map
+    return ssim_map, cs_map
+
+
+def ssim_and_cs(x: torch.Tensor, y: torch.Tensor, win: torch.Tensor, data_range: float = 255.0) -> Tuple[torch.Tensor, torch.Tensor]:
+    """metrics.py:69-104 `_ssim`: per-(image, channel) means of the SSIM map and of its contrast-structure factor."""
+    ssim_map, cs_map = ssim_and_cs_maps(x, y, win, data_range)
     return ssim_map.flatten(2).mean(-1), cs_map.flatten(2).mean(-1)
 
 
