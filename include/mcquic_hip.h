@@ -196,6 +196,15 @@ size_t mcq_packed_codebook_floats(int32_t m, int32_t k, int32_t d);
 int mcq_vq_pack_codebook_f32(const float* codebook, int32_t m, int32_t k, int32_t d,
                              float* cb_packed, void* stream);
 
+/* The same pack with a rate penalty folded into the norm section (entropy-constrained assignment): cdf uint32 [m, k + 1] is one
+ * level of mcq_pmf_to_quantized_cdf_dev's tables (device), lambda >= 0 a host float.  The operand stream is the one above; the norms are
+ *   c2'[g, i] = fl32( c2[g, i] + fl32( lambda * fl32(16 - log2((double)(cdf[g, i + 1] - cdf[g, i]))) ) )
+ * with c2 formed exactly as above, so mcq_vq_assign*_f32 on this buffer returns argmin_k (distance + lambda * bits_k) through the
+ * unchanged kernel.  lambda == 0 gives the buffer of mcq_vq_pack_codebook_f32 bit for bit.  Padded codewords, and a slot of width 0
+ * (no valid table has one), get +inf.  MCQ_EINVAL for lambda < 0, NaN or inf.  No allocation, no synchronisation. */
+int mcq_vq_pack_codebook_rate_f32(const float* codebook, const uint32_t* cdf, float lambda, int32_t m, int32_t k, int32_t d,
+                                  float* cb_packed, void* stream);
+
 /* codes[n, g, y, x] = argmin_k ( (|x_v|^2 + |c_k|^2) - 2 <x_v, c_k> ), first index on ties.
  * x: [N, m*d, h, w] (channel = g*d + j).  Replaces _multiCodebookQuantization._distance + encode
  * (mcquic/modules/quantizer.py:144-179) without materialising [N, m, h, w, k]. */

@@ -319,6 +319,39 @@ __global__ void vq_c2_kernel(const float* __restrict__ cb, int m, int k, int d, 
     c2p[i] = v;
 }
 
+// vq_c2_kernel's norm section with a per-codeword rate penalty folded in (mcq_vq_pack_codebook_rate_f32): the same indexing and the
+// same |c|^2 loop, then c2' = fl32(c2 + fl32(lambda * fl32(16 - log2((double)width)))), width = cdf[word + 1] - cdf[word] of the group's
+// 16-bit table [k + 1].  vq_assign_kernel reads this section as |c_k|^2, so its (x2 + c2') - 2 inter is distance + lambda * bits.
+// lambda = 0 adds +0 to a non-negative sum: the bits of vq_c2_kernel.  A slot of width 0 (no valid table has one) can never win.
+__global__ void vq_c2_rate_kernel(const float* __restrict__ cb, const uint32_t* __restrict__ cdf, float lambda, int m, int k, int d,
+                                  int ntile, float* __restrict__ c2p, size_t total) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int q = (int)(i & 3);
+    const int lane = (int)((i >> 2) & 63);
+    size_t rest = i >> 8;
+    const int tile = (int)(rest % (ntile + 1));
+    const int g = (int)(rest / (ntile + 1));
+    const int word = tile * 128 + 32 * q + (lane & 31);
+    float v = 0.0f;
+    if ((lane >> 5) == 0) {
+        v = INFINITY;   // padded codewords and empty slots can never win the argmin
+        if (tile < ntile && word < k) {
+            const float* row = cb + ((size_t)g * k + word) * d;
+            float s = 0.0f;
+            for (int c = 0; c < d; ++c) s = s + row[c] * row[c];
+            const uint32_t* t = cdf + (size_t)g * (k + 1) + word;
+            const uint32_t lo = t[0], up = t[1];
+            if (up > lo) {
+                const float bits = (float)(16.0 - log2((double)(up - lo)));
+                const float pen = lambda * bits;
+                v = s + pen;
+            }
+        }
+    }
+    c2p[i] = v;
+}
+
 __global__ void vq_gather_kernel(const int64_t* __restrict__ codes, const float* __restrict__ cb, float* __restrict__ out,
                                  float* __restrict__ out2, int N, int m, int d, int hw, int k) {
     // one thread per (n, g, pixel); writes d channel planes (coalesced across threads)
@@ -405,6 +438,22 @@ extern "C" int mcq_vq_pack_codebook_f32(const float* codebook, int32_t m, int32_
                        ntile, cb_packed, cb_total, cb_alloc);
     hipLaunchKernelGGL(vq_c2_kernel, dim3((unsigned)((c2_total + 255) / 256)), dim3(256), 0, s, codebook, m, k, d, ntile,
                        cb_packed + cb_alloc, c2_total);
+    return mcq_check_launch();
+}
+
+extern "C" int mcq_vq_pack_codebook_rate_f32(const float* codebook, const uint32_t* cdf, float lambda, int32_t m, int32_t k,
+                                             int32_t d, float* cb_packed, void* stream) {
+    if (!codebook || !cdf || !cb_packed || m <= 0 || k <= 0 || d <= 0) return MCQ_EINVAL;
+    if (!(lambda >= 0.0f) || isinf(lambda)) return MCQ_EINVAL;      // (negative, NaN, inf)
+    const int ntile = (k + 127) / 128, Sp = vq_sp(d);
+    const size_t cb_total = (size_t)m * ntile * Sp * 256;
+    const size_t cb_alloc = cb_total + (size_t)VQ_PF * 256;
+    const size_t c2_total = (size_t)m * (ntile + 1) * 256;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(vq_pack_kernel, dim3((unsigned)((cb_alloc + 255) / 256)), dim3(256), 0, s, codebook, m, k, d, Sp,
+                       ntile, cb_packed, cb_total, cb_alloc);
+    hipLaunchKernelGGL(vq_c2_rate_kernel, dim3((unsigned)((c2_total + 255) / 256)), dim3(256), 0, s, codebook, cdf, lambda, m, k, d,
+                       ntile, cb_packed + cb_alloc, c2_total);
     return mcq_check_launch();
 }
 

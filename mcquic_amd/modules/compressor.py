@@ -37,9 +37,11 @@ def _forget_captures_hook(module, incompatible_keys):
 class _GraphedCall:
     """One captured hipGraph of `fn` for fixed input shapes: replay costs one launch instead of ~165 Python-side
     kernel launches (at batch 1 the eager path is host-bound: ~25 us of Python per launch against ~10 us kernels).
-    Inputs are copied into the graph's static buffers, outputs are cloned out of them."""
+    Inputs are copied into the graph's static buffers, outputs are cloned out of them.  `owns`: device buffers the captured
+    launches read besides the model's own -- they live exactly as long as this capture; `token`: what they were made under."""
 
-    def __init__(self, fn, inputs):
+    def __init__(self, fn, inputs, owns=None, token=None):
+        self.owns, self.token = owns, token
         self.static_in = [t.clone() for t in inputs]
         cur = torch.cuda.current_stream()
         side = torch.cuda.Stream()
@@ -124,16 +126,36 @@ class BaseCompressor(nn.Module):
         self._forgetCaptures()
         return super()._apply(fn, *args, **kwargs)
 
-    def _graphed(self, kind: str, fn, inputs):
+    RATE_CAPTURES = 8                # penalised-encode captures kept at a time (least recently used goes first, with its packs)
+
+    def _graphed(self, kind: str, fn, inputs, variant: tuple = (), token=None, make=None):
+        """`variant`: what else the capture bakes in besides the weights -- the lambdas of a rate-constrained encode -- so that a
+        capture taken under one lambda never serves another, or the plain path.  Such a capture launches on penalised packs that are
+        no part of the model: `make()` -> (fn, packs) builds them on a miss only, the capture OWNS them (`_GraphedCall.owns`: they
+        cannot be freed or rewritten under it), and `token` -- the codebooks' and tables' stamp they were made under -- is compared
+        on every call: a capture whose token is stale is dropped, never replayed.  At most RATE_CAPTURES of them are kept."""
         from .. import ops
         stamp = (self._weightStamp(), ops.winograd_enabled())     # (the opt-in switch re-packs every convolution: as good as new weights)
         if stamp != self._graphStamp:            # weights changed since the captures: their packed operands are stale
             self._graphs.clear()
             self._graphStamp = stamp
-        key = (kind, tuple(tuple(t.shape) for t in inputs), inputs[0].device)
+        key = (kind, tuple(tuple(t.shape) for t in inputs), inputs[0].device) + tuple(variant)
         g = self._graphs.get(key)
+        if make is None:
+            if g is None:
+                g = self._graphs[key] = _GraphedCall(fn, inputs)
+            return g(inputs)
+        if g is not None:
+            del self._graphs[key]                # (re-inserted below: the dict's order is the order of last use)
+            if g.token != token:
+                g = None
         if g is None:
-            g = self._graphs[key] = _GraphedCall(fn, inputs)
+            owned = [k for k, c in self._graphs.items() if c.owns is not None]
+            for k in owned[:max(0, len(owned) - (self.RATE_CAPTURES - 1))]:
+                del self._graphs[k]
+            fn, packs = make()
+            g = _GraphedCall(fn, inputs, owns=packs, token=token)
+        self._graphs[key] = g
         return g(inputs)
 
     @property
@@ -230,7 +252,15 @@ class BaseCompressor(nn.Module):
             y = self._encoder[i](y)
         return y
 
-    def encode(self, x: torch.Tensor) -> List[torch.Tensor]:
+    def encode(self, x: torch.Tensor, rd_lambda=None) -> List[torch.Tensor]:
+        """`rd_lambda`: None = nearest codeword; a float >= 0 (or one per level) = the entropy-constrained assignment
+        argmin_k (distance + lambda * bits_k) under the coder's current tables (`UMGMQuantizer.encode`): one model, a continuous
+        rate knob; `decode` / `decompress` and the stream format do not know about it.  Inside a caller's own stream capture
+        (where plain `encode` works as it is) nothing can be built or read back: the packs of these lambdas must have been made by
+        a call outside the capture under the current codebooks and tables, else RuntimeError -- and the caller keeps them alive
+        with its graph (`packs = model._quantizer.ratePacks(model._quantizer.rateLambdas(lam))`)."""
+        if rd_lambda is not None:
+            return self._encodeRate(x, self._quantizer.rateLambdas(rd_lambda))
         self._check(x)
         if x.shape[0] == 0:
             # an empty shard (fewer images than ranks, parallel.shard_range): PyTorch's layers hand back empty tensors of the
@@ -249,16 +279,84 @@ class BaseCompressor(nn.Module):
                 return self._graphed("decode", lambda *c: self._decoder(self._quantizer.decode(list(c))), [c.contiguous() for c in codes])
             return self._decoder(self._quantizer.decode(codes))
 
-    def compress(self, x: torch.Tensor, coder: str = "host") -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
+    def _encodeRate(self, x: torch.Tensor, lams: tuple) -> List[torch.Tensor]:
+        """`encode` with the penalised packs of `lams` (already checked).  Under `enableGraphs` the packs are made BEFORE the capture
+        and the capture keeps them (`_graphed`): its key names the lambdas, its token the codebooks and tables they were made from,
+        so a replay never reads a buffer that was freed, rewritten or made for other tables.  A lambda never seen before costs a
+        capture; the least recently used go beyond `RATE_CAPTURES`."""
+        self._check(x)
+        if x.shape[0] == 0:                                   # (empty shard, see encode)
+            return [c[:0] for c in self._encodeRate(x.new_zeros((1,) + tuple(x.shape[1:])), lams)]
+        with torch.no_grad():
+            def make():
+                packs = self._quantizer.ratePacks(lams)
+                return (lambda t: self._quantizer.encode(self._encode_latent(t), packs=packs)), packs
+            if self._graphs is not None and x.is_cuda and not torch.cuda.is_current_stream_capturing():
+                return self._graphed("encode", None, [x.contiguous()], (lams,), token=self._quantizer.rateState(), make=make)
+            return make()[0](x)
+
+    def encode_to_rate(self, x: torch.Tensor, target_bpp: float, iters: int = 12, lambda_max: float = 64.0):
+        """Codes of `x` that the coder's tables charge at most `target_bpp` bits per pixel for, by a search over ONE lambda for the
+        whole batch: returns (codes, lam, bpp) with bpp = codeBits(codes).sum() / (n h w) <= target_bpp.  The image-side encoder runs
+        once; each of the at most `iters` + 2 trials re-runs the quantizer cascade only and reads one number back (so the search runs
+        outside any capture, eagerly).  lambda = 0 is tried first: if the plain codes already meet the target they are returned with
+        lam = 0.  Then `lambda_max`: if even that misses, ValueError names the bpp it reached.  Then the bracket (0, lambda_max] is
+        narrowed `iters` times -- a sixteenth of the upper end while the lower end is still 0 (the useful lambdas span decades and
+        depend on the latents' scale), the geometric mean after -- and the smallest lambda visited that met the target is returned.
+        Rate is not strictly monotone in lambda below level 0 (a level's residual depends on the level above), hence "visited"."""
+        from .. import ops
+        self._quantizer.rateLambdas(0.0)                     # (a quantizer without tables refuses here)
+        self._check(x)
+        target, iters = float(target_bpp), int(iters)
+        lambda_max = ops.lambda_f32(lambda_max)
+        if not (target > 0.0) or not (lambda_max > 0.0) or iters < 0:
+            raise ValueError(f"encode_to_rate: target_bpp and lambda_max must be positive and finite, iters >= 0 "
+                             f"(got {target_bpp}, {lambda_max}, {iters})")
+        if x.shape[0] == 0:
+            raise ValueError("encode_to_rate: an empty batch has no rate")
+        if x.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("encode_to_rate reads the rate back every trial: it cannot be captured")
+        pixels = float(x.shape[0] * x.shape[-2] * x.shape[-1])
+        with torch.no_grad():
+            y = self._encode_latent(x)
+
+            def trial(lam: float):
+                codes = self._quantizer.encode(y) if lam == 0.0 else self._quantizer.encode(y, rd_lambda=lam)
+                return codes, float(self.codeBits(codes).sum()) / pixels
+
+            codes, bpp = trial(0.0)
+            if bpp <= target:
+                return codes, 0.0, bpp
+            best = trial(lambda_max)
+            if best[1] > target:
+                raise ValueError(f"encode_to_rate: lambda_max = {lambda_max} reaches {best[1]:.6f} bpp, above the target {target}")
+            lo, hi = 0.0, lambda_max
+            for _ in range(iters):
+                mid = ops.lambda_f32(hi / 16.0 if lo == 0.0 else (lo * hi) ** 0.5)      # (the float32 the kernel takes: what is returned is what ran)
+                if not (lo < mid < hi):
+                    break
+                got = trial(mid)
+                if got[1] <= target:
+                    hi, best = mid, got
+                else:
+                    lo = mid
+        return best[0], hi, best[1]
+
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None) -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
         """`coder`: "host" (the default) codes the streams with csrc/rans.cpp on host threads, "device" with csrc/rans_dev.hip where
-        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same."""
+        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same.  `rd_lambda`: as for `encode`."""
         self._quantizer._checkCoder(coder)
+        if rd_lambda is not None:
+            rd_lambda = self._quantizer.rateLambdas(rd_lambda)
         self._check(x)
         n, c, h, w = x.shape
         if n == 0:                                            # (empty shard: no streams, no headers)
             return self.encode(x), [], []
         with torch.no_grad():
-            codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder)
+            if rd_lambda is None:
+                codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder)
+            else:
+                codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder, rd_lambda=rd_lambda)
         header = [FileHeader(__version__, self._qp, codeSize, ImageSize(height=h, width=w, channel=c)) for codeSize in codeSizes]
         return codes, binaries, header
 

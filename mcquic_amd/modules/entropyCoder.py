@@ -32,13 +32,16 @@ def _vp(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+INVALID_PMF = "Invalid `pmf`: negative / non-finite element, all zero, or more symbols than 2**precision"      # what a refused table row raises
+
+
 def pmfToQuantizedCDF(pmf, precision: int = 16) -> List[int]:
     """Same contract as `mcquic.rans.pmfToQuantizedCDF` (list of floats -> list of k + 1 ints)."""
     p = np.ascontiguousarray(np.asarray(pmf, dtype=np.float32))
     cdf = np.empty(p.shape[0] + 1, dtype=np.uint32)
     rc = _lib.load().mcq_pmf_to_quantized_cdf(_vp(p), p.shape[0], precision, _vp(cdf))
     if rc != 0:
-        raise ValueError("Invalid `pmf`: negative / non-finite element, all zero, or more symbols than 2**precision")
+        raise ValueError(INVALID_PMF)
     return cdf.tolist()
 
 
@@ -296,7 +299,7 @@ class EntropyCoder(nn.Module):
         from .. import ops
         # the stamp the tables were built under is kept with them and compared here, apart from `_key`: `_stale` (CDFs, NormalizedFreq,
         # compress) consumes that one, and a write to `_freqEMA` that the host side has seen first must still be seen here
-        stamp = (tuple((tensor_version(f), f.data_ptr()) for f in self._freqEMA), self.__dict__.get("_devEpoch", 0))
+        stamp = self.deviceCDFStamp()
         normalize = bool(normalize)
         device = self._freqEMA[0].device
         capturing = device.type == "cuda" and torch.cuda.is_current_stream_capturing()
@@ -310,6 +313,17 @@ class EntropyCoder(nn.Module):
         tables, status = ops.pmf_to_quantized_cdf_dev(rows, normalize, *(slot[:2] if slot else (None, None)))
         slots[normalize] = (tables, status, None if capturing else stamp)       # (a captured launch has not run yet)
         return tables
+
+    def deviceCDFStamp(self):
+        """What the device tables depend on, as a hashable value: every `_freqEMA`'s (version, address) and the `resetFreqAndCDF`
+        count.  Tables built under an equal stamp are equal; nothing is launched or read here (safe while a stream is capturing)."""
+        return (tuple((tensor_version(f), f.data_ptr()) for f in self._freqEMA), self.__dict__.get("_devEpoch", 0))
+
+    def deviceCDFBuiltStamp(self, normalize: bool = False):
+        """The `deviceCDFStamp()` the tables `deviceCDFs(normalize)` last returned were built under; None when they were never built
+        or were last issued inside a capture (which has not run yet)."""
+        slot = self.__dict__.get("_devCDF", {}).get(bool(normalize))
+        return None if slot is None else slot[2]
 
     def deviceCDFStatus(self, normalize: bool = False) -> torch.Tensor:
         """int32 [sum m_l] on the device, (level, group) order, for the tables `deviceCDFs(normalize)` last built: 0 = valid; non-zero = the
@@ -659,6 +673,8 @@ class VariousMCoder(nn.Module):
         self.__dict__["_devEpoch"] = self.__dict__.get("_devEpoch", 0) + 1
 
     deviceCDFs = EntropyCoder.deviceCDFs
+    deviceCDFStamp = EntropyCoder.deviceCDFStamp
+    deviceCDFBuiltStamp = EntropyCoder.deviceCDFBuiltStamp
     deviceCDFStatus = EntropyCoder.deviceCDFStatus
     codeBits = EntropyCoder.codeBits
     codeBitsError = EntropyCoder.codeBitsError

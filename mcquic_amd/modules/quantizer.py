@@ -16,7 +16,7 @@ import torch
 from torch import nn
 
 from .. import ops
-from .entropyCoder import EntropyCoder, VariousMCoder
+from .entropyCoder import INVALID_PMF, EntropyCoder, VariousMCoder
 
 EPS = 1e-6
 _TORCH_RAND = __import__("os").environ.get("MCQUIC_AMD_TORCH_RAND", "0") == "1"      # A/B switch: draw the uniforms with torch.rand
@@ -38,6 +38,55 @@ class _CodebookCache:
             self._packed = ops.PackedCodebook(codebook)
             self._key = key
         return self._packed
+
+
+def rateLambdas(rd_lambda, levels: int) -> tuple:
+    """`rd_lambda` of encode / compress as one float per level: a float >= 0 for all levels, or a sequence of `levels` of them.
+    The kernels take lambda as a float32, so every value is rounded to float32 HERE and that rounding is what is checked, cached on
+    and returned (1e39 is finite as a double and inf as a float: refused).  Negative, NaN, infinite, non-numeric or of another
+    length: ValueError (raised before any device work)."""
+    if isinstance(rd_lambda, (list, tuple)):
+        values = list(rd_lambda)
+        if len(values) != levels:
+            raise ValueError(f"rd_lambda: one value per level needs {levels} values, got {len(values)}")
+    elif torch.is_tensor(rd_lambda) and rd_lambda.dim() > 0:
+        raise ValueError("rd_lambda: a float, or a list / tuple of one float per level (not a tensor: reading it would synchronise)")
+    else:
+        values = [rd_lambda] * levels
+    try:
+        values = [float(v) for v in values]
+    except (TypeError, ValueError):
+        raise ValueError(f"rd_lambda: expected numbers, got {rd_lambda!r}") from None
+    return tuple(ops.lambda_f32(v) for v in values)
+
+
+class _RatePackCache:
+    """One level's penalised packs (ops.pack_codebook_rate), valid under one (codebook version, table stamp) and keyed on lambda.  A
+    pack is never rewritten in place and the cache owns it only while it is listed here: whoever launches on one beyond the call that
+    asked for it -- a captured graph -- must hold it itself (`Compressor._encodeRate` stores the packs with the capture)."""
+    KEEP = 4                                   # lambdas per level (a bisection walks through many; the last few stay)
+
+    def __init__(self):
+        self._state = None
+        self._packs = {}
+
+    def get(self, codebook: torch.Tensor, cdf: torch.Tensor, stamp, lam: float) -> ops.PackedCodebook:
+        state = (ops.tensor_version(codebook), codebook.data_ptr(), stamp)
+        if state != self._state:
+            self._state, self._packs = state, {}
+        pack = self._packs.pop(lam, None)
+        if pack is None:
+            pack = ops.pack_codebook_rate(codebook, cdf, lam)
+            while len(self._packs) >= self.KEEP:
+                self._packs.pop(next(iter(self._packs)))
+        self._packs[lam] = pack                # (most recently used last)
+        return pack
+
+    def peek(self, codebook: torch.Tensor, stamp, lam: float) -> Optional[ops.PackedCodebook]:
+        """The cached pack if it is current, building nothing (for a caller whose stream is capturing)."""
+        if self._state != (ops.tensor_version(codebook), codebook.data_ptr(), stamp):
+            return None
+        return self._packs.get(lam)
 
 
 class LowerBound(nn.Module):
@@ -114,9 +163,11 @@ class _multiCodebookQuantization(nn.Module):
         self._codebook.copy_(value)
         self._cache[0].invalidate()
 
-    def encode(self, x: torch.Tensor) -> torch.Tensor:
-        """[n, m*d, h, w] -> int64 [n, m, h, w] = argmin_k ((x2 + c2) - 2 x.c), first index on ties (:144-179)."""
-        return ops.vq_assign(x, self._cache[0].get(self._codebook))
+    def encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None) -> torch.Tensor:
+        """[n, m*d, h, w] -> int64 [n, m, h, w] = argmin_k ((x2 + c2) - 2 x.c), first index on ties (:144-179).  `packed`: this
+        codebook packed by the caller -- `ops.pack_codebook_rate`'s, whose norms carry lambda * bits: the same kernel then returns
+        the entropy-constrained assignment argmin_k (distance + lambda * bits_k)."""
+        return ops.vq_assign(x, self._cache[0].get(self._codebook) if packed is None else packed)
 
     def forward(self, x: torch.Tensor, freqEMA: torch.Tensor, uniforms=None, step=None, codebook=None):
         """Training-mode forward (:181-239), forward values only (no autograd graph yet).
@@ -197,18 +248,19 @@ class _quantizerEncoder(nn.Module):
     def reAssignCodebook(self, freq: torch.Tensor) -> torch.Tensor:
         return self._quantizer.reAssignCodebook(freq)
 
-    def encode(self, x: torch.Tensor):
-        residual, code, _ = self._encode(x)
+    def encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None):
+        residual, code, _ = self._encode(x, packed)
         return residual, code
 
-    def _encode(self, x: torch.Tensor):
-        """(residual for the next level or None, code, the tensor `_quantizer.encode` received)."""
+    def _encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None):
+        """(residual for the next level or None, code, the tensor `_quantizer.encode` received).  `packed`: see
+        `_multiCodebookQuantization.encode` (the residual is taken from the plain codebook's row of the code either way)."""
         from ..nn import blocks
         z = self._latentStageEncoder(x)
         head = self._latentHead
         if head is None:
             qin = self._quantizationHead(z)
-            return None, self._quantizer.encode(qin), qin
+            return None, self._quantizer.encode(qin, packed), qin
         if blocks.lockstep_ok([self._quantizationHead, head], [z, z]):
             # latentHead(z) does not depend on the codes until its closing conv: everything before that runs in lockstep with
             # quantizationHead (same layer shapes on the same z: one multi-problem launch per layer, four problems in the
@@ -216,10 +268,10 @@ class _quantizerEncoder(nn.Module):
             last = len(head) - 1
             q, t = blocks.lockstep_infer([self._quantizationHead, head], [z, z], layers=last)
             qin = self._quantizationHead[last](q)
-            code = self._quantizer.encode(qin)
+            code = self._quantizer.encode(qin, packed)
         else:
             qin = self._quantizationHead(z)
-            code = self._quantizer.encode(qin)
+            code = self._quantizer.encode(qin, packed)
             t = z
             for i in range(len(head) - 1):
                 t = head[i](t)
@@ -332,9 +384,16 @@ class BaseQuantizer(nn.Module):
             raise NotImplementedError(f"{type(self._entropyCoder).__name__} writes raw codes, not rANS streams: it has no device coder")
         return coder == "device"
 
-    def compress(self, x: torch.Tensor, coder: str = "host"):
+    def rateLambdas(self, rd_lambda) -> tuple:
+        """`rd_lambda` checked and spread over the levels (`rateLambdas`); quantizers without 16-bit tables refuse."""
+        if not isinstance(self._entropyCoder, EntropyCoder):
+            raise NotImplementedError(f"{type(self).__name__} has no rate-constrained encoding: its {type(self._entropyCoder).__name__} "
+                                      "writes raw codes and keeps no 16-bit tables to take the penalties from")
+        return rateLambdas(rd_lambda, len(self._k))
+
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None):
         device = self._checkCoder(coder)
-        codes = self.encode(x)
+        codes = self.encode(x) if rd_lambda is None else self.encode(x, rd_lambda=self.rateLambdas(rd_lambda))
         if device:
             streams = self._entropyCoder.compressDevice(codes)
             return codes, streams.tobytes(), streams.codeSizes
@@ -374,12 +433,58 @@ class UMGMQuantizer(BaseQuantizer):
     def Codebooks(self):
         return list(encoder.Codebook for encoder in self._encoders)
 
-    def encode(self, x: torch.Tensor) -> List[torch.Tensor]:
+    def encode(self, x: torch.Tensor, rd_lambda=None, packs=None) -> List[torch.Tensor]:
+        """`rd_lambda`: None = the plain nearest-codeword cascade; a float >= 0, or one per level, = every level picks
+        argmin_k (distance + lambda * bits_k), bits_k = what the coder's 16-bit table of that level charges for code k
+        (`ratePacks`).  Same decoder, same streams.  `packs`: the result of `ratePacks`, made by a caller that must not build
+        them here (a graph capture)."""
+        if rd_lambda is None and packs is None:
+            codes = []
+            for encoder in self._encoders:
+                x, code = encoder.encode(x)
+                codes.append(code)
+            return codes
+        if packs is None:
+            packs = self.ratePacks(self.rateLambdas(rd_lambda))
         codes = []
-        for encoder in self._encoders:
-            x, code = encoder.encode(x)
+        for encoder, packed in zip(self._encoders, packs):
+            x, code = encoder.encode(x, packed)
             codes.append(code)
         return codes
+
+    @torch.no_grad()
+    def ratePacks(self, lams) -> List[ops.PackedCodebook]:
+        """One penalised pack per level for the lambdas of `rateLambdas`: penalties from `deviceCDFs(normalize=False)`, the tables
+        `compress` codes with.  Cached per level on (codebook version, the tables' stamp, lambda): two small launches per level when
+        one of them changed, none otherwise.  When the tables were rebuilt their status is read once (one small copy to the host);
+        a row `compress` would refuse raises its ValueError here.  While the current stream is capturing nothing is built: the
+        packs must be cached and current (made by an earlier call outside the capture), else RuntimeError.  The cache keeps a few
+        lambdas per level; a caller that launches on a pack later than this call returns must keep the pack itself."""
+        coder = self._entropyCoder
+        caches = self.__dict__.get("_rateCaches")
+        if caches is None:
+            caches = self.__dict__["_rateCaches"] = [_RatePackCache() for _ in self._encoders]
+        if self._entropyCoder._freqEMA[0].is_cuda and torch.cuda.is_current_stream_capturing():
+            # inside a caller's capture nothing may be built or read back: only packs that are cached and current are handed out
+            stamp = coder.deviceCDFStamp()
+            packs = [cache.peek(encoder.Codebook, stamp, lam) for cache, encoder, lam in zip(caches, self._encoders, lams)]
+            if stamp != coder.deviceCDFBuiltStamp(False) or any(p is None for p in packs):
+                raise RuntimeError("rd_lambda inside a stream capture needs its packs made beforehand: call encode(x, rd_lambda=...) with "
+                                   "these lambdas once outside the capture (and again after the codebooks or the tables change)")
+            return packs
+        tables = coder.deviceCDFs(False)
+        stamp = coder.deviceCDFBuiltStamp(False)
+        if self.__dict__.get("_rateChecked") != stamp:
+            if bool(coder.deviceCDFStatus(False).any()):
+                raise ValueError(INVALID_PMF)
+            self.__dict__["_rateChecked"] = stamp
+        return [cache.get(encoder.Codebook, table, stamp, lam)
+                for cache, encoder, table, lam in zip(caches, self._encoders, tables, lams)]
+
+    def rateState(self):
+        """What a penalised encode depends on besides the lambdas and the weights of the layers: every level's codebook (version,
+        address) and the tables' stamp.  Nothing is launched or read."""
+        return (tuple((ops.tensor_version(e.Codebook), e.Codebook.data_ptr()) for e in self._encoders), self._entropyCoder.deviceCDFStamp())
 
     def quantizerInputs(self, y: torch.Tensor) -> List[torch.Tensor]:
         """What each level's `_quantizer.encode` receives on the inference path under the current codebooks: `encode`'s cascade
@@ -391,17 +496,19 @@ class UMGMQuantizer(BaseQuantizer):
             inputs.append(qin)
         return inputs
 
-    def compress(self, x: torch.Tensor, coder: str = "host"):
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None):
         """`encode` + the entropy coder (mcquic/modules/entropyCoder.py:108-126) with the coder taken level by level: a level's codes
         leave for the host (a copy in stream order, then a host thread) as soon as they are enqueued, while the GPU computes the levels below it --
-        level 0 holds three quarters of the symbols and is ready first.  Same codes, same bytes as encode() + coder.compress()."""
+        level 0 holds three quarters of the symbols and is ready first.  Same codes, same bytes as encode() + coder.compress().
+        `rd_lambda`: as for `encode`."""
         from .entropyCoder import CODER_OVERLAP
         if self._checkCoder(coder) or not (CODER_OVERLAP and x.is_cuda):     # (the device coder takes all levels in one launch)
-            return super().compress(x, coder)
+            return super().compress(x, coder, rd_lambda)
+        packs = [None] * len(self._encoders) if rd_lambda is None else self.ratePacks(self.rateLambdas(rd_lambda))
         job = self._entropyCoder.beginCompress(len(self._encoders))
         codes = []
         for lv, encoder in enumerate(self._encoders):
-            x, code = encoder.encode(x)
+            x, code = encoder.encode(x, packs[lv])
             codes.append(code)
             job.submit(lv, code)
         binaries, codeSize = job.finish()

@@ -7,6 +7,7 @@ fallback implementation.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from typing import List, Optional, Sequence
 
@@ -705,6 +706,37 @@ class PackedCodebook:
         with _guard(cb.device):
             check(lib.mcq_vq_pack_codebook_f32(_ptr(cb), m, k, d, _ptr(self.packed), _stream()), "mcq_vq_pack_codebook_f32")
         self.codebook, self.m, self.k, self.d = cb, m, k, d
+
+
+def lambda_f32(lam: float) -> float:
+    """`lam` rounded to float32, the type the pack kernel takes it in, as a Python float; ValueError unless that is finite and >= 0
+    (1e39 is a finite double and an infinite float)."""
+    v = ctypes.c_float(float(lam)).value
+    if not (v >= 0.0) or math.isinf(v):
+        raise ValueError(f"rd_lambda: every value must be a finite float32 >= 0, got {lam!r}")
+    return v
+
+
+def pack_codebook_rate(codebook: torch.Tensor, cdf: torch.Tensor, lam: float) -> PackedCodebook:
+    """A `PackedCodebook` whose norm section carries the rate penalty `lam * bits_k` under `cdf` (uint32 [m, k + 1], one level of
+    `pmf_to_quantized_cdf_dev`; bits_k = 16 - log2(cdf[k + 1] - cdf[k])): `vq_assign` on it returns argmin_k (distance + lam * bits_k)
+    through the unchanged kernel (mcq_vq_pack_codebook_rate_f32).  `lam` = 0 gives `PackedCodebook(codebook)`'s buffer bit for bit;
+    a `lam` that is negative, NaN or infinite as a float32 is a ValueError, raised before anything is allocated.  Usable wherever a `PackedCodebook` is; `vq_gather` reads the plain codebook."""
+    lam = lambda_f32(lam)
+    cb = _dev(codebook.detach(), "codebook").clone()
+    if cb.dim() != 3:
+        raise ValueError(f"pack_codebook_rate: codebook must be [m, k, d], got {tuple(cb.shape)}")
+    m, k, d = cb.shape
+    t = _dev(cdf, "cdf", torch.uint32)
+    if tuple(t.shape) != (m, k + 1) or t.device != cb.device:
+        raise ValueError(f"pack_codebook_rate: a codebook [{m}, {k}, {d}] needs a table [{m}, {k + 1}] on {cb.device}, got {tuple(t.shape)} on {t.device}")
+    lib = _lib.load()
+    self = PackedCodebook.__new__(PackedCodebook)
+    self.packed = torch.empty(lib.mcq_packed_codebook_floats(m, k, d), dtype=torch.float32, device=cb.device)
+    with _guard(cb.device):
+        check(lib.mcq_vq_pack_codebook_rate_f32(_ptr(cb), _ptr(t), lam, m, k, d, _ptr(self.packed), _stream()), "mcq_vq_pack_codebook_rate_f32")
+    self.codebook, self.m, self.k, self.d = cb, m, k, d
+    return self
 
 
 def vq_assign(x: torch.Tensor, cb: PackedCodebook) -> torch.Tensor:
