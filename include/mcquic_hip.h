@@ -220,6 +220,50 @@ int mcq_vq_assign_ws_f32(const float* x, const float* cb_packed, int64_t* codes,
                          int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k,
                          void* workspace, void* stream);
 
+/* ---- rate control per image and per region: lambda as an operand of the assignment (csrc/vq.hip, csrc/vq_rate_map.hip) ---- */
+/* Floats of one level's `bits` section, and the section itself from that level's table cdf uint32 [m, k + 1] (device): the layout of
+ * the packed codebook's norm section, [m][k/128 + 1][64][4], holding fl32(16 - log2((double)(cdf[g, i + 1] - cdf[g, i]))) for codeword
+ * i < k, 0 for padded codewords and the upper half-wave, +inf for a slot of width 0.  It depends on the table alone. */
+size_t mcq_packed_bits_floats(int32_t m, int32_t k);
+int mcq_vq_pack_bits_f32(const uint32_t* cdf, int32_t m, int32_t k, float* bits_packed, void* stream);
+
+/* mcq_vq_assign_ws_f32 with one lambda per latent vector: codes[n, g, y, x] = argmin_k fl32(fma(lambda_v, bits_k, dist_k)), dist_k
+ * the plain entry's fma(-2, inter, x2 + c2) on the PLAIN pack `cb_packed`, bits_k from `bits_packed` (mcq_vq_pack_bits_f32), first index
+ * on ties.  lambda of (n, y, x) is lam[n * stride_n + y * stride_y + x * stride_x] (device float32, element strides >= 0; (1, 0, 0) is
+ * one lambda per image) and is shared by the m groups; the caller guarantees lambda finite and >= 0 (mcq_rate_map_levels_f32 does).
+ * lambda_v = 0 returns the plain entry's code bit for bit; a slot of width 0 never wins.  Same workspace query and launch plan as
+ * mcq_vq_assign_ws_f32.  MCQ_EINVAL before any launch for a NULL pointer (workspace may be NULL), a non-positive size or a negative
+ * stride. */
+int mcq_vq_assign_rate_map_f32(const float* x, const float* cb_packed, const float* bits_packed, const float* lam,
+                               int64_t stride_n, int64_t stride_y, int64_t stride_x, int64_t* codes,
+                               int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k,
+                               void* workspace, void* stream);
+
+/* Every level's lambda buffer from the caller's map in ONE launch.  h0 = w0 = 0: the per-image form, map[i * stride_n] -> out[l] [n] =
+ * fl32(scale_l * map_i).  Else the grid form, map at [i * stride_n + y * stride_y + x * stride_x] on the level-0 code grid h0 x w0 ->
+ * out[l] [n, h_l, w_l] with h_l = ceil(h_{l-1} / 2): level 0 is the map; level l, cell (y, x), is the mean of the level-(l - 1) cells
+ * (2y .. 2y + 1, 2x .. 2x + 1) that exist, summed in row-major order in float32 and divided by their count, taken on the unscaled map;
+ * every level is then multiplied by scale_l.  A map value that is negative, NaN or infinite counts as 0 and sets error[i] = 1 for its
+ * image (error int32 [n], written 0 or 1 by every launch; no host read).  `scales`: host [levels], each finite and >= 0;
+ * `scales_dev` (or NULL): the same on the device, read by the kernel instead, so that a captured launch takes new scales.  `out`:
+ * host array of `levels` <= MCQ_VQ_MAX_LEVELS device pointers.  MCQ_EINVAL before any launch for a NULL pointer, a non-positive n or
+ * levels, a negative size or stride, or one of h0, w0 zero alone. */
+int mcq_rate_map_levels_f32(const float* map, int32_t n, int32_t h0, int32_t w0, int64_t stride_n, int64_t stride_y, int64_t stride_x,
+                            const float* scales, const float* scales_dev /* or NULL */, int32_t levels, float* const* out,
+                            int32_t* error, void* stream);
+
+/* One step of the per-image target-rate search, one thread per image, after trial number `trial` of `trials` >= 2 ran the cascade at
+ * lam[i]: bpp_i = (bits[i, 0] + ... + bits[i, levels - 1]) / pixels (double, in level order), met = bpp_i <= target[i].  Trial 0 ran
+ * lambda = 0 (this call makes the state): met -> the image is finished with answer 0; else lam = lambda_max, bracket (0, lambda_max].
+ * Trial 1: a miss finishes the image at lambda_max.  Later trials: met -> hi = lam, else lo = lam.  Then, unless finished, the next
+ * lambda is mid = fl32(hi / 16) while lo == 0, else fl32(sqrt((double)lo * (double)hi)); when !(lo < mid < hi), or after trial
+ * trials - 1, the image is finished with answer hi.  A finished image keeps lam = its answer.  trial == trials records the final run
+ * and decides nothing.  State: lam float32 [n], bracket float32 [n, 2], done int32 [n]; trace_lam float32 / trace_bpp double
+ * [trials + 1, n] (or NULL) receive row `trial`: the lambda that ran and its bpp.  All device pointers; no host read. */
+int mcq_rate_search_step(const double* bits, const double* target, float* lam, float* bracket, int32_t* done,
+                         float* trace_lam /* or NULL */, double* trace_bpp /* or NULL */, int32_t n, int32_t levels, double pixels,
+                         float lambda_max, int32_t trial, int32_t trials, void* stream);
+
 /* out[n, g*d + j, y, x] = codebook[g, codes[n, g, y, x], j]
  * (mcquic/modules/quantizer.py:249-259 _multiCodebookDeQuantization.decode).
  * Returns MCQ_OK; indices outside [0, k) are clamped (the reference would raise IndexError). */

@@ -26,8 +26,21 @@ namespace {
 // taking it from L2 every time cost 7 % (ablation: activation loads forced to one hot line 122 -> 130 TFLOP/s).  In this
 // mode the four waves of a workgroup are the four codeword slices of ONE vector tile, which they stage in LDS once
 // ([channel][64 vectors]: the B operand of a k-step is then two conflict-free ds_read_b32 per lane).
-template <int SPC, bool XLDS>
-__global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p) {
+// RATE (mcq_vq_assign_rate_map_f32): cost = fma(lambda_v, bits_k, dist) with one lambda per latent vector, an operand of the launch
+// (VqRate), where the scalar knob folds lambda * bits into the pack's norms.  `bits` is a second section in the norms' layout and
+// reaches the accumulator rows the way c2 does; lambda_v = 0 leaves the distance bit for bit.  RATE = false is the plain kernel: every
+// addition below sits behind `if (RATE)`, a compile-time constant.
+struct VqRate {
+    const float* bits;            // [m][ntile + 1][64][4]: fl32(16 - log2 width); 0 for padded codewords and the upper half-wave; +inf at width 0
+    const float* lam;             // lambda of (image, row, column) at lam[image * sn + row * sy + column * sx], shared by the m groups
+    long long sn, sy, sx;         // element strides >= 0 ((1, 0, 0): one lambda per image)
+};
+
+template <bool RATE> struct VqRateArg {};              // nothing travels with the plain kernel
+template <> struct VqRateArg<true> : VqRate {};
+
+template <int SPC, bool XLDS, bool RATE = false>
+__global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p, VqRateArg<RATE> rt) {
     __shared__ float xs[XLDS ? 2 * SPC * 64 : 1];
     constexpr int MB = VQ_MB, NB = VQ_NB, PF = VQ_PF;
     const int lane = threadIdx.x & 63;
@@ -101,6 +114,14 @@ __global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p) {
             for (int i = 0; i < 16; ++i) x2[nb] = x2[nb] + v[nb][i] * v[nb][i];
     }
 
+    // each lane's lambdas, once (both half-waves hold the same latent vectors)
+    float lamv[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb) {
+        lamv[nb] = 0.0f;
+        if constexpr (RATE) if (valid[nb]) lamv[nb] = rt.lam[(long long)img[nb] * rt.sn + (long long)yo[nb] * rt.sy + (long long)xo[nb] * rt.sx];
+    }
+
     f32x4v A[PF];
     float B[PF][NB];
     // (grid.z workgroups x CS waves share the codeword tiles of a vector tile: small launches, see the launcher)
@@ -115,6 +136,9 @@ __global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p) {
     const unsigned wlane = (unsigned)lane * 16u;
     unsigned wso = 0;
     const f32x4v* c2l = reinterpret_cast<const f32x4v*>(p.c2p) + ((size_t)g * (p.ntile + 1) + tile0) * 64 + lane;
+    // (RATE) the bits section through a descriptor: the lane offset is the operand stream's, the tile a scalar offset -- no registers
+    __amdgpu_buffer_rsrc_t br = wr;
+    if constexpr (RATE) br = mcq_make_rsrc(rt.bits + ((size_t)g * (p.ntile + 1) + tile0) * 256, 0x7fffffffu);
     int ls = 0;
     unsigned soffL = 0;
     const unsigned step_bytes = 2u * (unsigned)HW * 4u;
@@ -140,6 +164,7 @@ __global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p) {
     const float bone = hi == 0 ? 1.0f : 0.0f;
 
     f32x4v c2a = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4v bta = f32x4v{0.0f, 0.0f, 0.0f, 0.0f};
     if (tile0 < tile1) {
 #pragma unroll
         for (int st = 0; st < PF; ++st) issue(st);
@@ -148,6 +173,9 @@ __global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p) {
 
     for (int tile = tile0; tile < tile1; ++tile) {
         const f32x4v c2n = c2l[(size_t)(tile - tile0 + 1) * 64];   // next tile's norms (one spare tile is allocated)
+        // (RATE) this tile's bits arrive behind its last k-steps: held over PF steps only, where the unrolled forms can place the load
+        const unsigned bso = (unsigned)(tile - tile0) * 1024u;
+        if (RATE && !SPC) bta = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(br, (int)wlane, (int)bso, 0));
         f32x16 acc[MB][NB];
 #pragma unroll
         for (int mb = 0; mb < MB; ++mb)
@@ -161,6 +189,8 @@ __global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p) {
             // compile-time number, so the LDS read takes an immediate offset and nothing is computed per lane
             const int lsn = SPC ? (t + PF) % (SPC ? SPC : 1) : ls;
             const unsigned son = SPC ? (unsigned)lsn * step_bytes : soffL;
+            if (RATE && SPC && t == (SPC ? SPC : PF) - PF && st == 0)
+                bta = __builtin_bit_cast(f32x4v, __builtin_amdgcn_raw_buffer_load_b128(br, (int)wlane, (int)bso, 0));
             // vector-block major, each activation slot refilled right after its last use (as in the convolution kernel)
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
@@ -197,6 +227,37 @@ __global__ __launch_bounds__(256, 2) void vq_assign_kernel(VqK p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) z[r] = 0.0f;
             const f32x16 c2d = __builtin_amdgcn_mfma_f32_32x32x2f32(c2a[mb], bone, z, 0, 0, 0);
+            if constexpr (RATE) {
+                // the distances first, in place of the inner products (c2d is then dead), then bits_k in the rows' layout, exact, and
+                // cost = fma(lambda_v, bits_k, dist): one more rounding (a width-0 slot gives +inf, or NaN at lambda 0: never < best)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        const f32x2v s2 = f32x2v{x2[nb], x2[nb]} + f32x2v{c2d[r], c2d[r + 1]};
+                        const f32x2v dv2 = __builtin_elementwise_fma(f32x2v{-2.0f, -2.0f}, f32x2v{acc[mb][nb][r], acc[mb][nb][r + 1]}, s2);
+                        acc[mb][nb][r] = dv2[0]; acc[mb][nb][r + 1] = dv2[1];
+                    }
+                const f32x16 btd = __builtin_amdgcn_mfma_f32_32x32x2f32(bta[mb], bone, z, 0, 0, 0);
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) {
+                    float dv[16];
+#pragma unroll
+                    for (int r = 0; r < 16; r += 2) {
+                        const f32x2v dv2 = __builtin_elementwise_fma(f32x2v{lamv[nb], lamv[nb]}, f32x2v{btd[r], btd[r + 1]},
+                                                                     f32x2v{acc[mb][nb][r], acc[mb][nb][r + 1]});
+                        dv[r] = dv2[0]; dv[r + 1] = dv2[1];
+                    }
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int word = word0 + mb * 32 + mcq_drow(r, hi);
+                        if (dv[r] < best[nb]) { best[nb] = dv[r]; bidx[nb] = word; }
+                    }
+                }
+                // one band at a time: hipcc otherwise issues the eight row-layout MFMAs of a tile together and their 128 results spill
+                __builtin_amdgcn_sched_barrier(0);
+                continue;
+            }
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 // (x2 + c2) - 2 * inter ; 2 * inter is exact, so the fused form rounds identically.  Two distances per
@@ -499,9 +560,10 @@ extern "C" int mcq_vq_assign_f32(const float* x, const float* cb_packed, int64_t
     return mcq_vq_assign_ws_f32(x, cb_packed, codes, N, m, d, h, w, k, nullptr, stream);
 }
 
-extern "C" int mcq_vq_assign_ws_f32(const float* x, const float* cb_packed, int64_t* codes, int32_t N, int32_t m, int32_t d,
-                                    int32_t h, int32_t w, int32_t k, void* workspace, void* stream) {
-    if (!x || !cb_packed || !codes || N <= 0 || m <= 0 || d <= 0 || h <= 0 || w <= 0 || k <= 0) return MCQ_EINVAL;
+namespace {
+// the plain launch (rate == nullptr) and the per-vector-lambda one share the plan, the workspace and the fold
+int vq_assign_launch(const float* x, const float* cb_packed, const VqRate* rate, int64_t* codes, int32_t N, int32_t m, int32_t d,
+                     int32_t h, int32_t w, int32_t k, void* workspace, void* stream) {
     if ((uint64_t)d * h * w * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
     VqK p;
     p.x = x; p.codes = codes; p.N = N; p.m = m; p.d = d; p.h = h; p.w = w; p.k = k;
@@ -532,15 +594,40 @@ extern "C" int mcq_vq_assign_ws_f32(const float* x, const float* cb_packed, int6
     const int per_wg = 4 >> cs_log2;
     const unsigned gx = (unsigned)((vtiles + per_wg - 1) / per_wg);
     const dim3 grid(gx, (unsigned)m, (unsigned)p.zs);
-    if (p.Sp == 32) hipLaunchKernelGGL((vq_assign_kernel<32, false>), grid, dim3(256), 0, (hipStream_t)stream, p);          // d = 64
-    else if (p.Sp == 8) hipLaunchKernelGGL((vq_assign_kernel<8, false>), grid, dim3(256), 0, (hipStream_t)stream, p);      // d = 16 (model No. 12), d = 8 ... 15
-    else if (p.Sp == 128 && cs_log2 == 2) hipLaunchKernelGGL((vq_assign_kernel<128, true>), grid, dim3(256), 0, (hipStream_t)stream, p);   // d = 256
-    else if (p.Sp == 128) hipLaunchKernelGGL((vq_assign_kernel<128, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((vq_assign_kernel<0, false>), grid, dim3(256), 0, (hipStream_t)stream, p);
+    if (rate) {
+        VqRateArg<true> rt;
+        static_cast<VqRate&>(rt) = *rate;
+        if (p.Sp == 32) hipLaunchKernelGGL((vq_assign_kernel<32, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
+        else if (p.Sp == 8) hipLaunchKernelGGL((vq_assign_kernel<8, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
+        else if (p.Sp == 128 && cs_log2 == 2) hipLaunchKernelGGL((vq_assign_kernel<128, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
+        else if (p.Sp == 128) hipLaunchKernelGGL((vq_assign_kernel<128, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
+        else hipLaunchKernelGGL((vq_assign_kernel<0, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
+    }
+    else if (p.Sp == 32) hipLaunchKernelGGL((vq_assign_kernel<32, false>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});          // d = 64
+    else if (p.Sp == 8) hipLaunchKernelGGL((vq_assign_kernel<8, false>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});      // d = 16 (model No. 12), d = 8 ... 15
+    else if (p.Sp == 128 && cs_log2 == 2) hipLaunchKernelGGL((vq_assign_kernel<128, true>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});   // d = 256
+    else if (p.Sp == 128) hipLaunchKernelGGL((vq_assign_kernel<128, false>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});
+    else hipLaunchKernelGGL((vq_assign_kernel<0, false>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});
     if (p.zs > 1)
         hipLaunchKernelGGL(vq_fold_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p.ws_best, p.ws_idx, p.zs,
                            nvec, codes);
     return mcq_check_launch();
+}
+}  // namespace
+
+extern "C" int mcq_vq_assign_ws_f32(const float* x, const float* cb_packed, int64_t* codes, int32_t N, int32_t m, int32_t d,
+                                    int32_t h, int32_t w, int32_t k, void* workspace, void* stream) {
+    if (!x || !cb_packed || !codes || N <= 0 || m <= 0 || d <= 0 || h <= 0 || w <= 0 || k <= 0) return MCQ_EINVAL;
+    return vq_assign_launch(x, cb_packed, nullptr, codes, N, m, d, h, w, k, workspace, stream);
+}
+
+extern "C" int mcq_vq_assign_rate_map_f32(const float* x, const float* cb_packed, const float* bits_packed, const float* lam,
+                                          int64_t stride_n, int64_t stride_y, int64_t stride_x, int64_t* codes, int32_t N, int32_t m,
+                                          int32_t d, int32_t h, int32_t w, int32_t k, void* workspace, void* stream) {
+    if (!x || !cb_packed || !bits_packed || !lam || !codes || N <= 0 || m <= 0 || d <= 0 || h <= 0 || w <= 0 || k <= 0) return MCQ_EINVAL;
+    if (stride_n < 0 || stride_y < 0 || stride_x < 0) return MCQ_EINVAL;
+    const VqRate rt{bits_packed, lam, (long long)stride_n, (long long)stride_y, (long long)stride_x};
+    return vq_assign_launch(x, cb_packed, &rt, codes, N, m, d, h, w, k, workspace, stream);
 }
 
 extern "C" int mcq_vq_gather_f32(const int64_t* codes, const float* codebook, float* out, float* out_silu, int32_t N,

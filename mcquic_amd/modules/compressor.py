@@ -126,6 +126,13 @@ class BaseCompressor(nn.Module):
         self._forgetCaptures()
         return super()._apply(fn, *args, **kwargs)
 
+    def _dropStaleCaptures(self):
+        from .. import ops
+        stamp = (self._weightStamp(), ops.winograd_enabled())     # (the opt-in switch re-packs every convolution: as good as new weights)
+        if stamp != self._graphStamp:            # weights changed since the captures: their packed operands are stale
+            self._graphs.clear()
+            self._graphStamp = stamp
+
     RATE_CAPTURES = 8                # penalised-encode captures kept at a time (least recently used goes first, with its packs)
 
     def _graphed(self, kind: str, fn, inputs, variant: tuple = (), token=None, make=None):
@@ -134,11 +141,7 @@ class BaseCompressor(nn.Module):
         no part of the model: `make()` -> (fn, packs) builds them on a miss only, the capture OWNS them (`_GraphedCall.owns`: they
         cannot be freed or rewritten under it), and `token` -- the codebooks' and tables' stamp they were made under -- is compared
         on every call: a capture whose token is stale is dropped, never replayed.  At most RATE_CAPTURES of them are kept."""
-        from .. import ops
-        stamp = (self._weightStamp(), ops.winograd_enabled())     # (the opt-in switch re-packs every convolution: as good as new weights)
-        if stamp != self._graphStamp:            # weights changed since the captures: their packed operands are stale
-            self._graphs.clear()
-            self._graphStamp = stamp
+        self._dropStaleCaptures()
         key = (kind, tuple(tuple(t.shape) for t in inputs), inputs[0].device) + tuple(variant)
         g = self._graphs.get(key)
         if make is None:
@@ -252,13 +255,19 @@ class BaseCompressor(nn.Module):
             y = self._encoder[i](y)
         return y
 
-    def encode(self, x: torch.Tensor, rd_lambda=None) -> List[torch.Tensor]:
+    def encode(self, x: torch.Tensor, rd_lambda=None, rd_map=None) -> List[torch.Tensor]:
         """`rd_lambda`: None = nearest codeword; a float >= 0 (or one per level) = the entropy-constrained assignment
         argmin_k (distance + lambda * bits_k) under the coder's current tables (`UMGMQuantizer.encode`): one model, a continuous
         rate knob; `decode` / `decompress` and the stream format do not know about it.  Inside a caller's own stream capture
         (where plain `encode` works as it is) nothing can be built or read back: the packs of these lambdas must have been made by
         a call outside the capture under the current codebooks and tables, else RuntimeError -- and the caller keeps them alive
-        with its graph (`packs = model._quantizer.ratePacks(model._quantizer.rateLambdas(lam))`)."""
+        with its graph (`packs = model._quantizer.ratePacks(model._quantizer.rateLambdas(lam))`).
+        `rd_map`: rate control per image ([n]) or per level-0 code cell ([n, H / 16, W / 16] of the 128-aligned image), a float32
+        device tensor; `rd_lambda` is then the per-level scale (`UMGMQuantizer.encode`).  The map is an operand: under `enableGraphs`
+        one capture per image shape and map form serves every map and every scale; inside a caller's capture it works once a call
+        outside it has made the tables' bits sections."""
+        if rd_map is not None:
+            return self._encodeRateMap(x, self._quantizer.rateLambdas(1.0 if rd_lambda is None else rd_lambda), rd_map)
         if rd_lambda is not None:
             return self._encodeRate(x, self._quantizer.rateLambdas(rd_lambda))
         self._check(x)
@@ -295,7 +304,55 @@ class BaseCompressor(nn.Module):
                 return self._graphed("encode", None, [x.contiguous()], (lams,), token=self._quantizer.rateState(), make=make)
             return make()[0](x)
 
-    def encode_to_rate(self, x: torch.Tensor, target_bpp: float, iters: int = 12, lambda_max: float = 64.0):
+    def _rateGrid(self, x: torch.Tensor):
+        """(n, h0, w0): the level-0 code grid of the image batch `x` -- the aligned image halved four times."""
+        base = self._padding._base
+        h, w = -(-int(x.shape[-2]) // base) * base, -(-int(x.shape[-1]) // base) * base
+        for _ in range(4):
+            h, w = (h + 1) // 2, (w + 1) // 2
+        return int(x.shape[0]), h, w
+
+    def _encodeRateMap(self, x: torch.Tensor, scales: tuple, rd_map: torch.Tensor) -> List[torch.Tensor]:
+        """`encode` with `rd_map` (scales already checked).  Under `enableGraphs` the map and the scales are INPUTS of the capture: its
+        key names the image shape and the map's shape, not their values, and it holds no lambda-dependent buffer -- only the tables'
+        bits sections, which it keeps, and whose stamp is compared on every call (a capture under older tables is taken again)."""
+        self._check(x)
+        self._quantizer.checkRateMap(rd_map, *self._rateGrid(x), x.device)
+        if x.shape[0] == 0:
+            raise ValueError("rd_map: an empty batch has no map")
+        with torch.no_grad():
+            if self._graphs is None or not x.is_cuda or torch.cuda.is_current_stream_capturing():
+                return self._quantizer.encode(self._encode_latent(x), rd_lambda=scales, rd_map=rd_map)
+            self._dropStaleCaptures()
+            inputs = [x.contiguous(), rd_map.contiguous()]
+            key = ("encode", tuple(tuple(t.shape) for t in inputs), x.device, "rd_map")
+            token = self._quantizer._entropyCoder.deviceCDFStamp()
+            g = self._graphs.get(key)
+            if g is None or g.token != token:
+                bits = self._quantizer.rateBitsPacks()
+                ones = (1.0,) * len(scales)          # (the kernel reads the scales from the capture's third input)
+                pinned = torch.tensor(scales, dtype=torch.float32).pin_memory()
+                g = self._graphs[key] = _GraphedCall(lambda t, mp, sc: self._quantizer.encode(self._encode_latent(t), rd_lambda=ones, rd_map=mp,
+                                                                                          scales_dev=sc), inputs + [pinned.to(x.device)], token=token)
+                # what the captured launches read and write besides the inputs lives as long as the capture: the tables' bits sections,
+                # and the error word of the captured call (allocated inside the capture, so in the graph's own pool)
+                g.bits, g.error = bits, self._quantizer.rateMapError()
+                g.scales, g.pinned = scales, pinned
+            elif g.scales != scales:                 # new scales go into the static input from a pinned buffer, and only when they change
+                g.pinned.copy_(torch.tensor(scales, dtype=torch.float32))
+                g.static_in[2].copy_(g.pinned)
+                g.scales = scales
+            codes = g(inputs)                        # (zip stops at the two inputs given: the scales are already in place)
+            self._quantizer.__dict__["_rateMapErr"] = g.error      # the capture's own word, just rewritten by THIS replay (nothing allocated)
+            return codes
+
+    def rateMapError(self) -> torch.Tensor:
+        """int32 [n] on the device, from the last `encode` / `compress` / `encode_to_rate` call with a map, replays under `enableGraphs`
+        included: 1 where an image's map held a negative, NaN or infinite value (which counted as 0).  Nothing is read on the host."""
+        return self._quantizer.rateMapError()
+
+    def encode_to_rate(self, x: torch.Tensor, target_bpp, iters: int = 12, lambda_max: float = 64.0, per_image: bool = False,
+                       trace: bool = False):
         """Codes of `x` that the coder's tables charge at most `target_bpp` bits per pixel for, by a search over ONE lambda for the
         whole batch: returns (codes, lam, bpp) with bpp = codeBits(codes).sum() / (n h w) <= target_bpp.  The image-side encoder runs
         once; each of the at most `iters` + 2 trials re-runs the quantizer cascade only and reads one number back (so the search runs
@@ -307,6 +364,8 @@ class BaseCompressor(nn.Module):
         from .. import ops
         self._quantizer.rateLambdas(0.0)                     # (a quantizer without tables refuses here)
         self._check(x)
+        if per_image:
+            return self._encodeToRatePerImage(x, target_bpp, int(iters), lambda_max, bool(trace))
         target, iters = float(target_bpp), int(iters)
         lambda_max = ops.lambda_f32(lambda_max)
         if not (target > 0.0) or not (lambda_max > 0.0) or iters < 0:
@@ -342,10 +401,65 @@ class BaseCompressor(nn.Module):
                     lo = mid
         return best[0], hi, best[1]
 
-    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None) -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
+    def _encodeToRatePerImage(self, x: torch.Tensor, target_bpp, iters: int, lambda_max, trace: bool):
+        """`encode_to_rate(per_image=True)`: every image is brought to ITS target by its own lambda, the search's state on the device.
+        `target_bpp`: a float, or a device tensor [n].  The image-side encoder runs once; then `iters` + 2 lockstep trials of the
+        quantizer cascade with rd_map = lambda[n], each followed by `codeBits` and one `ops.rate_search_step` launch; then the final
+        cascade at the chosen lambdas.  Per image the rule is the batch search's: 0 first (met: done), `lambda_max` (missed: the image
+        ends there), else the bracket -- a sixteenth of the upper end while the lower is 0, the geometric mean after, frozen when the
+        float32 midpoint leaves the open bracket -- and the answer is the upper end.  Finished images ride along at their answer.
+        Nothing is read on the host: with the bits sections made beforehand (any `encode(x, rd_map=...)` outside) the whole call
+        captures into a caller's graph.  Returns (codes, lam float32 [n], bpp float64 [n]) on the device, bpp = the final run's
+        codeBits summed over the levels / (H W); an unreachable target does not raise: the image ends at `lambda_max` and its bpp
+        shows it.  `trace`: also (lams float32, bpps float64) [trials, n], what every trial ran at and reached."""
+        from .. import ops
+        lambda_max = ops.lambda_f32(lambda_max)
+        if not (lambda_max > 0.0) or iters < 0:
+            raise ValueError(f"encode_to_rate: lambda_max must be positive and finite, iters >= 0 (got {lambda_max}, {iters})")
+        n = int(x.shape[0])
+        if n == 0:
+            raise ValueError("encode_to_rate: an empty batch has no rate")
+        if torch.is_tensor(target_bpp) and target_bpp.dim() > 0:
+            if tuple(target_bpp.shape) != (n,) or target_bpp.device != x.device or not target_bpp.dtype.is_floating_point:
+                raise ValueError(f"encode_to_rate: a target tensor must be floating point [{n}] on {x.device}, got "
+                                 f"{target_bpp.dtype} {tuple(target_bpp.shape)} on {target_bpp.device}")
+            target = None
+        else:
+            target = float(target_bpp)
+            if not (target > 0.0) or target == float("inf"):
+                raise ValueError(f"encode_to_rate: target_bpp must be positive and finite (got {target_bpp})")
+        if not x.is_cuda:
+            raise RuntimeError(f"mcquic_amd: encode_to_rate(per_image=True) runs on a HIP device only (input on {x.device})")
+        dev, trials = x.device, iters + 2
+        pixels = float(x.shape[-2] * x.shape[-1])
+        with torch.no_grad():
+            tgt = target_bpp.to(torch.float64).contiguous() if target is None else torch.full((n,), target, dtype=torch.float64, device=dev)
+            lam = torch.zeros(n, dtype=torch.float32, device=dev)
+            bracket = torch.empty((n, 2), dtype=torch.float32, device=dev)
+            done = torch.empty(n, dtype=torch.int32, device=dev)
+            tlam = torch.empty((trials + 1, n), dtype=torch.float32, device=dev)
+            tbpp = torch.empty((trials + 1, n), dtype=torch.float64, device=dev)
+            y = self._encode_latent(x)
+            for t in range(trials + 1):                       # (the last one is the final run: recorded, nothing decided)
+                codes = self._quantizer.encode(y, rd_map=lam)
+                ops.rate_search_step(self.codeBits(codes), tgt, lam, bracket, done, tlam, tbpp, pixels, lambda_max, t, trials)
+        out = (codes, lam, tbpp[trials].clone())
+        return out + (tlam[:trials], tbpp[:trials]) if trace else out
+
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None) -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
         """`coder`: "host" (the default) codes the streams with csrc/rans.cpp on host threads, "device" with csrc/rans_dev.hip where
-        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same.  `rd_lambda`: as for `encode`."""
+        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same.  `rd_lambda`, `rd_map`: as for `encode`."""
         self._quantizer._checkCoder(coder)
+        if rd_map is not None:
+            scales = self._quantizer.rateLambdas(1.0 if rd_lambda is None else rd_lambda)
+            self._check(x)
+            self._quantizer.checkRateMap(rd_map, *self._rateGrid(x), x.device)
+            n, c, h, w = x.shape
+            if n == 0:
+                raise ValueError("rd_map: an empty batch has no map")
+            with torch.no_grad():
+                codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder, rd_lambda=scales, rd_map=rd_map)
+            return codes, binaries, [FileHeader(__version__, self._qp, codeSize, ImageSize(height=h, width=w, channel=c)) for codeSize in codeSizes]
         if rd_lambda is not None:
             rd_lambda = self._quantizer.rateLambdas(rd_lambda)
         self._check(x)

@@ -169,6 +169,11 @@ class _multiCodebookQuantization(nn.Module):
         the entropy-constrained assignment argmin_k (distance + lambda * bits_k)."""
         return ops.vq_assign(x, self._cache[0].get(self._codebook) if packed is None else packed)
 
+    def encodeRateMap(self, x: torch.Tensor, bits: torch.Tensor, lam: torch.Tensor) -> torch.Tensor:
+        """argmin_k fma(lambda_v, bits_k, distance) with one lambda per latent vector (`ops.vq_assign_rate_map`): the plain pack, the
+        level's `ops.pack_bits` section, `lam` [n] or [n, h, w] of `ops.rate_map_levels`."""
+        return ops.vq_assign_rate_map(x, self._cache[0].get(self._codebook), bits, lam)
+
     def forward(self, x: torch.Tensor, freqEMA: torch.Tensor, uniforms=None, step=None, codebook=None):
         """Training-mode forward (:181-239), forward values only (no autograd graph yet).
         `codebook`: an alias of `self._codebook` to differentiate through (a quantizer whose codebook is shared by several levels
@@ -248,19 +253,21 @@ class _quantizerEncoder(nn.Module):
     def reAssignCodebook(self, freq: torch.Tensor) -> torch.Tensor:
         return self._quantizer.reAssignCodebook(freq)
 
-    def encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None):
-        residual, code, _ = self._encode(x, packed)
+    def encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None, rate=None):
+        residual, code, _ = self._encode(x, packed, rate)
         return residual, code
 
-    def _encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None):
+    def _encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None, rate=None):
         """(residual for the next level or None, code, the tensor `_quantizer.encode` received).  `packed`: see
-        `_multiCodebookQuantization.encode` (the residual is taken from the plain codebook's row of the code either way)."""
+        `_multiCodebookQuantization.encode` (the residual is taken from the plain codebook's row of the code either way).  `rate`:
+        (bits section, lambda buffer) of this level for `_multiCodebookQuantization.encodeRateMap` instead."""
         from ..nn import blocks
         z = self._latentStageEncoder(x)
         head = self._latentHead
+        assign = self._quantizer.encode if rate is None else (lambda q, _packed: self._quantizer.encodeRateMap(q, *rate))
         if head is None:
             qin = self._quantizationHead(z)
-            return None, self._quantizer.encode(qin, packed), qin
+            return None, assign(qin, packed), qin
         if blocks.lockstep_ok([self._quantizationHead, head], [z, z]):
             # latentHead(z) does not depend on the codes until its closing conv: everything before that runs in lockstep with
             # quantizationHead (same layer shapes on the same z: one multi-problem launch per layer, four problems in the
@@ -268,10 +275,10 @@ class _quantizerEncoder(nn.Module):
             last = len(head) - 1
             q, t = blocks.lockstep_infer([self._quantizationHead, head], [z, z], layers=last)
             qin = self._quantizationHead[last](q)
-            code = self._quantizer.encode(qin, packed)
+            code = assign(qin, packed)
         else:
             qin = self._quantizationHead(z)
-            code = self._quantizer.encode(qin, packed)
+            code = assign(qin, packed)
             t = z
             for i in range(len(head) - 1):
                 t = head[i](t)
@@ -391,9 +398,13 @@ class BaseQuantizer(nn.Module):
                                       "writes raw codes and keeps no 16-bit tables to take the penalties from")
         return rateLambdas(rd_lambda, len(self._k))
 
-    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None):
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None):
         device = self._checkCoder(coder)
-        codes = self.encode(x) if rd_lambda is None else self.encode(x, rd_lambda=self.rateLambdas(rd_lambda))
+        if rd_map is not None:
+            self.rateLambdas(1.0 if rd_lambda is None else rd_lambda)          # (quantizers without tables refuse here)
+            codes = self.encode(x, rd_lambda=rd_lambda, rd_map=rd_map)
+        else:
+            codes = self.encode(x) if rd_lambda is None else self.encode(x, rd_lambda=self.rateLambdas(rd_lambda))
         if device:
             streams = self._entropyCoder.compressDevice(codes)
             return codes, streams.tobytes(), streams.codeSizes
@@ -433,11 +444,27 @@ class UMGMQuantizer(BaseQuantizer):
     def Codebooks(self):
         return list(encoder.Codebook for encoder in self._encoders)
 
-    def encode(self, x: torch.Tensor, rd_lambda=None, packs=None) -> List[torch.Tensor]:
+    def encode(self, x: torch.Tensor, rd_lambda=None, packs=None, rd_map=None, scales_dev=None) -> List[torch.Tensor]:
         """`rd_lambda`: None = the plain nearest-codeword cascade; a float >= 0, or one per level, = every level picks
         argmin_k (distance + lambda * bits_k), bits_k = what the coder's 16-bit table of that level charges for code k
         (`ratePacks`).  Same decoder, same streams.  `packs`: the result of `ratePacks`, made by a caller that must not build
-        them here (a graph capture)."""
+        them here (a graph capture).
+        `rd_map`: rate control per image or per region -- a float32 device tensor, [n] (one lambda per image) or [n, h0, w0] (one per
+        level-0 code cell; the levels below take the mean of their 2 x 2 cells, `ops.rate_map_levels`).  `rd_lambda` is then the
+        per-level scale (None = 1), lambda = fl32(scale_l * map_l) an operand of the assignment kernel, not a constant of a pack: the
+        map's values are never read on the host, any map and any scale run the same launches on the plain packs and the tables'
+        `rateBitsPacks`.  A negative, NaN or infinite map value counts as 0 and shows in `rateMapError()`.  `scales_dev`: the scales
+        again as a device tensor the kernel reads instead (for a capture whose replays take new scales).  A caller that captures this
+        call into a graph of its own keeps `rateBitsPacks()`'s list with that graph, as it keeps `ratePacks` for the scalar path: the
+        graph launches on those sections, and the cache here lets go of them when the tables change."""
+        if rd_map is not None:
+            if packs is not None:
+                raise ValueError("rd_map: `packs` belong to the scalar rd_lambda path")
+            codes = []
+            for encoder, rate in zip(self._encoders, self._rateOperands(x, rd_lambda, rd_map, scales_dev)):
+                x, code = encoder.encode(x, rate=rate)
+                codes.append(code)
+            return codes
         if rd_lambda is None and packs is None:
             codes = []
             for encoder in self._encoders:
@@ -481,6 +508,65 @@ class UMGMQuantizer(BaseQuantizer):
         return [cache.get(encoder.Codebook, table, stamp, lam)
                 for cache, encoder, table, lam in zip(caches, self._encoders, tables, lams)]
 
+    def _rateOperands(self, y: torch.Tensor, rd_lambda, rd_map, scales_dev=None):
+        """[(bits section, lambda buffer)] per level for the latent `y`: everything checked on the host first, then ONE launch
+        (`ops.rate_map_levels`).  The error word is a fresh tensor on every call -- inside a capture it belongs to that graph's pool, so
+        no replay ever writes a word that a later call has replaced -- and becomes what `rateMapError()` returns."""
+        scales = self.rateLambdas(1.0 if rd_lambda is None else rd_lambda)
+        self.checkRateMap(rd_map, int(y.shape[0]), (int(y.shape[-2]) + 1) // 2, (int(y.shape[-1]) + 1) // 2, y.device)
+        bits = self.rateBitsPacks()
+        lams, self.__dict__["_rateMapErr"] = ops.rate_map_levels(rd_map, scales, scales_dev=scales_dev)
+        return list(zip(bits, lams))
+
+    @staticmethod
+    def checkRateMap(rd_map, n: int, h0: int, w0: int, device) -> None:
+        """ValueError, before any launch, unless `rd_map` is a float32 tensor on `device`, [n] or [n, h0, w0] with h0 x w0 the level-0
+        code grid (half the latent's size, with ceil)."""
+        if not torch.is_tensor(rd_map):
+            raise ValueError(f"rd_map: expected a float32 tensor, got {type(rd_map).__name__}")
+        if rd_map.dtype != torch.float32:
+            raise ValueError(f"rd_map: must be float32, got {rd_map.dtype}")
+        if rd_map.device != device:
+            raise ValueError(f"rd_map: lives on {rd_map.device}, the images on {device}")
+        if tuple(rd_map.shape) not in ((n,), (n, h0, w0)):
+            raise ValueError(f"rd_map: expected [{n}] (per image) or [{n}, {h0}, {w0}] (the level-0 code grid), got {tuple(rd_map.shape)}")
+
+    @torch.no_grad()
+    def rateBitsPacks(self) -> List[torch.Tensor]:
+        """One `ops.pack_bits` section per level from `deviceCDFs(normalize=False)`, cached on the tables' stamp alone (they depend on
+        neither lambda nor the codebooks): one small launch per level when the tables changed, none otherwise.  The tables' status is
+        read once per stamp, as in `ratePacks`, with its ValueError.  While the current stream is capturing nothing is built: the
+        sections must be cached and current, else RuntimeError."""
+        coder = self._entropyCoder
+        cached = self.__dict__.get("_rateBits")                                     # (stamp, [sections])
+        if coder._freqEMA[0].is_cuda and torch.cuda.is_current_stream_capturing():
+            stamp = coder.deviceCDFStamp()
+            # (cached[0] is the stamp of tables that were built and checked outside a capture; `codeBits` inside this capture may have
+            #  re-issued the table launch since, which clears the built stamp but not what the sections were made from)
+            if cached is None or cached[0] != stamp:
+                raise RuntimeError("rd_map inside a stream capture needs its bits sections made beforehand: call encode(x, rd_map=...) once "
+                                   "outside the capture (and again after the tables change)")
+            return cached[1]
+        tables = coder.deviceCDFs(False)
+        stamp = coder.deviceCDFBuiltStamp(False)
+        if self.__dict__.get("_rateChecked") != stamp:
+            if bool(coder.deviceCDFStatus(False).any()):
+                raise ValueError(INVALID_PMF)
+            self.__dict__["_rateChecked"] = stamp
+        if cached is None or cached[0] != stamp:
+            cached = self.__dict__["_rateBits"] = (stamp, [ops.pack_bits(t) for t in tables])
+        return cached[1]
+
+    def rateMapError(self) -> torch.Tensor:
+        """int32 [n] on the device, from the last `encode(..., rd_map=...)` issued here: 1 where an image's map held a negative, NaN or
+        infinite value (taken as 0).  Nothing is read here.  Every call writes a word of its own; the word of a call that a caller
+        captured is that graph's, rewritten by each replay, and is what this returns until another call is issued
+        (`Compressor.rateMapError` also follows the replays of `enableGraphs`)."""
+        err = self.__dict__.get("_rateMapErr")
+        if err is None:
+            raise RuntimeError("rateMapError: no encode with `rd_map` has run yet")
+        return err
+
     def rateState(self):
         """What a penalised encode depends on besides the lambdas and the weights of the layers: every level's codebook (version,
         address) and the tables' stamp.  Nothing is launched or read."""
@@ -496,19 +582,20 @@ class UMGMQuantizer(BaseQuantizer):
             inputs.append(qin)
         return inputs
 
-    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None):
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None):
         """`encode` + the entropy coder (mcquic/modules/entropyCoder.py:108-126) with the coder taken level by level: a level's codes
         leave for the host (a copy in stream order, then a host thread) as soon as they are enqueued, while the GPU computes the levels below it --
         level 0 holds three quarters of the symbols and is ready first.  Same codes, same bytes as encode() + coder.compress().
-        `rd_lambda`: as for `encode`."""
+        `rd_lambda`, `rd_map`: as for `encode` (the same overlap with either)."""
         from .entropyCoder import CODER_OVERLAP
         if self._checkCoder(coder) or not (CODER_OVERLAP and x.is_cuda):     # (the device coder takes all levels in one launch)
-            return super().compress(x, coder, rd_lambda)
-        packs = [None] * len(self._encoders) if rd_lambda is None else self.ratePacks(self.rateLambdas(rd_lambda))
+            return super().compress(x, coder, rd_lambda, rd_map)
+        rates = [None] * len(self._encoders) if rd_map is None else self._rateOperands(x, rd_lambda, rd_map)
+        packs = [None] * len(self._encoders) if rd_lambda is None or rd_map is not None else self.ratePacks(self.rateLambdas(rd_lambda))
         job = self._entropyCoder.beginCompress(len(self._encoders))
         codes = []
         for lv, encoder in enumerate(self._encoders):
-            x, code = encoder.encode(x, packs[lv])
+            x, code = encoder.encode(x, packs[lv], rates[lv])
             codes.append(code)
             job.submit(lv, code)
         binaries, codeSize = job.finish()

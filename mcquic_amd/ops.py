@@ -755,6 +755,126 @@ def vq_assign(x: torch.Tensor, cb: PackedCodebook) -> torch.Tensor:
     return codes
 
 
+def pack_bits(cdf: torch.Tensor) -> torch.Tensor:
+    """The `bits` section of one level for `vq_assign_rate_map` from its table `cdf` uint32 [m, k + 1] on the device
+    (mcq_vq_pack_bits_f32): float32 in the layout of a packed codebook's norms, fl32(16 - log2 width) per codeword, 0 in the padding,
+    +inf for a slot of width 0.  It depends on the table alone -- not on lambda, not on the codebook."""
+    t = _dev(cdf, "cdf", torch.uint32)
+    if t.dim() != 2 or t.shape[1] < 2:
+        raise ValueError(f"pack_bits: a table [m, k + 1], got {tuple(t.shape)}")
+    m, k = int(t.shape[0]), int(t.shape[1]) - 1
+    lib = _lib.load()
+    out = torch.empty(lib.mcq_packed_bits_floats(m, k), dtype=torch.float32, device=t.device)
+    with _guard(t.device):
+        check(lib.mcq_vq_pack_bits_f32(_ptr(t), m, k, _ptr(out), _stream()), "mcq_vq_pack_bits_f32")
+    return out
+
+
+def vq_assign_rate_map(x: torch.Tensor, cb: PackedCodebook, bits: torch.Tensor, lam: torch.Tensor, strides=None) -> torch.Tensor:
+    """int64 codes [n, m, h, w] = argmin_k fma(lambda_v, bits_k, distance), one lambda per latent vector (mcq_vq_assign_rate_map_f32) on
+    the PLAIN pack `cb` and `pack_bits`' section.  `lam`: float32 on x's device, finite and >= 0 (`rate_map_levels` makes such buffers).
+    `strides` None: lam is [n] (one lambda per image) or [n, h, w], any view with non-negative strides; else the element strides
+    (image, row, column) into `lam`'s storage from its first element.  lambda 0 gives `vq_assign`'s code."""
+    x = _dev(x, "x")
+    n, c, h, w = x.shape
+    if c != cb.m * cb.d:
+        raise ValueError(f"latent has {c} channels, codebook expects {cb.m}*{cb.d}")
+    lib = _lib.load()
+    if not (torch.is_tensor(bits) and bits.is_cuda and bits.device == x.device and bits.dtype == torch.float32 and bits.is_contiguous()
+            and bits.numel() == lib.mcq_packed_bits_floats(cb.m, cb.k)):
+        raise ValueError(f"vq_assign_rate_map: `bits` must be pack_bits' section for m = {cb.m}, k = {cb.k} on {x.device}")
+    if not (torch.is_tensor(lam) and lam.dtype == torch.float32 and lam.device == x.device):
+        raise ValueError(f"vq_assign_rate_map: `lam` must be a float32 tensor on {x.device}")
+    if strides is None:
+        if tuple(lam.shape) == (n,):
+            strides = (lam.stride(0), 0, 0)
+        elif tuple(lam.shape) == (n, h, w):
+            strides = tuple(lam.stride())
+        else:
+            raise ValueError(f"vq_assign_rate_map: `lam` must be [{n}] or [{n}, {h}, {w}], got {tuple(lam.shape)}")
+    sn, sy, sx = (int(s) for s in strides)
+    room = lam.untyped_storage().nbytes() // 4 - lam.storage_offset()
+    if min(sn, sy, sx) < 0 or (n - 1) * sn + (h - 1) * sy + (w - 1) * sx >= room:
+        raise ValueError(f"vq_assign_rate_map: strides {(sn, sy, sx)} are negative or leave `lam`'s storage")
+    codes = torch.empty((n, cb.m, h, w), dtype=torch.int64, device=x.device)
+    nbytes = lib.mcq_vq_assign_workspace_bytes(n, cb.m, cb.d, h, w, cb.k)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
+    with _guard(x.device):
+        check(lib.mcq_vq_assign_rate_map_f32(_ptr(x), _ptr(cb.packed), _ptr(bits), _ptr(lam), sn, sy, sx, _ptr(codes), n, cb.m, cb.d, h, w,
+                                             cb.k, _ptr(ws), _stream()), "mcq_vq_assign_rate_map_f32")
+    return codes
+
+
+def rate_map_grids(h0: int, w0: int, levels: int):
+    """The code grids below a level-0 grid: [(h_l, w_l)], halving with ceil."""
+    grids = [(int(h0), int(w0))]
+    for _ in range(1, levels):
+        grids.append(((grids[-1][0] + 1) // 2, (grids[-1][1] + 1) // 2))
+    return grids
+
+
+def rate_map_levels(rd_map: torch.Tensor, scales, out=None, error: Optional[torch.Tensor] = None, scales_dev: Optional[torch.Tensor] = None):
+    """Every level's lambda buffer from the caller's map in ONE launch (mcq_rate_map_levels_f32).  `rd_map`: float32 on the device, [n]
+    (one lambda per image: every level is scale_l * map) or [n, h0, w0] on the level-0 code grid (level l = scale_l * the mean of the
+    2 x 2 cells of level l - 1 that exist, taken on the unscaled map, grids halving with ceil); any view with non-negative strides.
+    `scales`: one float per level, finite and >= 0 (`lambda_f32`); `scales_dev`: the same as a float32 device tensor, read by the kernel
+    instead (a captured launch then takes new scales).  A map value that is negative, NaN or infinite counts as 0 and sets its image's
+    word in `error` (int32 [n], on the device, 0 or 1).  Returns (buffers, error); `out` / `error`: the caller's, written in place."""
+    who = "rate_map_levels"
+    if not (torch.is_tensor(rd_map) and rd_map.is_cuda and rd_map.dtype == torch.float32 and rd_map.dim() in (1, 3) and rd_map.numel() > 0):
+        raise ValueError(f"{who}: `rd_map` must be a non-empty float32 device tensor [n] or [n, h0, w0]")
+    scales = [lambda_f32(s) for s in scales]
+    levels = len(scales)
+    lib = _lib.load()
+    if levels == 0 or levels > int(lib.mcq_vq_max_levels()):
+        raise ValueError(f"{who}: 1 .. {int(lib.mcq_vq_max_levels())} levels")
+    if any(int(s) < 0 for s in rd_map.stride()):
+        raise ValueError(f"{who}: negative strides")
+    dev, n = rd_map.device, int(rd_map.shape[0])
+    if rd_map.dim() == 1:
+        h0 = w0 = 0
+        strides = (rd_map.stride(0), 0, 0)
+        shapes = [(n,)] * levels
+    else:
+        h0, w0 = int(rd_map.shape[1]), int(rd_map.shape[2])
+        strides = tuple(rd_map.stride())
+        shapes = [(n, h, w) for h, w in rate_map_grids(h0, w0, levels)]
+    out = _reassign_rows(out, shapes, torch.float32, dev, "out", who)
+    if error is None:
+        error = torch.empty(n, dtype=torch.int32, device=dev)
+    elif not (error.is_cuda and error.device == dev and error.dtype == torch.int32 and error.numel() == n and error.is_contiguous()):
+        raise ValueError(f"{who}: `error` must be {n} contiguous int32 words on {dev}")
+    if scales_dev is not None and not (scales_dev.is_cuda and scales_dev.device == dev and scales_dev.dtype == torch.float32
+                                       and scales_dev.numel() == levels and scales_dev.is_contiguous()):
+        raise ValueError(f"{who}: `scales_dev` must be {levels} contiguous float32 values on {dev}")
+    with _guard(dev):
+        check(lib.mcq_rate_map_levels_f32(_ptr(rd_map), n, h0, w0, int(strides[0]), int(strides[1]), int(strides[2]),
+                                          (ctypes.c_float * levels)(*scales), _ptr(scales_dev), levels,
+                                          (ctypes.c_void_p * levels)(*[t.data_ptr() for t in out]), _ptr(error), _stream()),
+              "mcq_rate_map_levels_f32")
+    return out, error
+
+
+def rate_search_step(bits: torch.Tensor, target: torch.Tensor, lam: torch.Tensor, bracket: torch.Tensor, done: torch.Tensor,
+                     trace_lam: Optional[torch.Tensor], trace_bpp: Optional[torch.Tensor], pixels: float, lambda_max: float, trial: int,
+                     trials: int) -> None:
+    """One launch of the per-image target-rate search after trial `trial` of `trials` (mcq_rate_search_step; the rule is in the header):
+    `bits` double [n, levels] of the trial's codes, `target` double [n]; state `lam` float32 [n], `bracket` float32 [n, 2], `done` int32
+    [n] and the traces float32 / double [trials + 1, n] are updated in place on the device."""
+    n, levels = int(bits.shape[0]), int(bits.shape[1])
+    for t, dt, numel, name in ((bits, torch.float64, n * levels, "bits"), (target, torch.float64, n, "target"), (lam, torch.float32, n, "lam"),
+                               (bracket, torch.float32, 2 * n, "bracket"), (done, torch.int32, n, "done"),
+                               (trace_lam, torch.float32, (trials + 1) * n, "trace_lam"), (trace_bpp, torch.float64, (trials + 1) * n, "trace_bpp")):
+        if t is None and name.startswith("trace"):
+            continue
+        if not (torch.is_tensor(t) and t.is_cuda and t.device == bits.device and t.dtype == dt and t.numel() == numel and t.is_contiguous()):
+            raise ValueError(f"rate_search_step: `{name}` must be {numel} contiguous {dt} values on {bits.device}")
+    with _guard(bits.device):
+        check(_lib.load().mcq_rate_search_step(_ptr(bits), _ptr(target), _ptr(lam), _ptr(bracket), _ptr(done), _ptr(trace_lam), _ptr(trace_bpp),
+                                               n, levels, float(pixels), float(lambda_max), int(trial), int(trials), _stream()),
+              "mcq_rate_search_step")
+
+
 def vq_gather(codes: torch.Tensor, cb: PackedCodebook, dual_silu: bool = False) -> torch.Tensor:
     """fp32 [n, m*d, h, w] = codebook[g, codes] (mcq_vq_gather_f32)."""
     codes = _dev(codes, "codes", torch.int64)
