@@ -220,6 +220,23 @@ int mcq_vq_assign_ws_f32(const float* x, const float* cb_packed, int64_t* codes,
                          int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k,
                          void* workspace, void* stream);
 
+/* Read-only: the launch plan of mcq_vq_assign_ws_f32 (rate = 0) and mcq_vq_assign_rate_map_f32 (rate = 1) for a shape.
+ * out[6] = {instance, Sp, cs_log2, zs, bw_log2, vector_tiles}: the kernel instance (below), the k-steps per codeword tile, log2 of the
+ * waves of a workgroup that slice the codeword tiles of one vector tile, the ranges they are dealt over when a workspace is given
+ * (1 without one; mcq_vq_assign_workspace_bytes is zs * N * m * h * w * 8 for zs > 1, else 0; every (range, slice) takes
+ * per = ceil(tiles / (zs << cs_log2)) tiles in order, and only the ceil(tiles / (per << cs_log2)) <= zs ranges that own a tile are
+ * launched, one workgroup each), log2 of the pixel block's width (blocks
+ * of 32 pixels, 32 >> bw_log2 rows high) and the tiles of two blocks = 64 latent vectors.  Host code only; the plan the entry points
+ * themselves launch by -- today the same for both values of `rate`, which picks the kernel's form, not its instance.  Returns 1, or 0
+ * (out untouched) for a shape the entry points refuse (MCQ_EINVAL / MCQ_ETOOLARGE), a `rate` other than 0 or 1 and a NULL out.
+ * Additive: ABI 18 stays. */
+#define MCQ_VQ_ASSIGN_LOOP       0   /* run-time k-loop: every vector length without an unrolled instance (d = 17..48, 65..240, > 256) */
+#define MCQ_VQ_ASSIGN_SP8        1   /* 8 k-steps unrolled: d = 1..16 */
+#define MCQ_VQ_ASSIGN_SP32       2   /* 32 k-steps unrolled: d = 49..64 */
+#define MCQ_VQ_ASSIGN_SP128      3   /* 128 k-steps unrolled: d = 241..256 with fewer than four codeword tiles */
+#define MCQ_VQ_ASSIGN_SP128_LDS  4   /* the same with the vector tile staged in LDS, always four slices */
+int mcq_vq_assign_plan(int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, int32_t rate, int32_t* out);
+
 /* ---- rate control per image and per region: lambda as an operand of the assignment (csrc/vq.hip, csrc/vq_rate_map.hip) ---- */
 /* Floats of one level's `bits` section, and the section itself from that level's table cdf uint32 [m, k + 1] (device): the layout of
  * the packed codebook's norm section, [m][k/128 + 1][64][4], holding fl32(16 - log2((double)(cdf[g, i + 1] - cdf[g, i]))) for codeword

@@ -528,31 +528,76 @@ int vq_assign_ranges(long long vtiles, int m, int ntile, int cs_log2) {
     while (zs < 16 && waves * zs < 1536 && (ntile >> cs_log2) >= 2 * zs) zs *= 2;
     return zs;
 }
-int vq_assign_plan(int N, int m, int d, int h, int w, int k, int& cs_log2_out) {
-    int bw_log2;
-    block_shape(h, w, bw_log2);
-    const int bw = 1 << bw_log2, bh = 32 >> bw_log2;
-    const long long tb = (long long)N * ((w + bw - 1) / bw) * ((h + bh - 1) / bh);
-    const long long vtiles = (tb + VQ_NB - 1) / VQ_NB;
-    const int ntile = (k + 127) / 128, Sp = vq_sp(d);
+// The kernel deals per_slice = ceil(ntile / (CS zs)) tiles to every (range, slice) in order, so the tiles run out at some slot: range z
+// owns none iff z CS per_slice >= ntile.  That happens wherever CS zs per_slice overshoots ntile by a whole range -- 17..24 tiles over
+// 4 x 4 slots of 2 leave range 3 empty, 33..40 tiles over 8 x 4 leave ranges 5..7, 65..72 over 16 x 4 leave ranges 9..15.  Those workgroups
+// are not launched (as vq_logits_kernel's launcher trims its grid.z): grid.z = ceil(ntile / (CS per_slice)), every launched range's first
+// slice owns a tile, and the fold reads the launched ranges only.  zs stays the divisor, so no wave's walk gets longer.
+int vq_assign_launched_ranges(int ntile, int cs_log2, int zs) {
+    const int cs = 1 << cs_log2;
+    const int per_range = cs * ((ntile + cs * zs - 1) / (cs * zs));
+    return (ntile + per_range - 1) / per_range;
+}
+
+// Everything the assignment launch decides from the shape alone: pure host code, the one copy.  vq_assign_launch launches by it,
+// mcq_vq_assign_workspace_bytes sizes by it and mcq_vq_assign_plan shows it (tests/test_vq_assign_plan.py holds it to literals).
+struct VqAssignPlan {
+    int instance;                 // MCQ_VQ_ASSIGN_*: the <SPC, XLDS> pair of vq_assign_kernel
+    int Sp, ntile;
+    int cs_log2;                  // 1 << cs_log2 waves of a workgroup slice the codeword tiles of one vector tile
+    int zs;                       // ranges the tiles are dealt over, given a workspace: ceil(ntile / (CS zs)) tiles a slice, in order
+    int gz;                       // grid.z: the ranges that own a tile (see vq_assign_launched_ranges), <= zs
+    int bw_log2, nbx, nby, total_blocks;
+    long long vtiles;             // vector tiles of VQ_NB blocks: one wave (or one group of slices) each
+};
+// MCQ_OK, or the status the entry points refuse the shape with
+int vq_assign_plan(int N, int m, int d, int h, int w, int k, VqAssignPlan& pl) {
+    if (N <= 0 || m <= 0 || d <= 0 || h <= 0 || w <= 0 || k <= 0) return MCQ_EINVAL;
+    if ((uint64_t)d * h * w * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
+    block_shape(h, w, pl.bw_log2);
+    const int bw = 1 << pl.bw_log2, bh = 32 >> pl.bw_log2;
+    pl.nbx = (w + bw - 1) / bw;
+    pl.nby = (h + bh - 1) / bh;
+    const long long tb = (long long)N * pl.nbx * pl.nby;
+    if (tb > 0x7fffffffLL) return MCQ_ETOOLARGE;
+    pl.total_blocks = (int)tb;
+    pl.vtiles = (tb + VQ_NB - 1) / VQ_NB;
+    pl.ntile = (k + 127) / 128;
+    pl.Sp = vq_sp(d);
+    // Every wave walks all codeword tiles of its 64 vectors, so the launch has (vector tiles x m) waves whatever k is:
+    // too few for the 2048 wave slots (2 per SIMD) on the small levels, and 1.5 rounds for config #4.  Splitting the
+    // codeword tiles over 2 or 4 waves of a workgroup multiplies the waves and divides their length; pick the split
+    // with the fewest whole rounds of work.
     int cs_log2 = 0;
     double best_cost = 1e30;
-    for (int lg = 0; lg <= 2 && (1 << lg) <= ntile; ++lg) {
-        const long long waves = vtiles * m << lg;
+    for (int lg = 0; lg <= 2 && (1 << lg) <= pl.ntile; ++lg) {
+        const long long waves = pl.vtiles * m << lg;
         const double cost = (double)((waves + 2047) / 2048) / (double)(1 << lg);
         if (cost < best_cost - 1e-12) { best_cost = cost; cs_log2 = lg; }
     }
-    if (Sp == 128 && ntile >= 4) cs_log2 = 2;          // the LDS-staged mode: four slices share one vector tile
-    cs_log2_out = cs_log2;
-    return vq_assign_ranges(vtiles, m, ntile, cs_log2);
+    if (pl.Sp == 128 && pl.ntile >= 4) cs_log2 = 2;          // the LDS-staged mode: four slices share one vector tile
+    pl.cs_log2 = cs_log2;
+    pl.zs = vq_assign_ranges(pl.vtiles, m, pl.ntile, cs_log2);
+    pl.gz = vq_assign_launched_ranges(pl.ntile, cs_log2, pl.zs);
+    pl.instance = pl.Sp == 32 ? MCQ_VQ_ASSIGN_SP32                                   // d = 49 .. 64
+                : pl.Sp == 8 ? MCQ_VQ_ASSIGN_SP8                                     // d = 16 (model No. 12), d = 1 .. 15
+                : pl.Sp == 128 ? (cs_log2 == 2 ? MCQ_VQ_ASSIGN_SP128_LDS : MCQ_VQ_ASSIGN_SP128)     // d = 241 .. 256
+                : MCQ_VQ_ASSIGN_LOOP;
+    return MCQ_OK;
 }
 }  // namespace
 
+extern "C" int mcq_vq_assign_plan(int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, int32_t rate, int32_t* out) {
+    VqAssignPlan pl;
+    if (!out || (rate != 0 && rate != 1) || vq_assign_plan(N, m, d, h, w, k, pl) != MCQ_OK) return 0;
+    out[0] = pl.instance; out[1] = pl.Sp; out[2] = pl.cs_log2; out[3] = pl.zs; out[4] = pl.bw_log2; out[5] = (int32_t)pl.vtiles;
+    return 1;
+}
+
 extern "C" size_t mcq_vq_assign_workspace_bytes(int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k) {
-    if (N <= 0 || m <= 0 || d <= 0 || h <= 0 || w <= 0 || k <= 0) return 0;
-    int cs;
-    const int zs = vq_assign_plan(N, m, d, h, w, k, cs);
-    return zs > 1 ? (size_t)zs * N * m * h * w * 8u : 0;
+    VqAssignPlan pl;
+    if (vq_assign_plan(N, m, d, h, w, k, pl) != MCQ_OK) return 0;
+    return pl.zs > 1 ? (size_t)pl.zs * N * m * h * w * 8u : 0;
 }
 
 extern "C" int mcq_vq_assign_f32(const float* x, const float* cb_packed, int64_t* codes, int32_t N, int32_t m, int32_t d,
@@ -561,55 +606,50 @@ extern "C" int mcq_vq_assign_f32(const float* x, const float* cb_packed, int64_t
 }
 
 namespace {
+// one instance of the plan's table, with or without the rate operand
+template <bool RATE>
+void vq_assign_run(int instance, dim3 grid, hipStream_t s, const VqK& p, const VqRateArg<RATE>& rt) {
+    switch (instance) {
+    case MCQ_VQ_ASSIGN_SP32: hipLaunchKernelGGL((vq_assign_kernel<32, false, RATE>), grid, dim3(256), 0, s, p, rt); break;
+    case MCQ_VQ_ASSIGN_SP8: hipLaunchKernelGGL((vq_assign_kernel<8, false, RATE>), grid, dim3(256), 0, s, p, rt); break;
+    case MCQ_VQ_ASSIGN_SP128_LDS: hipLaunchKernelGGL((vq_assign_kernel<128, true, RATE>), grid, dim3(256), 0, s, p, rt); break;
+    case MCQ_VQ_ASSIGN_SP128: hipLaunchKernelGGL((vq_assign_kernel<128, false, RATE>), grid, dim3(256), 0, s, p, rt); break;
+    default: hipLaunchKernelGGL((vq_assign_kernel<0, false, RATE>), grid, dim3(256), 0, s, p, rt); break;
+    }
+}
+
 // the plain launch (rate == nullptr) and the per-vector-lambda one share the plan, the workspace and the fold
 int vq_assign_launch(const float* x, const float* cb_packed, const VqRate* rate, int64_t* codes, int32_t N, int32_t m, int32_t d,
                      int32_t h, int32_t w, int32_t k, void* workspace, void* stream) {
-    if ((uint64_t)d * h * w * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
+    VqAssignPlan pl;
+    const int status = vq_assign_plan(N, m, d, h, w, k, pl);
+    if (status != MCQ_OK) return status;
     VqK p;
     p.x = x; p.codes = codes; p.N = N; p.m = m; p.d = d; p.h = h; p.w = w; p.k = k;
-    p.ntile = (k + 127) / 128;
-    p.Sp = vq_sp(d);
+    p.ntile = pl.ntile;
+    p.Sp = pl.Sp;
     const size_t cb_alloc = ((size_t)m * p.ntile * p.Sp + VQ_PF) * 256;
     p.cbp = cb_packed;
     p.c2p = cb_packed + cb_alloc;
-    block_shape(h, w, p.bw_log2);
-    const int bw = 1 << p.bw_log2, bh = 32 >> p.bw_log2;
-    p.nbx = (w + bw - 1) / bw;
-    p.nby = (h + bh - 1) / bh;
-    const long long tb = (long long)N * p.nbx * p.nby;
-    if (tb > 0x7fffffffLL) return MCQ_ETOOLARGE;
-    p.total_blocks = (int)tb;
-    // Every wave walks all codeword tiles of its 64 vectors, so the launch has (vector tiles x m) waves whatever k is:
-    // too few for the 2048 wave slots (2 per SIMD) on the small levels, and 1.5 rounds for config #4.  Splitting the
-    // codeword tiles over 2 or 4 waves of a workgroup multiplies the waves and divides their length; pick the split
-    // with the fewest whole rounds of work.
-    const long long vtiles = (tb + VQ_NB - 1) / VQ_NB;
-    int cs_log2 = 0;
-    const int zs_plan = vq_assign_plan(N, m, d, h, w, k, cs_log2);
-    p.cs_log2 = cs_log2;
-    p.zs = workspace ? zs_plan : 1;                          // (without a workspace: one workgroup per vector tile, as before)
+    p.bw_log2 = pl.bw_log2; p.nbx = pl.nbx; p.nby = pl.nby; p.total_blocks = pl.total_blocks;
+    p.cs_log2 = pl.cs_log2;
+    p.zs = workspace ? pl.zs : 1;                            // (without a workspace: one workgroup per vector tile, as before)
     const size_t nvec = (size_t)N * m * h * w;
     p.ws_best = static_cast<float*>(workspace);
     p.ws_idx = reinterpret_cast<int*>(p.ws_best + (size_t)p.zs * nvec);
-    const int per_wg = 4 >> cs_log2;
-    const unsigned gx = (unsigned)((vtiles + per_wg - 1) / per_wg);
-    const dim3 grid(gx, (unsigned)m, (unsigned)p.zs);
+    const int per_wg = 4 >> pl.cs_log2;
+    const unsigned gx = (unsigned)((pl.vtiles + per_wg - 1) / per_wg);
+    const int gz = workspace ? pl.gz : 1;                    // the ranges that own a tile; the kernel deals by p.zs, the fold reads gz
+    const dim3 grid(gx, (unsigned)m, (unsigned)gz);
     if (rate) {
         VqRateArg<true> rt;
         static_cast<VqRate&>(rt) = *rate;
-        if (p.Sp == 32) hipLaunchKernelGGL((vq_assign_kernel<32, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
-        else if (p.Sp == 8) hipLaunchKernelGGL((vq_assign_kernel<8, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
-        else if (p.Sp == 128 && cs_log2 == 2) hipLaunchKernelGGL((vq_assign_kernel<128, true, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
-        else if (p.Sp == 128) hipLaunchKernelGGL((vq_assign_kernel<128, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
-        else hipLaunchKernelGGL((vq_assign_kernel<0, false, true>), grid, dim3(256), 0, (hipStream_t)stream, p, rt);
+        vq_assign_run<true>(pl.instance, grid, (hipStream_t)stream, p, rt);
+    } else {
+        vq_assign_run<false>(pl.instance, grid, (hipStream_t)stream, p, VqRateArg<false>{});
     }
-    else if (p.Sp == 32) hipLaunchKernelGGL((vq_assign_kernel<32, false>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});          // d = 64
-    else if (p.Sp == 8) hipLaunchKernelGGL((vq_assign_kernel<8, false>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});      // d = 16 (model No. 12), d = 8 ... 15
-    else if (p.Sp == 128 && cs_log2 == 2) hipLaunchKernelGGL((vq_assign_kernel<128, true>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});   // d = 256
-    else if (p.Sp == 128) hipLaunchKernelGGL((vq_assign_kernel<128, false>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});
-    else hipLaunchKernelGGL((vq_assign_kernel<0, false>), grid, dim3(256), 0, (hipStream_t)stream, p, VqRateArg<false>{});
     if (p.zs > 1)
-        hipLaunchKernelGGL(vq_fold_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p.ws_best, p.ws_idx, p.zs,
+        hipLaunchKernelGGL(vq_fold_kernel, dim3((unsigned)((nvec + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p.ws_best, p.ws_idx, gz,
                            nvec, codes);
     return mcq_check_launch();
 }
