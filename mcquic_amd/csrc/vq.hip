@@ -336,77 +336,40 @@ __global__ void vq_fold_kernel(const float* __restrict__ ws_best, const int* __r
     codes[v] = (int64_t)idx;
 }
 
-// codebook [m, k, d] -> cbp [m][ntile][Sp][64][4] (+ zero tail) and c2p [m][ntile + 1][64][4]
-__global__ void vq_pack_kernel(const float* __restrict__ cb, int m, int k, int d, int Sp, int ntile,
-                               float* __restrict__ cbp, size_t cb_total, size_t cb_alloc) {
+// codebook [m, k, d] -> cbp [m][ntile][Sp][64][4] (+ zero tail) and c2p [m][ntile + 1][64][4] (VqPackLayout, vq_common.h)
+__global__ void vq_pack_kernel(const float* __restrict__ cb, int k, int d, VqPackLayout L, float* __restrict__ cbp) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= cb_alloc) return;
+    if (i >= L.cb_alloc) return;
     float v = 0.0f;
-    if (i < cb_total) {
-        const int q = (int)(i & 3);
-        const int lane = (int)((i >> 2) & 63);
-        size_t rest = i >> 8;
-        const int s = (int)(rest % Sp); rest /= Sp;
-        const int tile = (int)(rest % ntile);
-        const int g = (int)(rest / ntile);
-        const int word = tile * 128 + 32 * q + (lane & 31);
-        const int c = 2 * s + (lane >> 5);
-        if (word < k && c < d) v = cb[((size_t)g * k + word) * d + c];
+    if (i < L.cb_total) {
+        const VqSlot s = vq_operand_slot(i, L.ntile, L.Sp);
+        const int c = 2 * s.step + s.upper;
+        if (s.word < k && c < d) v = cb[((size_t)s.g * k + s.word) * d + c];
     }
     cbp[i] = v;
 }
 
-__global__ void vq_c2_kernel(const float* __restrict__ cb, int m, int k, int d, int ntile, float* __restrict__ c2p,
-                             size_t total) {
+// The norm section.  cdf == nullptr: |c_k|^2.  Else (mcq_vq_pack_codebook_rate_f32) with a per-codeword rate penalty folded in: the same
+// |c|^2 loop, then c2' = fl32(c2 + fl32(lambda * bits_k)), bits_k = vq_table_bits of the group's 16-bit table [k + 1].  vq_assign_kernel
+// reads this section as |c_k|^2, so its (x2 + c2') - 2 inter is distance + lambda * bits.  lambda = 0 adds +0 to a non-negative sum: the
+// bits of the plain section.  Padded codewords and slots of width 0 (no valid table has one) are +inf: they can never win the argmin.
+__global__ void vq_c2_kernel(const float* __restrict__ cb, const uint32_t* __restrict__ cdf, float lambda, int k, int d, VqPackLayout L,
+                             float* __restrict__ c2p) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int q = (int)(i & 3);
-    const int lane = (int)((i >> 2) & 63);
-    size_t rest = i >> 8;
-    const int tile = (int)(rest % (ntile + 1));
-    const int g = (int)(rest / (ntile + 1));
-    const int word = tile * 128 + 32 * q + (lane & 31);
+    if (i >= L.c2_total) return;
+    const VqSlot sl = vq_norm_slot(i, L.ntile);
     float v = 0.0f;
-    if ((lane >> 5) == 0) {
-        if (tile < ntile && word < k) {
-            const float* row = cb + ((size_t)g * k + word) * d;
+    if (!sl.upper) {
+        v = INFINITY;
+        if (sl.tile < L.ntile && sl.word < k) {
+            const float* row = cb + ((size_t)sl.g * k + sl.word) * d;
             float s = 0.0f;
             for (int c = 0; c < d; ++c) s = s + row[c] * row[c];
             v = s;
-        } else {
-            v = INFINITY;   // padded codewords can never win the argmin
-        }
-    }
-    c2p[i] = v;
-}
-
-// vq_c2_kernel's norm section with a per-codeword rate penalty folded in (mcq_vq_pack_codebook_rate_f32): the same indexing and the
-// same |c|^2 loop, then c2' = fl32(c2 + fl32(lambda * fl32(16 - log2((double)width)))), width = cdf[word + 1] - cdf[word] of the group's
-// 16-bit table [k + 1].  vq_assign_kernel reads this section as |c_k|^2, so its (x2 + c2') - 2 inter is distance + lambda * bits.
-// lambda = 0 adds +0 to a non-negative sum: the bits of vq_c2_kernel.  A slot of width 0 (no valid table has one) can never win.
-__global__ void vq_c2_rate_kernel(const float* __restrict__ cb, const uint32_t* __restrict__ cdf, float lambda, int m, int k, int d,
-                                  int ntile, float* __restrict__ c2p, size_t total) {
-    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int q = (int)(i & 3);
-    const int lane = (int)((i >> 2) & 63);
-    size_t rest = i >> 8;
-    const int tile = (int)(rest % (ntile + 1));
-    const int g = (int)(rest / (ntile + 1));
-    const int word = tile * 128 + 32 * q + (lane & 31);
-    float v = 0.0f;
-    if ((lane >> 5) == 0) {
-        v = INFINITY;   // padded codewords and empty slots can never win the argmin
-        if (tile < ntile && word < k) {
-            const float* row = cb + ((size_t)g * k + word) * d;
-            float s = 0.0f;
-            for (int c = 0; c < d; ++c) s = s + row[c] * row[c];
-            const uint32_t* t = cdf + (size_t)g * (k + 1) + word;
-            const uint32_t lo = t[0], up = t[1];
-            if (up > lo) {
-                const float bits = (float)(16.0 - log2((double)(up - lo)));
+            if (cdf) {
+                const float bits = vq_table_bits(cdf, sl.g, k, sl.word);
                 const float pen = lambda * bits;
-                v = s + pen;
+                v = bits < INFINITY ? s + pen : INFINITY;
             }
         }
     }
@@ -481,41 +444,31 @@ __global__ void detransform_kernel(const float* __restrict__ x, uint8_t* __restr
 
 extern "C" size_t mcq_packed_codebook_floats(int32_t m, int32_t k, int32_t d) {
     if (m <= 0 || k <= 0 || d <= 0) return 0;
-    const size_t ntile = (size_t)(k + 127) / 128;
-    const size_t cb = ((size_t)m * ntile * vq_sp(d) + VQ_PF) * 256;   // operand stream + prefetch tail
-    const size_t c2 = (size_t)m * (ntile + 1) * 256;                  // norms (+1 spare tile per group)
-    return cb + c2;
+    const VqPackLayout L = vq_pack_layout(m, k, d);
+    return L.cb_alloc + L.c2_total;
+}
+
+// both pack entry points: the operand stream, then the norm section (cdf == nullptr: the plain one)
+static int vq_pack_launch(const float* codebook, const uint32_t* cdf, float lambda, int m, int k, int d, float* cb_packed, void* stream) {
+    const VqPackLayout L = vq_pack_layout(m, k, d);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(vq_pack_kernel, dim3((unsigned)((L.cb_alloc + 255) / 256)), dim3(256), 0, s, codebook, k, d, L, cb_packed);
+    hipLaunchKernelGGL(vq_c2_kernel, dim3((unsigned)((L.c2_total + 255) / 256)), dim3(256), 0, s, codebook, cdf, lambda, k, d, L,
+                       cb_packed + L.cb_alloc);
+    return mcq_check_launch();
 }
 
 extern "C" int mcq_vq_pack_codebook_f32(const float* codebook, int32_t m, int32_t k, int32_t d, float* cb_packed,
                                         void* stream) {
     if (!codebook || !cb_packed || m <= 0 || k <= 0 || d <= 0) return MCQ_EINVAL;
-    const int ntile = (k + 127) / 128, Sp = vq_sp(d);
-    const size_t cb_total = (size_t)m * ntile * Sp * 256;
-    const size_t cb_alloc = cb_total + (size_t)VQ_PF * 256;
-    const size_t c2_total = (size_t)m * (ntile + 1) * 256;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(vq_pack_kernel, dim3((unsigned)((cb_alloc + 255) / 256)), dim3(256), 0, s, codebook, m, k, d, Sp,
-                       ntile, cb_packed, cb_total, cb_alloc);
-    hipLaunchKernelGGL(vq_c2_kernel, dim3((unsigned)((c2_total + 255) / 256)), dim3(256), 0, s, codebook, m, k, d, ntile,
-                       cb_packed + cb_alloc, c2_total);
-    return mcq_check_launch();
+    return vq_pack_launch(codebook, nullptr, 0.0f, m, k, d, cb_packed, stream);
 }
 
 extern "C" int mcq_vq_pack_codebook_rate_f32(const float* codebook, const uint32_t* cdf, float lambda, int32_t m, int32_t k,
                                              int32_t d, float* cb_packed, void* stream) {
     if (!codebook || !cdf || !cb_packed || m <= 0 || k <= 0 || d <= 0) return MCQ_EINVAL;
     if (!(lambda >= 0.0f) || isinf(lambda)) return MCQ_EINVAL;      // (negative, NaN, inf)
-    const int ntile = (k + 127) / 128, Sp = vq_sp(d);
-    const size_t cb_total = (size_t)m * ntile * Sp * 256;
-    const size_t cb_alloc = cb_total + (size_t)VQ_PF * 256;
-    const size_t c2_total = (size_t)m * (ntile + 1) * 256;
-    hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(vq_pack_kernel, dim3((unsigned)((cb_alloc + 255) / 256)), dim3(256), 0, s, codebook, m, k, d, Sp,
-                       ntile, cb_packed, cb_total, cb_alloc);
-    hipLaunchKernelGGL(vq_c2_rate_kernel, dim3((unsigned)((c2_total + 255) / 256)), dim3(256), 0, s, codebook, cdf, lambda, m, k, d,
-                       ntile, cb_packed + cb_alloc, c2_total);
-    return mcq_check_launch();
+    return vq_pack_launch(codebook, cdf, lambda, m, k, d, cb_packed, stream);
 }
 
 namespace {
@@ -543,45 +496,36 @@ int vq_assign_launched_ranges(int ntile, int cs_log2, int zs) {
 // mcq_vq_assign_workspace_bytes sizes by it and mcq_vq_assign_plan shows it (tests/test_vq_assign_plan.py holds it to literals).
 struct VqAssignPlan {
     int instance;                 // MCQ_VQ_ASSIGN_*: the <SPC, XLDS> pair of vq_assign_kernel
-    int Sp, ntile;
-    int cs_log2;                  // 1 << cs_log2 waves of a workgroup slice the codeword tiles of one vector tile
-    int zs;                       // ranges the tiles are dealt over, given a workspace: ceil(ntile / (CS zs)) tiles a slice, in order
+    VqK p;                        // the kernel's argument with its geometry (vq_geometry), cs_log2 and zs filled in; zs = the ranges the tiles
+                                  // are dealt over, given a workspace: ceil(ntile / (CS zs)) tiles a slice, in order
     int gz;                       // grid.z: the ranges that own a tile (see vq_assign_launched_ranges), <= zs
-    int bw_log2, nbx, nby, total_blocks;
     long long vtiles;             // vector tiles of VQ_NB blocks: one wave (or one group of slices) each
 };
 // MCQ_OK, or the status the entry points refuse the shape with
 int vq_assign_plan(int N, int m, int d, int h, int w, int k, VqAssignPlan& pl) {
     if (N <= 0 || m <= 0 || d <= 0 || h <= 0 || w <= 0 || k <= 0) return MCQ_EINVAL;
     if ((uint64_t)d * h * w * 4ull >= 0x80000000ull) return MCQ_ETOOLARGE;
-    block_shape(h, w, pl.bw_log2);
-    const int bw = 1 << pl.bw_log2, bh = 32 >> pl.bw_log2;
-    pl.nbx = (w + bw - 1) / bw;
-    pl.nby = (h + bh - 1) / bh;
-    const long long tb = (long long)N * pl.nbx * pl.nby;
-    if (tb > 0x7fffffffLL) return MCQ_ETOOLARGE;
-    pl.total_blocks = (int)tb;
-    pl.vtiles = (tb + VQ_NB - 1) / VQ_NB;
-    pl.ntile = (k + 127) / 128;
-    pl.Sp = vq_sp(d);
+    VqK& p = pl.p;
+    if (!vq_geometry(p, N, m, d, h, w, k)) return MCQ_ETOOLARGE;
+    pl.vtiles = ((long long)p.total_blocks + VQ_NB - 1) / VQ_NB;
     // Every wave walks all codeword tiles of its 64 vectors, so the launch has (vector tiles x m) waves whatever k is:
     // too few for the 2048 wave slots (2 per SIMD) on the small levels, and 1.5 rounds for config #4.  Splitting the
     // codeword tiles over 2 or 4 waves of a workgroup multiplies the waves and divides their length; pick the split
     // with the fewest whole rounds of work.
     int cs_log2 = 0;
     double best_cost = 1e30;
-    for (int lg = 0; lg <= 2 && (1 << lg) <= pl.ntile; ++lg) {
+    for (int lg = 0; lg <= 2 && (1 << lg) <= p.ntile; ++lg) {
         const long long waves = pl.vtiles * m << lg;
         const double cost = (double)((waves + 2047) / 2048) / (double)(1 << lg);
         if (cost < best_cost - 1e-12) { best_cost = cost; cs_log2 = lg; }
     }
-    if (pl.Sp == 128 && pl.ntile >= 4) cs_log2 = 2;          // the LDS-staged mode: four slices share one vector tile
-    pl.cs_log2 = cs_log2;
-    pl.zs = vq_assign_ranges(pl.vtiles, m, pl.ntile, cs_log2);
-    pl.gz = vq_assign_launched_ranges(pl.ntile, cs_log2, pl.zs);
-    pl.instance = pl.Sp == 32 ? MCQ_VQ_ASSIGN_SP32                                   // d = 49 .. 64
-                : pl.Sp == 8 ? MCQ_VQ_ASSIGN_SP8                                     // d = 16 (model No. 12), d = 1 .. 15
-                : pl.Sp == 128 ? (cs_log2 == 2 ? MCQ_VQ_ASSIGN_SP128_LDS : MCQ_VQ_ASSIGN_SP128)     // d = 241 .. 256
+    if (p.Sp == 128 && p.ntile >= 4) cs_log2 = 2;            // the LDS-staged mode: four slices share one vector tile
+    p.cs_log2 = cs_log2;
+    p.zs = vq_assign_ranges(pl.vtiles, m, p.ntile, cs_log2);
+    pl.gz = vq_assign_launched_ranges(p.ntile, cs_log2, p.zs);
+    pl.instance = p.Sp == 32 ? MCQ_VQ_ASSIGN_SP32                                    // d = 49 .. 64
+                : p.Sp == 8 ? MCQ_VQ_ASSIGN_SP8                                      // d = 16 (model No. 12), d = 1 .. 15
+                : p.Sp == 128 ? (cs_log2 == 2 ? MCQ_VQ_ASSIGN_SP128_LDS : MCQ_VQ_ASSIGN_SP128)      // d = 241 .. 256
                 : MCQ_VQ_ASSIGN_LOOP;
     return MCQ_OK;
 }
@@ -590,14 +534,14 @@ int vq_assign_plan(int N, int m, int d, int h, int w, int k, VqAssignPlan& pl) {
 extern "C" int mcq_vq_assign_plan(int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k, int32_t rate, int32_t* out) {
     VqAssignPlan pl;
     if (!out || (rate != 0 && rate != 1) || vq_assign_plan(N, m, d, h, w, k, pl) != MCQ_OK) return 0;
-    out[0] = pl.instance; out[1] = pl.Sp; out[2] = pl.cs_log2; out[3] = pl.zs; out[4] = pl.bw_log2; out[5] = (int32_t)pl.vtiles;
+    out[0] = pl.instance; out[1] = pl.p.Sp; out[2] = pl.p.cs_log2; out[3] = pl.p.zs; out[4] = pl.p.bw_log2; out[5] = (int32_t)pl.vtiles;
     return 1;
 }
 
 extern "C" size_t mcq_vq_assign_workspace_bytes(int32_t N, int32_t m, int32_t d, int32_t h, int32_t w, int32_t k) {
     VqAssignPlan pl;
     if (vq_assign_plan(N, m, d, h, w, k, pl) != MCQ_OK) return 0;
-    return pl.zs > 1 ? (size_t)pl.zs * N * m * h * w * 8u : 0;
+    return pl.p.zs > 1 ? (size_t)pl.p.zs * N * m * h * w * 8u : 0;
 }
 
 extern "C" int mcq_vq_assign_f32(const float* x, const float* cb_packed, int64_t* codes, int32_t N, int32_t m, int32_t d,
@@ -624,20 +568,14 @@ int vq_assign_launch(const float* x, const float* cb_packed, const VqRate* rate,
     VqAssignPlan pl;
     const int status = vq_assign_plan(N, m, d, h, w, k, pl);
     if (status != MCQ_OK) return status;
-    VqK p;
-    p.x = x; p.codes = codes; p.N = N; p.m = m; p.d = d; p.h = h; p.w = w; p.k = k;
-    p.ntile = pl.ntile;
-    p.Sp = pl.Sp;
-    const size_t cb_alloc = ((size_t)m * p.ntile * p.Sp + VQ_PF) * 256;
-    p.cbp = cb_packed;
-    p.c2p = cb_packed + cb_alloc;
-    p.bw_log2 = pl.bw_log2; p.nbx = pl.nbx; p.nby = pl.nby; p.total_blocks = pl.total_blocks;
-    p.cs_log2 = pl.cs_log2;
-    p.zs = workspace ? pl.zs : 1;                            // (without a workspace: one workgroup per vector tile, as before)
+    VqK& p = pl.p;
+    vq_operands(p, x, cb_packed);
+    p.codes = codes;
+    if (!workspace) p.zs = 1;                                // (without a workspace: one workgroup per vector tile, as before)
     const size_t nvec = (size_t)N * m * h * w;
     p.ws_best = static_cast<float*>(workspace);
     p.ws_idx = reinterpret_cast<int*>(p.ws_best + (size_t)p.zs * nvec);
-    const int per_wg = 4 >> pl.cs_log2;
+    const int per_wg = 4 >> p.cs_log2;
     const unsigned gx = (unsigned)((pl.vtiles + per_wg - 1) / per_wg);
     const int gz = workspace ? pl.gz : 1;                    // the ranges that own a tile; the kernel deals by p.zs, the fold reads gz
     const dim3 grid(gx, (unsigned)m, (unsigned)gz);

@@ -1,5 +1,6 @@
 // Shared host/device definitions of the vector-quantizer kernels (vq.hip, vq_train.hip).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 
 namespace {
@@ -34,15 +35,49 @@ inline void block_shape(int Ho, int Wo, int& lg_out) {
 
 inline int vq_sp(int d) { return (((d + 1) / 2) + VQ_PF - 1) / VQ_PF * VQ_PF; }
 
+// The packed codebook of (m, k, d), in floats -- the one copy of its sizes: the operand stream [m][ntile][Sp][64][4] (cb_total) with its
+// prefetch tail (cb_alloc), then the norm section [m][ntile + 1][64][4] (c2_total; one spare tile per group).  A bits section
+// (vq_rate_map.hip) has the norm section's layout and size, whatever d is.
+struct VqPackLayout { int ntile, Sp; size_t cb_total, cb_alloc, c2_total; };
+inline VqPackLayout vq_pack_layout(int m, int k, int d) {
+    VqPackLayout L;
+    L.ntile = (k + 127) / 128;
+    L.Sp = vq_sp(d);
+    L.cb_total = (size_t)m * L.ntile * L.Sp * 256;
+    L.cb_alloc = L.cb_total + (size_t)VQ_PF * 256;
+    L.c2_total = (size_t)m * (L.ntile + 1) * 256;
+    return L;
+}
 
-// fill the geometry / operand-stream fields common to every VQ launch; returns false when the shape is too large
-inline bool vq_setup(VqK& p, const float* x, const float* cb_packed, int N, int m, int d, int h, int w, int k) {
-    p.x = x; p.N = N; p.m = m; p.d = d; p.h = h; p.w = w; p.k = k;
-    p.ntile = (k + 127) / 128;
-    p.Sp = vq_sp(d);
-    const size_t cb_alloc = ((size_t)m * p.ntile * p.Sp + VQ_PF) * 256;
-    p.cbp = cb_packed;
-    p.c2p = cb_packed + cb_alloc;
+// Float i of a section [g][tiles][steps][64 lanes][4]: lane (l, q) of a tile holds codeword tile * 128 + 32 q + (l & 31); the upper
+// half-wave (l >= 32) holds the odd channel of a k-step in the operand stream and nothing (0) in the norm and bits sections.
+struct VqSlot { int g, tile, step, word, upper; };
+__host__ __device__ inline VqSlot vq_slot(size_t i, int tiles, int steps) {
+    const int q = (int)(i & 3), lane = (int)((i >> 2) & 63);
+    size_t rest = i >> 8;
+    VqSlot s;
+    s.step = (int)(rest % steps); rest /= steps;
+    s.tile = (int)(rest % tiles);
+    s.g = (int)(rest / tiles);
+    s.word = s.tile * 128 + 32 * q + (lane & 31);
+    s.upper = lane >> 5;
+    return s;
+}
+__host__ __device__ inline VqSlot vq_norm_slot(size_t i, int ntile) { return vq_slot(i, ntile + 1, 1); }
+__host__ __device__ inline VqSlot vq_operand_slot(size_t i, int ntile, int Sp) { return vq_slot(i, ntile, Sp); }
+
+// what group g's 16-bit table cdf [m, k + 1] charges for codeword `word`: fl32(16 - log2((double)width)), +inf for a slot of width 0
+__device__ inline float vq_table_bits(const uint32_t* cdf, int g, int k, int word) {
+    const uint32_t* t = cdf + (size_t)g * (k + 1) + word;
+    const uint32_t lo = t[0], up = t[1];
+    return up > lo ? (float)(16.0 - log2((double)(up - lo))) : INFINITY;
+}
+
+// the geometry fields common to every VQ launch; returns false when the shape is too large
+inline bool vq_geometry(VqK& p, int N, int m, int d, int h, int w, int k) {
+    p.N = N; p.m = m; p.d = d; p.h = h; p.w = w; p.k = k;
+    const VqPackLayout L = vq_pack_layout(m, k, d);
+    p.ntile = L.ntile; p.Sp = L.Sp;
     block_shape(h, w, p.bw_log2);
     const int bw = 1 << p.bw_log2, bh = 32 >> p.bw_log2;
     p.nbx = (w + bw - 1) / bw;
@@ -51,6 +86,20 @@ inline bool vq_setup(VqK& p, const float* x, const float* cb_packed, int N, int 
     if (tb > 0x7fffffffLL) return false;
     p.total_blocks = (int)tb;
     return true;
+}
+
+// the operand-stream fields, for the shape vq_geometry stored
+inline void vq_operands(VqK& p, const float* x, const float* cb_packed) {
+    p.x = x;
+    p.cbp = cb_packed;
+    p.c2p = cb_packed + vq_pack_layout(p.m, p.k, p.d).cb_alloc;
+}
+
+// both; returns false when the shape is too large
+inline bool vq_setup(VqK& p, const float* x, const float* cb_packed, int N, int m, int d, int h, int w, int k) {
+    const bool ok = vq_geometry(p, N, m, d, h, w, k);
+    vq_operands(p, x, cb_packed);
+    return ok;
 }
 
 }  // namespace

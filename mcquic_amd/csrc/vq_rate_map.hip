@@ -2,8 +2,8 @@
 // host read.
 //
 //   vq_pack_bits_kernel    one level's 16-bit table uint32 [m, k + 1] -> the `bits` section [m][ntile + 1][64][4] in the layout of the
-//                          packed codebook's norms: fl32(16 - log2((double)width)) for a codeword < k, 0 for padded codewords and the
-//                          upper half-wave (the lanes whose MFMA operand is multiplied by 0), +inf for a slot of width 0.
+//                          packed codebook's norms (vq_norm_slot, vq_common.h): vq_table_bits for a codeword < k (+inf for a slot of
+//                          width 0), 0 for padded codewords and the upper half-wave (the lanes whose MFMA operand is multiplied by 0).
 //   rate_map_levels_kernel every level's lambda buffer from the caller's map in ONE launch, one workgroup per image.  Level 0 is the
 //                          map with every negative, NaN or infinite value replaced by 0 (the image's error word says so); level l,
 //                          cell (y, x), is the mean of the level-(l - 1) cells (2y .. 2y + 1, 2x .. 2x + 1) that exist -- summed in
@@ -13,27 +13,17 @@
 //   rate_search_kernel     one thread per image: the bracket update of Compressor.encode_to_rate(per_image=True) after a trial, state
 //                          and trace on the device (see mcq_rate_search_step in the header for the rule).
 #include "mcq_common.h"
+#include "vq_common.h"
 #include "../../include/mcquic_hip.h"
 #include <math.h>
 
 namespace {
 
-__global__ void vq_pack_bits_kernel(const uint32_t* __restrict__ cdf, int m, int k, int ntile, float* __restrict__ out, size_t total) {
+__global__ void vq_pack_bits_kernel(const uint32_t* __restrict__ cdf, int k, int ntile, float* __restrict__ out, size_t total) {
     size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= total) return;
-    const int q = (int)(i & 3);
-    const int lane = (int)((i >> 2) & 63);
-    size_t rest = i >> 8;
-    const int tile = (int)(rest % (ntile + 1));
-    const int g = (int)(rest / (ntile + 1));
-    const int word = tile * 128 + 32 * q + (lane & 31);
-    float v = 0.0f;
-    if ((lane >> 5) == 0 && tile < ntile && word < k) {
-        const uint32_t* t = cdf + (size_t)g * (k + 1) + word;
-        const uint32_t lo = t[0], up = t[1];
-        v = up > lo ? (float)(16.0 - log2((double)(up - lo))) : INFINITY;
-    }
-    out[i] = v;
+    const VqSlot s = vq_norm_slot(i, ntile);
+    out[i] = !s.upper && s.tile < ntile && s.word < k ? vq_table_bits(cdf, s.g, k, s.word) : 0.0f;
 }
 
 struct RateMapK {
@@ -162,15 +152,14 @@ __global__ void rate_search_kernel(RateSearchK p) {
 
 extern "C" size_t mcq_packed_bits_floats(int32_t m, int32_t k) {
     if (m <= 0 || k <= 0) return 0;
-    return (size_t)m * ((size_t)(k + 127) / 128 + 1) * 256;
+    return vq_pack_layout(m, k, 1).c2_total;
 }
 
 extern "C" int mcq_vq_pack_bits_f32(const uint32_t* cdf, int32_t m, int32_t k, float* bits_packed, void* stream) {
     if (!cdf || !bits_packed || m <= 0 || k <= 0) return MCQ_EINVAL;
-    const int ntile = (k + 127) / 128;
-    const size_t total = (size_t)m * (ntile + 1) * 256;
-    hipLaunchKernelGGL(vq_pack_bits_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cdf, m, k, ntile,
-                       bits_packed, total);
+    const VqPackLayout L = vq_pack_layout(m, k, 1);          // (the section is the norms': the same for every d)
+    hipLaunchKernelGGL(vq_pack_bits_kernel, dim3((unsigned)((L.c2_total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, cdf, k, L.ntile,
+                       bits_packed, L.c2_total);
     return mcq_check_launch();
 }
 

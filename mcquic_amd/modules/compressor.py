@@ -266,25 +266,44 @@ class BaseCompressor(nn.Module):
         device tensor; `rd_lambda` is then the per-level scale (`UMGMQuantizer.encode`).  The map is an operand: under `enableGraphs`
         one capture per image shape and map form serves every map and every scale; inside a caller's capture it works once a call
         outside it has made the tables' bits sections."""
-        if rd_map is not None:
-            return self._encodeRateMap(x, self._quantizer.rateLambdas(1.0 if rd_lambda is None else rd_lambda), rd_map)
-        if rd_lambda is not None:
-            return self._encodeRate(x, self._quantizer.rateLambdas(rd_lambda))
-        self._check(x)
-        if x.shape[0] == 0:
+        lams, empty = self._rateArgs(x, rd_lambda, rd_map)
+        if empty:
             # an empty shard (fewer images than ranks, parallel.shard_range): PyTorch's layers hand back empty tensors of the
             # right geometry (the reference's behaviour); the kernels refuse empty launches, so the geometry comes from one blank image
-            return [c[:0] for c in self.encode(x.new_zeros((1,) + tuple(x.shape[1:])))]
+            return [c[:0] for c in self.encode(x.new_zeros((1,) + tuple(x.shape[1:])), rd_lambda=lams)]
+        if rd_map is not None:
+            return self._encodeRateMap(x, lams, rd_map)
+        if lams is not None:
+            return self._encodeRate(x, lams)
         with torch.no_grad():
-            if self._graphs is not None and x.is_cuda and not torch.cuda.is_current_stream_capturing():
+            if self._replays(x):
                 return self._graphed("encode", lambda t: self._quantizer.encode(self._encode_latent(t)), [x.contiguous()])
             return self._quantizer.encode(self._encode_latent(x))
+
+    def _rateArgs(self, x: torch.Tensor, rd_lambda, rd_map):
+        """The arguments of `encode` / `compress` checked, in this order, before any device work: `rd_lambda` (`rateLambdas`: quantizers
+        without tables refuse first), the image batch, the map against its level-0 code grid.  Returns (lams, empty): lams = None for
+        the plain path, the lambdas of the scalar knob, or with a map the per-level scales (None = 1); empty: a batch of no images (with
+        a map that raises: it has no batch to belong to)."""
+        lams = None
+        if rd_lambda is not None or rd_map is not None:
+            lams = self._quantizer.rateLambdas(1.0 if rd_lambda is None else rd_lambda)
+        self._check(x)
+        if rd_map is not None:
+            self._quantizer.checkRateMap(rd_map, *self._rateGrid(x), x.device)
+        if x.shape[0] == 0 and rd_map is not None:
+            raise ValueError("rd_map: an empty batch has no map")
+        return lams, x.shape[0] == 0
+
+    def _replays(self, t: torch.Tensor) -> bool:
+        """A call on `t` replays through the captures of `enableGraphs` (not inside a caller's own capture: that one records us eagerly)."""
+        return self._graphs is not None and t.is_cuda and not torch.cuda.is_current_stream_capturing()
 
     def decode(self, codes: List[torch.Tensor]) -> torch.Tensor:
         if codes[0].shape[0] == 0:                            # (empty shard, see encode)
             return self.decode([c.new_zeros((1,) + tuple(c.shape[1:])) for c in codes])[:0]
         with torch.no_grad():
-            if self._graphs is not None and codes[0].is_cuda and not torch.cuda.is_current_stream_capturing():
+            if self._replays(codes[0]):
                 return self._graphed("decode", lambda *c: self._decoder(self._quantizer.decode(list(c))), [c.contiguous() for c in codes])
             return self._decoder(self._quantizer.decode(codes))
 
@@ -293,14 +312,11 @@ class BaseCompressor(nn.Module):
         and the capture keeps them (`_graphed`): its key names the lambdas, its token the codebooks and tables they were made from,
         so a replay never reads a buffer that was freed, rewritten or made for other tables.  A lambda never seen before costs a
         capture; the least recently used go beyond `RATE_CAPTURES`."""
-        self._check(x)
-        if x.shape[0] == 0:                                   # (empty shard, see encode)
-            return [c[:0] for c in self._encodeRate(x.new_zeros((1,) + tuple(x.shape[1:])), lams)]
         with torch.no_grad():
             def make():
                 packs = self._quantizer.ratePacks(lams)
                 return (lambda t: self._quantizer.encode(self._encode_latent(t), packs=packs)), packs
-            if self._graphs is not None and x.is_cuda and not torch.cuda.is_current_stream_capturing():
+            if self._replays(x):
                 return self._graphed("encode", None, [x.contiguous()], (lams,), token=self._quantizer.rateState(), make=make)
             return make()[0](x)
 
@@ -316,12 +332,8 @@ class BaseCompressor(nn.Module):
         """`encode` with `rd_map` (scales already checked).  Under `enableGraphs` the map and the scales are INPUTS of the capture: its
         key names the image shape and the map's shape, not their values, and it holds no lambda-dependent buffer -- only the tables'
         bits sections, which it keeps, and whose stamp is compared on every call (a capture under older tables is taken again)."""
-        self._check(x)
-        self._quantizer.checkRateMap(rd_map, *self._rateGrid(x), x.device)
-        if x.shape[0] == 0:
-            raise ValueError("rd_map: an empty batch has no map")
         with torch.no_grad():
-            if self._graphs is None or not x.is_cuda or torch.cuda.is_current_stream_capturing():
+            if not self._replays(x):
                 return self._quantizer.encode(self._encode_latent(x), rd_lambda=scales, rd_map=rd_map)
             self._dropStaleCaptures()
             inputs = [x.contiguous(), rd_map.contiguous()]
@@ -450,27 +462,12 @@ class BaseCompressor(nn.Module):
         """`coder`: "host" (the default) codes the streams with csrc/rans.cpp on host threads, "device" with csrc/rans_dev.hip where
         the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same.  `rd_lambda`, `rd_map`: as for `encode`."""
         self._quantizer._checkCoder(coder)
-        if rd_map is not None:
-            scales = self._quantizer.rateLambdas(1.0 if rd_lambda is None else rd_lambda)
-            self._check(x)
-            self._quantizer.checkRateMap(rd_map, *self._rateGrid(x), x.device)
-            n, c, h, w = x.shape
-            if n == 0:
-                raise ValueError("rd_map: an empty batch has no map")
-            with torch.no_grad():
-                codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder, rd_lambda=scales, rd_map=rd_map)
-            return codes, binaries, [FileHeader(__version__, self._qp, codeSize, ImageSize(height=h, width=w, channel=c)) for codeSize in codeSizes]
-        if rd_lambda is not None:
-            rd_lambda = self._quantizer.rateLambdas(rd_lambda)
-        self._check(x)
-        n, c, h, w = x.shape
-        if n == 0:                                            # (empty shard: no streams, no headers)
+        lams, empty = self._rateArgs(x, rd_lambda, rd_map)
+        if empty:                                             # (empty shard: no streams, no headers)
             return self.encode(x), [], []
+        n, c, h, w = x.shape
         with torch.no_grad():
-            if rd_lambda is None:
-                codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder)
-            else:
-                codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder, rd_lambda=rd_lambda)
+            codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder, rd_lambda=lams, rd_map=rd_map)
         header = [FileHeader(__version__, self._qp, codeSize, ImageSize(height=h, width=w, channel=c)) for codeSize in codeSizes]
         return codes, binaries, header
 

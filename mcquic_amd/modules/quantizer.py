@@ -163,16 +163,16 @@ class _multiCodebookQuantization(nn.Module):
         self._codebook.copy_(value)
         self._cache[0].invalidate()
 
-    def encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None) -> torch.Tensor:
-        """[n, m*d, h, w] -> int64 [n, m, h, w] = argmin_k ((x2 + c2) - 2 x.c), first index on ties (:144-179).  `packed`: this
-        codebook packed by the caller -- `ops.pack_codebook_rate`'s, whose norms carry lambda * bits: the same kernel then returns
-        the entropy-constrained assignment argmin_k (distance + lambda * bits_k)."""
-        return ops.vq_assign(x, self._cache[0].get(self._codebook) if packed is None else packed)
-
-    def encodeRateMap(self, x: torch.Tensor, bits: torch.Tensor, lam: torch.Tensor) -> torch.Tensor:
-        """argmin_k fma(lambda_v, bits_k, distance) with one lambda per latent vector (`ops.vq_assign_rate_map`): the plain pack, the
-        level's `ops.pack_bits` section, `lam` [n] or [n, h, w] of `ops.rate_map_levels`."""
-        return ops.vq_assign_rate_map(x, self._cache[0].get(self._codebook), bits, lam)
+    def encode(self, x: torch.Tensor, how=None) -> torch.Tensor:
+        """[n, m*d, h, w] -> int64 [n, m, h, w] = argmin_k ((x2 + c2) - 2 x.c), first index on ties (:144-179).  `how`, the level's
+        assignment operand: None = this codebook's own cached pack; an `ops.PackedCodebook` = this codebook packed by the caller --
+        `ops.pack_codebook_rate`'s, whose norms carry lambda * bits: the same kernel then returns the entropy-constrained assignment
+        argmin_k (distance + lambda * bits_k); a pair (bits section, lambda buffer) = argmin_k fma(lambda_v, bits_k, distance) with one
+        lambda per latent vector (`ops.vq_assign_rate_map`) on the own pack: the level's `ops.pack_bits` section, `lam` [n] or
+        [n, h, w] of `ops.rate_map_levels`."""
+        if isinstance(how, tuple):
+            return ops.vq_assign_rate_map(x, self._cache[0].get(self._codebook), *how)
+        return ops.vq_assign(x, self._cache[0].get(self._codebook) if how is None else how)
 
     def forward(self, x: torch.Tensor, freqEMA: torch.Tensor, uniforms=None, step=None, codebook=None):
         """Training-mode forward (:181-239), forward values only (no autograd graph yet).
@@ -253,21 +253,19 @@ class _quantizerEncoder(nn.Module):
     def reAssignCodebook(self, freq: torch.Tensor) -> torch.Tensor:
         return self._quantizer.reAssignCodebook(freq)
 
-    def encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None, rate=None):
-        residual, code, _ = self._encode(x, packed, rate)
+    def encode(self, x: torch.Tensor, how=None):
+        residual, code, _ = self._encode(x, how)
         return residual, code
 
-    def _encode(self, x: torch.Tensor, packed: Optional[ops.PackedCodebook] = None, rate=None):
-        """(residual for the next level or None, code, the tensor `_quantizer.encode` received).  `packed`: see
-        `_multiCodebookQuantization.encode` (the residual is taken from the plain codebook's row of the code either way).  `rate`:
-        (bits section, lambda buffer) of this level for `_multiCodebookQuantization.encodeRateMap` instead."""
+    def _encode(self, x: torch.Tensor, how=None):
+        """(residual for the next level or None, code, the tensor `_quantizer.encode` received).  `how`: see
+        `_multiCodebookQuantization.encode` (the residual is taken from the plain codebook's row of the code whatever it is)."""
         from ..nn import blocks
         z = self._latentStageEncoder(x)
         head = self._latentHead
-        assign = self._quantizer.encode if rate is None else (lambda q, _packed: self._quantizer.encodeRateMap(q, *rate))
         if head is None:
             qin = self._quantizationHead(z)
-            return None, assign(qin, packed), qin
+            return None, self._quantizer.encode(qin, how), qin
         if blocks.lockstep_ok([self._quantizationHead, head], [z, z]):
             # latentHead(z) does not depend on the codes until its closing conv: everything before that runs in lockstep with
             # quantizationHead (same layer shapes on the same z: one multi-problem launch per layer, four problems in the
@@ -275,10 +273,10 @@ class _quantizerEncoder(nn.Module):
             last = len(head) - 1
             q, t = blocks.lockstep_infer([self._quantizationHead, head], [z, z], layers=last)
             qin = self._quantizationHead[last](q)
-            code = assign(qin, packed)
+            code = self._quantizer.encode(qin, how)
         else:
             qin = self._quantizationHead(z)
-            code = assign(qin, packed)
+            code = self._quantizer.encode(qin, how)
             t = z
             for i in range(len(head) - 1):
                 t = head[i](t)
@@ -400,11 +398,11 @@ class BaseQuantizer(nn.Module):
 
     def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None):
         device = self._checkCoder(coder)
-        if rd_map is not None:
+        rate = {}
+        if rd_lambda is not None or rd_map is not None:
             self.rateLambdas(1.0 if rd_lambda is None else rd_lambda)          # (quantizers without tables refuse here)
-            codes = self.encode(x, rd_lambda=rd_lambda, rd_map=rd_map)
-        else:
-            codes = self.encode(x) if rd_lambda is None else self.encode(x, rd_lambda=self.rateLambdas(rd_lambda))
+            rate = dict(rd_lambda=rd_lambda, rd_map=rd_map)
+        codes = self.encode(x, **rate)
         if device:
             streams = self._entropyCoder.compressDevice(codes)
             return codes, streams.tobytes(), streams.codeSizes
@@ -457,27 +455,48 @@ class UMGMQuantizer(BaseQuantizer):
         again as a device tensor the kernel reads instead (for a capture whose replays take new scales).  A caller that captures this
         call into a graph of its own keeps `rateBitsPacks()`'s list with that graph, as it keeps `ratePacks` for the scalar path: the
         graph launches on those sections, and the cache here lets go of them when the tables change."""
+        return self._cascade(x, self._levelOperands(x, rd_lambda, packs, rd_map, scales_dev))
+
+    def _levelOperands(self, y: torch.Tensor, rd_lambda=None, packs=None, rd_map=None, scales_dev=None) -> list:
+        """`encode`'s arguments as one assignment operand per level (`_multiCodebookQuantization.encode`'s `how`) for the latent `y`:
+        None (plain), the penalised pack (the scalar knob) or (bits section, lambda buffer) (the map).  For a map everything is checked
+        on the host first, then ONE launch (`ops.rate_map_levels`).  The error word is a fresh tensor on every call -- inside a capture it
+        belongs to that graph's pool, so no replay ever writes a word that a later call has replaced -- and becomes what
+        `rateMapError()` returns."""
         if rd_map is not None:
             if packs is not None:
                 raise ValueError("rd_map: `packs` belong to the scalar rd_lambda path")
-            codes = []
-            for encoder, rate in zip(self._encoders, self._rateOperands(x, rd_lambda, rd_map, scales_dev)):
-                x, code = encoder.encode(x, rate=rate)
-                codes.append(code)
-            return codes
-        if rd_lambda is None and packs is None:
-            codes = []
-            for encoder in self._encoders:
-                x, code = encoder.encode(x)
-                codes.append(code)
-            return codes
-        if packs is None:
-            packs = self.ratePacks(self.rateLambdas(rd_lambda))
+            scales = self.rateLambdas(1.0 if rd_lambda is None else rd_lambda)
+            self.checkRateMap(rd_map, int(y.shape[0]), (int(y.shape[-2]) + 1) // 2, (int(y.shape[-1]) + 1) // 2, y.device)
+            bits = self.rateBitsPacks()
+            lams, self.__dict__["_rateMapErr"] = ops.rate_map_levels(rd_map, scales, scales_dev=scales_dev)
+            return list(zip(bits, lams))
+        if packs is not None:
+            return packs
+        return [None] * len(self._encoders) if rd_lambda is None else self.ratePacks(self.rateLambdas(rd_lambda))
+
+    def _cascade(self, x: torch.Tensor, hows, each=None) -> List[torch.Tensor]:
+        """The level cascade, the one copy: level l assigns by `hows[l]` and hands its residual down.  `each(level, code, qin)`: called as
+        soon as a level's launches are enqueued, qin = what its `_quantizer.encode` received."""
         codes = []
-        for encoder, packed in zip(self._encoders, packs):
-            x, code = encoder.encode(x, packed)
+        for lv, (encoder, how) in enumerate(zip(self._encoders, hows)):
+            x, code, qin = encoder._encode(x, how)
             codes.append(code)
+            if each is not None:
+                each(lv, code, qin)
         return codes
+
+    def _rateTables(self):
+        """(the coder's current `deviceCDFs(normalize=False)`, their stamp); their status is read once per stamp (one small copy to the
+        host): a row `compress` would refuse raises its ValueError."""
+        coder = self._entropyCoder
+        tables = coder.deviceCDFs(False)
+        stamp = coder.deviceCDFBuiltStamp(False)
+        if self.__dict__.get("_rateChecked") != stamp:
+            if bool(coder.deviceCDFStatus(False).any()):
+                raise ValueError(INVALID_PMF)
+            self.__dict__["_rateChecked"] = stamp
+        return tables, stamp
 
     @torch.no_grad()
     def ratePacks(self, lams) -> List[ops.PackedCodebook]:
@@ -499,24 +518,9 @@ class UMGMQuantizer(BaseQuantizer):
                 raise RuntimeError("rd_lambda inside a stream capture needs its packs made beforehand: call encode(x, rd_lambda=...) with "
                                    "these lambdas once outside the capture (and again after the codebooks or the tables change)")
             return packs
-        tables = coder.deviceCDFs(False)
-        stamp = coder.deviceCDFBuiltStamp(False)
-        if self.__dict__.get("_rateChecked") != stamp:
-            if bool(coder.deviceCDFStatus(False).any()):
-                raise ValueError(INVALID_PMF)
-            self.__dict__["_rateChecked"] = stamp
+        tables, stamp = self._rateTables()
         return [cache.get(encoder.Codebook, table, stamp, lam)
                 for cache, encoder, table, lam in zip(caches, self._encoders, tables, lams)]
-
-    def _rateOperands(self, y: torch.Tensor, rd_lambda, rd_map, scales_dev=None):
-        """[(bits section, lambda buffer)] per level for the latent `y`: everything checked on the host first, then ONE launch
-        (`ops.rate_map_levels`).  The error word is a fresh tensor on every call -- inside a capture it belongs to that graph's pool, so
-        no replay ever writes a word that a later call has replaced -- and becomes what `rateMapError()` returns."""
-        scales = self.rateLambdas(1.0 if rd_lambda is None else rd_lambda)
-        self.checkRateMap(rd_map, int(y.shape[0]), (int(y.shape[-2]) + 1) // 2, (int(y.shape[-1]) + 1) // 2, y.device)
-        bits = self.rateBitsPacks()
-        lams, self.__dict__["_rateMapErr"] = ops.rate_map_levels(rd_map, scales, scales_dev=scales_dev)
-        return list(zip(bits, lams))
 
     @staticmethod
     def checkRateMap(rd_map, n: int, h0: int, w0: int, device) -> None:
@@ -547,12 +551,7 @@ class UMGMQuantizer(BaseQuantizer):
                 raise RuntimeError("rd_map inside a stream capture needs its bits sections made beforehand: call encode(x, rd_map=...) once "
                                    "outside the capture (and again after the tables change)")
             return cached[1]
-        tables = coder.deviceCDFs(False)
-        stamp = coder.deviceCDFBuiltStamp(False)
-        if self.__dict__.get("_rateChecked") != stamp:
-            if bool(coder.deviceCDFStatus(False).any()):
-                raise ValueError(INVALID_PMF)
-            self.__dict__["_rateChecked"] = stamp
+        tables, stamp = self._rateTables()
         if cached is None or cached[0] != stamp:
             cached = self.__dict__["_rateBits"] = (stamp, [ops.pack_bits(t) for t in tables])
         return cached[1]
@@ -577,9 +576,7 @@ class UMGMQuantizer(BaseQuantizer):
         (the very same launches, lockstep paths included) with the quantization heads' outputs kept -- the data a level's codebook
         is fitted to (mcquic_amd.kmeans)."""
         inputs = []
-        for encoder in self._encoders:
-            y, _, qin = encoder._encode(y)
-            inputs.append(qin)
+        self._cascade(y, self._levelOperands(y), lambda lv, code, qin: inputs.append(qin))
         return inputs
 
     def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None):
@@ -590,14 +587,9 @@ class UMGMQuantizer(BaseQuantizer):
         from .entropyCoder import CODER_OVERLAP
         if self._checkCoder(coder) or not (CODER_OVERLAP and x.is_cuda):     # (the device coder takes all levels in one launch)
             return super().compress(x, coder, rd_lambda, rd_map)
-        rates = [None] * len(self._encoders) if rd_map is None else self._rateOperands(x, rd_lambda, rd_map)
-        packs = [None] * len(self._encoders) if rd_lambda is None or rd_map is not None else self.ratePacks(self.rateLambdas(rd_lambda))
+        hows = self._levelOperands(x, rd_lambda, rd_map=rd_map)
         job = self._entropyCoder.beginCompress(len(self._encoders))
-        codes = []
-        for lv, encoder in enumerate(self._encoders):
-            x, code = encoder.encode(x, packs[lv], rates[lv])
-            codes.append(code)
-            job.submit(lv, code)
+        codes = self._cascade(x, hows, lambda lv, code, qin: job.submit(lv, code))
         binaries, codeSize = job.finish()
         return codes, binaries, codeSize
 

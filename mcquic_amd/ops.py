@@ -693,18 +693,27 @@ def nonneg_reparam_bwd2(p0: torch.Tensor, d0: torch.Tensor, bound0: float, p1: t
 
 
 class PackedCodebook:
-    """Codebook [m, k, d] in MFMA operand order + codeword norms (mcq_vq_pack_codebook_f32)."""
+    """Codebook [m, k, d] in MFMA operand order + codeword norms (mcq_vq_pack_codebook_f32).  `rate`: (cdf, lam) of
+    `pack_codebook_rate`, whose launch then takes the plain one's place."""
 
     __slots__ = ("packed", "codebook", "m", "k", "d")
 
-    def __init__(self, codebook: torch.Tensor):
+    def __init__(self, codebook: torch.Tensor, rate=None):
         cb = _dev(codebook.detach(), "codebook").clone()
+        name, args = "mcq_vq_pack_codebook_f32", ()
+        if rate is not None:
+            if cb.dim() != 3:
+                raise ValueError(f"pack_codebook_rate: codebook must be [m, k, d], got {tuple(cb.shape)}")
+            m, k, d = cb.shape
+            t = _dev(rate[0], "cdf", torch.uint32)
+            if tuple(t.shape) != (m, k + 1) or t.device != cb.device:
+                raise ValueError(f"pack_codebook_rate: a codebook [{m}, {k}, {d}] needs a table [{m}, {k + 1}] on {cb.device}, got {tuple(t.shape)} on {t.device}")
+            name, args = "mcq_vq_pack_codebook_rate_f32", (_ptr(t), rate[1])
         m, k, d = cb.shape
         lib = _lib.load()
-        n = lib.mcq_packed_codebook_floats(m, k, d)
-        self.packed = torch.empty(n, dtype=torch.float32, device=cb.device)
+        self.packed = torch.empty(lib.mcq_packed_codebook_floats(m, k, d), dtype=torch.float32, device=cb.device)
         with _guard(cb.device):
-            check(lib.mcq_vq_pack_codebook_f32(_ptr(cb), m, k, d, _ptr(self.packed), _stream()), "mcq_vq_pack_codebook_f32")
+            check(getattr(lib, name)(_ptr(cb), *args, m, k, d, _ptr(self.packed), _stream()), name)
         self.codebook, self.m, self.k, self.d = cb, m, k, d
 
 
@@ -722,37 +731,33 @@ def pack_codebook_rate(codebook: torch.Tensor, cdf: torch.Tensor, lam: float) ->
     `pmf_to_quantized_cdf_dev`; bits_k = 16 - log2(cdf[k + 1] - cdf[k])): `vq_assign` on it returns argmin_k (distance + lam * bits_k)
     through the unchanged kernel (mcq_vq_pack_codebook_rate_f32).  `lam` = 0 gives `PackedCodebook(codebook)`'s buffer bit for bit;
     a `lam` that is negative, NaN or infinite as a float32 is a ValueError, raised before anything is allocated.  Usable wherever a `PackedCodebook` is; `vq_gather` reads the plain codebook."""
-    lam = lambda_f32(lam)
-    cb = _dev(codebook.detach(), "codebook").clone()
-    if cb.dim() != 3:
-        raise ValueError(f"pack_codebook_rate: codebook must be [m, k, d], got {tuple(cb.shape)}")
-    m, k, d = cb.shape
-    t = _dev(cdf, "cdf", torch.uint32)
-    if tuple(t.shape) != (m, k + 1) or t.device != cb.device:
-        raise ValueError(f"pack_codebook_rate: a codebook [{m}, {k}, {d}] needs a table [{m}, {k + 1}] on {cb.device}, got {tuple(t.shape)} on {t.device}")
-    lib = _lib.load()
-    self = PackedCodebook.__new__(PackedCodebook)
-    self.packed = torch.empty(lib.mcq_packed_codebook_floats(m, k, d), dtype=torch.float32, device=cb.device)
-    with _guard(cb.device):
-        check(lib.mcq_vq_pack_codebook_rate_f32(_ptr(cb), _ptr(t), lam, m, k, d, _ptr(self.packed), _stream()), "mcq_vq_pack_codebook_rate_f32")
-    self.codebook, self.m, self.k, self.d = cb, m, k, d
-    return self
+    return PackedCodebook(codebook, rate=(cdf, lambda_f32(lam)))
 
 
-def vq_assign(x: torch.Tensor, cb: PackedCodebook) -> torch.Tensor:
-    """int64 codes [n, m, h, w] = argmin_k distance (mcq_vq_assign_f32)."""
+def _latent(x: torch.Tensor, cb: PackedCodebook):
+    """(x on the device, n, h, w) of a latent [n, m*d, h, w] for the codebook `cb`."""
     x = _dev(x, "x")
     n, c, h, w = x.shape
     if c != cb.m * cb.d:
         raise ValueError(f"latent has {c} channels, codebook expects {cb.m}*{cb.d}")
+    return x, n, h, w
+
+
+def _assign(name: str, x: torch.Tensor, cb: PackedCodebook, n: int, h: int, w: int, *rate) -> torch.Tensor:
+    """The codes and the workspace of an assignment launch, and the launch: `name` with `rate` between the pack and the codes."""
     codes = torch.empty((n, cb.m, h, w), dtype=torch.int64, device=x.device)
     lib = _lib.load()
     nbytes = lib.mcq_vq_assign_workspace_bytes(n, cb.m, cb.d, h, w, cb.k)       # > 0: a launch too small to fill the GPU ranges the codewords
     ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
     with _guard(x.device):
-        check(lib.mcq_vq_assign_ws_f32(_ptr(x), _ptr(cb.packed), _ptr(codes), n, cb.m, cb.d, h, w, cb.k, _ptr(ws), _stream()),
-              "mcq_vq_assign_ws_f32")
+        check(getattr(lib, name)(_ptr(x), _ptr(cb.packed), *rate, _ptr(codes), n, cb.m, cb.d, h, w, cb.k, _ptr(ws), _stream()), name)
     return codes
+
+
+def vq_assign(x: torch.Tensor, cb: PackedCodebook) -> torch.Tensor:
+    """int64 codes [n, m, h, w] = argmin_k distance (mcq_vq_assign_f32)."""
+    x, n, h, w = _latent(x, cb)
+    return _assign("mcq_vq_assign_ws_f32", x, cb, n, h, w)
 
 
 def pack_bits(cdf: torch.Tensor) -> torch.Tensor:
@@ -775,10 +780,7 @@ def vq_assign_rate_map(x: torch.Tensor, cb: PackedCodebook, bits: torch.Tensor, 
     the PLAIN pack `cb` and `pack_bits`' section.  `lam`: float32 on x's device, finite and >= 0 (`rate_map_levels` makes such buffers).
     `strides` None: lam is [n] (one lambda per image) or [n, h, w], any view with non-negative strides; else the element strides
     (image, row, column) into `lam`'s storage from its first element.  lambda 0 gives `vq_assign`'s code."""
-    x = _dev(x, "x")
-    n, c, h, w = x.shape
-    if c != cb.m * cb.d:
-        raise ValueError(f"latent has {c} channels, codebook expects {cb.m}*{cb.d}")
+    x, n, h, w = _latent(x, cb)
     lib = _lib.load()
     if not (torch.is_tensor(bits) and bits.is_cuda and bits.device == x.device and bits.dtype == torch.float32 and bits.is_contiguous()
             and bits.numel() == lib.mcq_packed_bits_floats(cb.m, cb.k)):
@@ -796,13 +798,7 @@ def vq_assign_rate_map(x: torch.Tensor, cb: PackedCodebook, bits: torch.Tensor, 
     room = lam.untyped_storage().nbytes() // 4 - lam.storage_offset()
     if min(sn, sy, sx) < 0 or (n - 1) * sn + (h - 1) * sy + (w - 1) * sx >= room:
         raise ValueError(f"vq_assign_rate_map: strides {(sn, sy, sx)} are negative or leave `lam`'s storage")
-    codes = torch.empty((n, cb.m, h, w), dtype=torch.int64, device=x.device)
-    nbytes = lib.mcq_vq_assign_workspace_bytes(n, cb.m, cb.d, h, w, cb.k)
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device) if nbytes else None
-    with _guard(x.device):
-        check(lib.mcq_vq_assign_rate_map_f32(_ptr(x), _ptr(cb.packed), _ptr(bits), _ptr(lam), sn, sy, sx, _ptr(codes), n, cb.m, cb.d, h, w,
-                                             cb.k, _ptr(ws), _stream()), "mcq_vq_assign_rate_map_f32")
-    return codes
+    return _assign("mcq_vq_assign_rate_map_f32", x, cb, n, h, w, _ptr(bits), _ptr(lam), sn, sy, sx)
 
 
 def rate_map_grids(h0: int, w0: int, levels: int):
@@ -893,10 +889,7 @@ def vq_gather(codes: torch.Tensor, cb: PackedCodebook, dual_silu: bool = False) 
 
 def vq_logits(x: torch.Tensor, cb: PackedCodebook, temperature: torch.Tensor, bound: float) -> torch.Tensor:
     """Training logits [n, m, h, w, k] = (-dist / sqrt(k)) * max(temperature, bound) (mcq_vq_logits_f32)."""
-    x = _dev(x, "x")
-    n, c, h, w = x.shape
-    if c != cb.m * cb.d:
-        raise ValueError(f"latent has {c} channels, codebook expects {cb.m}*{cb.d}")
+    x, n, h, w = _latent(x, cb)
     t = _dev(temperature.detach().reshape(-1), "temperature")
     logits = torch.empty((n, cb.m, h, w, cb.k), dtype=torch.float32, device=x.device)
     with _guard(x.device):
