@@ -793,6 +793,38 @@ int mcq_rans_decode_dev(const uint8_t* blob, int64_t blob_bytes, const int64_t* 
                         const int32_t* m, const int32_t* k, const int32_t* hw, int32_t levels, int32_t n, int32_t level0, int32_t row_levels,
                         int64_t* const* codes /* [levels] device pointers */, int32_t* status, void* stream);
 
+/* Lane-interleaved streams (additive: ABI 18 stays; csrc/rans_lanes.hip on the device, csrc/rans.cpp on the host): a second, opt-in stream layout whose
+ * unit of work is a wave, not a lane.  A stream still codes one (image, level), but carries W in {1, 2, 4, ..., 64} independent rANS
+ * states over ONE sequence of 32-bit little-endian words.  Per-state arithmetic is the plain coder's, unchanged.  Within group g, round
+ * r = 0 .. ceil(hw / W) - 1 holds positions p = r W + l; lane l is active iff p < hw; the states carry over from group to group and a
+ * round never straddles two groups.  As the decoder reads it:
+ *   word 0            the prefix 'M' 'Q' 'L' W, i.e. MCQ_RANS_LANES_MAGIC | W << 24
+ *   words 1 .. 2 W    the initial states: lane l's x = word[1 + 2 l] | word[2 + 2 l] << 32
+ *   then              round by round every active lane decodes its symbol; the active lanes whose new x < L take the next words in
+ *                     increasing lane order
+ * The encoder is the mirror: groups m - 1 .. 0, rounds last to first, lanes from the highest to the lowest, words written backwards, then
+ * the state words, then the prefix; every lane starts at L, and a lane that never codes flushes L.  At W = 1 the stream is the prefix
+ * followed by the plain stream, byte for byte.  A stream never exceeds 4 (1 + 2 W + m hw) bytes.
+ * `lanes` (per level on the device, per call on the host): 0 = auto, mcq_rans_lanes_auto(m hw) = the largest power of two
+ * <= m hw / MCQ_RANS_LANES_AUTO_SYMBOLS, clamped to [1, MCQ_RANS_LANES_MAX] -- the 2 W flush words then cost at most 1/8 bit per symbol --,
+ * or one of the seven widths; anything else is MCQ_EINVAL.  The decoders take W from the prefix and from nothing else.
+ *   mcq_rans_lanes_encode_dev   as mcq_rans_encode_dev, ONE launch, one wave per stream; the packed blob comes from mcq_rans_pack_dev
+ *             unchanged.  cap_bytes: at least 4 (1 + 2 W_l + m_l hw_l) for every level, else MCQ_EINVAL.
+ *   mcq_rans_lanes_decode_dev   as mcq_rans_decode_dev, ONE launch, one wave per stream.  Untrusted input: a wrong prefix, a W that is not
+ *             one of the seven, fewer than 4 (1 + 2 W) bytes, a length that is not a multiple of 4, running out of words, a bin that does
+ *             not contain the state's low 16 bits, offsets outside the blob or decreasing: MCQ_RANS_BAD_STREAM for that stream only, its
+ *             outputs zeroed; no content of the blob, the offsets or the prefix leads to a load outside the stream. */
+#define MCQ_RANS_LANES_MAX 64
+#define MCQ_RANS_LANES_AUTO_SYMBOLS 512
+#define MCQ_RANS_LANES_MAGIC 0x4C514D
+int mcq_rans_lanes_encode_dev(const int64_t* const* codes /* [levels] device pointers */, const uint32_t* const* cdf /* [levels] device pointers */,
+                              const int32_t* m, const int32_t* k, const int32_t* hw, const int32_t* lanes, int32_t levels, int32_t n,
+                              int32_t level0, int32_t row_levels, uint8_t* scratch, int64_t cap_bytes, int64_t* sizes, int32_t* status,
+                              void* stream);
+int mcq_rans_lanes_decode_dev(const uint8_t* blob, int64_t blob_bytes, const int64_t* offsets, const uint32_t* const* cdf /* [levels] device pointers */,
+                              const int32_t* m, const int32_t* k, const int32_t* hw, int32_t levels, int32_t n, int32_t level0,
+                              int32_t row_levels, int64_t* const* codes /* [levels] device pointers */, int32_t* status, void* stream);
+
 /* Per-step training telemetry kept on the device (csrc/step_meter.hip; host mirror mcquic_amd.monitor.StepMeter): what the
  * reference's trainer reports after an update (mcquic/train/trainer.py:423-441, 463-491) as one float32 row per step in a ring
  * buffer, written by two launches that read every per-step value through a device pointer.  Level tables as for
@@ -1009,6 +1041,17 @@ int mcq_rans_decode_batch_with_indexes(const uint8_t* in, const int64_t* in_offs
                                        int64_t n, const uint32_t* cdfs, const int32_t* cdf_starts, const int32_t* cdf_sizes,
                                        const int32_t* cdf_lens, const int32_t* offsets, int32_t n_cdfs, int32_t* out_symbols,
                                        int32_t n_threads);
+
+/* The lanes layout (see mcq_rans_lanes_encode_dev) on the host: n_streams streams of m hw symbols each (symbols[n_streams][m hw], [m, hw]
+ * order), coded under `cdfs` uint32 [m, k + 1] with `lanes` states (0 = auto), stream i written to out + i * stride (stride >=
+ * 4 (1 + 2 W + m hw) always suffices) with its length in out_nbytes[i]; a symbol outside [0, k) or a bin of width 0 is MCQ_EINVAL.  The
+ * inverse reads stream i = in[in_offsets[i] .. in_offsets[i + 1]) of a blob of in_bytes bytes into out_symbols[i][m hw]; a stream it
+ * refuses (the list at mcq_rans_lanes_decode_dev) leaves zeros and makes the call return MCQ_EINVAL.  Same thread pool as above. */
+int32_t mcq_rans_lanes_auto(int64_t symbols);
+int mcq_rans_lanes_encode_batch(const int32_t* symbols, int64_t n_streams, int32_t m, int64_t hw, const uint32_t* cdfs, int32_t k,
+                                int32_t lanes, uint8_t* out, int64_t stride, int64_t* out_nbytes, int32_t n_threads);
+int mcq_rans_lanes_decode_batch(const uint8_t* in, int64_t in_bytes, const int64_t* in_offsets, int64_t n_streams, int32_t m, int64_t hw,
+                                const uint32_t* cdfs, int32_t k, int32_t* out_symbols, int32_t n_threads);
 
 /* ---- validation metrics (callers of the path: mcquic/validate/handlers.py:14-41) --------------------------------
  * MS-SSIM of two uint8 batches x, y [N, C, H, W] as the reference's MsSSIM handler computes it

@@ -276,3 +276,126 @@ extern "C" int mcq_rans_decode_batch_with_indexes(const uint8_t* in, const int64
         return decode_stream(in + in_offsets[i], in_offsets[i + 1] - in_offsets[i], indexes, n, t, out_symbols + i * n);
     });
 }
+
+// ---- the lanes layout (include/mcquic_hip.h, "lane-interleaved streams"; device side csrc/rans_lanes.hip) ------------------------------
+// W independent states over ONE sequence of words.  Within group g, round r holds positions r W + l; lane l is active iff that is below hw.
+// The decoder reads forwards: prefix 'M' 'Q' 'L' W, the 2 W state words, then per round the words of the lanes that renormalise, lowest
+// lane first.  The encoder is the mirror: groups, rounds and lanes from the last to the first, words written backwards.  Per-state
+// arithmetic is enc_put's and decode_stream's.  Tables are the level's [m, k + 1] array; a code outside [0, k) or a bin whose width is 0 as
+// a uint16 is MCQ_EINVAL, as in encode_stream with the product's cdf_sizes = k + 2 (no bypass digit is ever reached).
+namespace {
+
+constexpr uint32_t kLanesMagic = 0x4Du | 0x51u << 8 | 0x4Cu << 16;
+
+inline bool lanes_width_ok(int64_t w) { return w >= 1 && w <= MCQ_RANS_LANES_MAX && (w & (w - 1)) == 0; }
+
+int64_t lanes_encode_stream(const int32_t* symbols, int32_t m, int64_t hw, const uint32_t* cdfs, int32_t k, int32_t W, uint8_t* out,
+                            int64_t capacity) {
+    const int64_t count = (int64_t)m * hw;
+    for (int64_t i = 0; i < count; ++i) {                       // before anything is indexed with it
+        const int32_t c = symbols[i];
+        if (c < 0 || c >= k) return MCQ_EINVAL;
+        const uint32_t* t = cdfs + (i / hw) * ((int64_t)k + 1);
+        if ((uint16_t)(t[c + 1] - t[c]) == 0) return MCQ_EINVAL;
+    }
+    std::vector<uint32_t> buf((size_t)(count + 2 * W + 1));
+    uint32_t* ptr = buf.data() + buf.size();
+    uint64_t x[MCQ_RANS_LANES_MAX];
+    for (int l = 0; l < W; ++l) x[l] = kRansL;
+    const int64_t rounds = (hw + W - 1) / W;
+    for (int32_t g = m; g-- > 0;) {
+        const uint32_t* t = cdfs + (int64_t)g * ((int64_t)k + 1);
+        const int32_t* sym = symbols + (int64_t)g * hw;
+        for (int64_t r = rounds; r-- > 0;)
+            for (int l = W; l-- > 0;) {
+                const int64_t p = r * W + l;
+                if (p >= hw) continue;
+                const int32_t c = sym[p];
+                enc_put(x[l], ptr, (uint16_t)t[c], (uint16_t)(t[c + 1] - t[c]), kPrecision);
+            }
+    }
+    for (int l = W; l-- > 0;) {
+        ptr -= 2;
+        ptr[0] = (uint32_t)x[l];
+        ptr[1] = (uint32_t)(x[l] >> 32);
+    }
+    *--ptr = kLanesMagic | (uint32_t)W << 24;
+    const int64_t nbytes = (int64_t)((buf.data() + buf.size()) - ptr) * 4;
+    if (nbytes > capacity) return MCQ_ETOOLARGE;
+    std::memcpy(out, ptr, (size_t)nbytes);
+    return nbytes;
+}
+
+int lanes_decode_stream(const uint8_t* in, int64_t nbytes, int32_t m, int64_t hw, const uint32_t* cdfs, int32_t k, int32_t* out_symbols) {
+    if (nbytes < 4 || (nbytes & 3)) return MCQ_EINVAL;
+    uint32_t prefix;
+    std::memcpy(&prefix, in, 4);
+    const int W = (int)(prefix >> 24);
+    if ((prefix & 0xffffffu) != kLanesMagic || !lanes_width_ok(W) || nbytes < 4 * (1 + 2 * (int64_t)W)) return MCQ_EINVAL;
+    std::vector<uint32_t> words((size_t)nbytes / 4);
+    std::memcpy(words.data(), in, (size_t)nbytes);
+    const uint32_t* ptr = words.data() + 1 + 2 * W;
+    const uint32_t* end = words.data() + words.size();
+    uint64_t x[MCQ_RANS_LANES_MAX];
+    for (int l = 0; l < W; ++l) x[l] = (uint64_t)words[1 + 2 * l] | ((uint64_t)words[2 + 2 * l] << 32);
+    const int64_t rounds = (hw + W - 1) / W;
+    for (int32_t g = 0; g < m; ++g) {
+        const uint32_t* t = cdfs + (int64_t)g * ((int64_t)k + 1);
+        int32_t* sym = out_symbols + (int64_t)g * hw;
+        for (int64_t r = 0; r < rounds; ++r)
+            for (int l = 0; l < W; ++l) {
+                const int64_t p = r * W + l;
+                if (p >= hw) break;
+                const uint32_t cum = (uint32_t)(x[l] & 0xffffu);
+                int32_t lo = 1, hi = k;                         // first of the entries 1 .. k - 1 strictly above cum, less one
+                while (lo < hi) { const int32_t mid = (lo + hi) >> 1; if (t[mid] > cum) hi = mid; else lo = mid + 1; }
+                const int32_t s = lo - 1;
+                const uint32_t start = t[s], next = t[s + 1];
+                if (!(start <= cum && cum < next)) return MCQ_EINVAL;          // not this bin's: a table whose ends are not 0 and 2^16
+                x[l] = (uint64_t)(next - start) * (x[l] >> kPrecision) + cum - start;
+                if (x[l] < kRansL) {
+                    if (ptr >= end) return MCQ_EINVAL;
+                    x[l] = (x[l] << 32) | *ptr++;
+                }
+                sym[p] = s;
+            }
+    }
+    return MCQ_OK;
+}
+
+}  // namespace
+
+extern "C" int32_t mcq_rans_lanes_auto(int64_t symbols) {
+    int32_t w = 1;
+    while (w < MCQ_RANS_LANES_MAX && (int64_t)w * 2 * MCQ_RANS_LANES_AUTO_SYMBOLS <= symbols) w *= 2;
+    return w;
+}
+
+extern "C" int mcq_rans_lanes_encode_batch(const int32_t* symbols, int64_t n_streams, int32_t m, int64_t hw, const uint32_t* cdfs, int32_t k,
+                                           int32_t lanes, uint8_t* out, int64_t stride, int64_t* out_nbytes, int32_t n_threads) {
+    if (!symbols || !cdfs || !out || !out_nbytes || n_streams < 0 || m <= 0 || hw <= 0 || k <= 0 || k > 65536) return MCQ_EINVAL;
+    if (lanes != 0 && !lanes_width_ok(lanes)) return MCQ_EINVAL;
+    if (hw > MCQ_RANS_DEV_MAX_SYMBOLS / m) return MCQ_ETOOLARGE;
+    const int32_t W = lanes ? lanes : mcq_rans_lanes_auto((int64_t)m * hw);
+    if (stride < 4 * (1 + 2 * (int64_t)W)) return MCQ_EINVAL;
+    const int64_t n = (int64_t)m * hw;
+    return run_pool(n_streams, n_threads, [&](int64_t i) -> int {
+        const int64_t nb = lanes_encode_stream(symbols + i * n, m, hw, cdfs, k, W, out + i * stride, stride);
+        out_nbytes[i] = nb < 0 ? 0 : nb;
+        return nb < 0 ? (int)nb : MCQ_OK;
+    });
+}
+
+extern "C" int mcq_rans_lanes_decode_batch(const uint8_t* in, int64_t in_bytes, const int64_t* in_offsets, int64_t n_streams, int32_t m,
+                                           int64_t hw, const uint32_t* cdfs, int32_t k, int32_t* out_symbols, int32_t n_threads) {
+    if (!in || !in_offsets || !cdfs || !out_symbols || in_bytes < 0 || n_streams < 0 || m <= 0 || hw <= 0 || k <= 0 || k > 65536) return MCQ_EINVAL;
+    if (hw > MCQ_RANS_DEV_MAX_SYMBOLS / m) return MCQ_ETOOLARGE;
+    const int64_t n = (int64_t)m * hw;
+    return run_pool(n_streams, n_threads, [&](int64_t i) -> int {
+        const int64_t a = in_offsets[i], b = in_offsets[i + 1];
+        int rc = MCQ_EINVAL;                                    // offsets outside the blob or decreasing: nothing is read through them
+        if (a >= 0 && b >= a && b <= in_bytes) rc = lanes_decode_stream(in + a, b - a, m, hw, cdfs, k, out_symbols + i * n);
+        if (rc != MCQ_OK) std::memset(out_symbols + i * n, 0, (size_t)n * sizeof(int32_t));      // a refused stream leaves zeros
+        return rc;
+    });
+}

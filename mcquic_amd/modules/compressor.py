@@ -458,16 +458,20 @@ class BaseCompressor(nn.Module):
         out = (codes, lam, tbpp[trials].clone())
         return out + (tlam[:trials], tbpp[:trials]) if trace else out
 
-    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None) -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None,
+                 lanes=None) -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
         """`coder`: "host" (the default) codes the streams with csrc/rans.cpp on host threads, "device" with csrc/rans_dev.hip where
-        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same.  `rd_lambda`, `rd_map`: as for `encode`."""
+        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same.  `rd_lambda`, `rd_map`: as for `encode`.
+        `lanes`: None (the default) for the reference's streams; "auto" or a power of two <= 64 for the lane-interleaved layout
+        (DESIGN.md section 3), whose streams `decompress(..., lanes=True)` reads -- the same bytes under either coder."""
         self._quantizer._checkCoder(coder)
+        layout = self._quantizer._checkLanes(lanes)
         lams, empty = self._rateArgs(x, rd_lambda, rd_map)
         if empty:                                             # (empty shard: no streams, no headers)
             return self.encode(x), [], []
         n, c, h, w = x.shape
         with torch.no_grad():
-            codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder, rd_lambda=lams, rd_map=rd_map)
+            codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder, rd_lambda=lams, rd_map=rd_map, **layout)
         header = [FileHeader(__version__, self._qp, codeSize, ImageSize(height=h, width=w, channel=c)) for codeSize in codeSizes]
         return codes, binaries, header
 
@@ -484,13 +488,15 @@ class BaseCompressor(nn.Module):
                 raise RuntimeError(f"The header's code size {list(code.heights)} x {list(code.widths)} does not belong to a "
                                    f"{size.height} x {size.width} image.")
 
-    def decompress(self, binaries: List[List[bytes]], headers: List[FileHeader], coder: str = "host") -> torch.Tensor:
-        """`coder`: "host" (the default) or "device" (`EntropyCoder.decompressDevice`), as for `compress`; the same image either way."""
+    def decompress(self, binaries: List[List[bytes]], headers: List[FileHeader], coder: str = "host", lanes: bool = False) -> torch.Tensor:
+        """`coder`: "host" (the default) or "device" (`EntropyCoder.decompressDevice`), as for `compress`; the same image either way.
+        `lanes`: True for the streams of `compress(..., lanes=...)`; streams of the other layout raise."""
         self._quantizer._checkCoder(coder)
+        layout = self._quantizer._checkLanes(lanes)
         if type(self)._encode_latent is BaseCompressor._encode_latent:       # (Compressor's 16x stem; Neon's geometry differs)
             self._checkHeaderGeometry(headers)
         with torch.no_grad():
-            restored = self._decoder(self._quantizer.decompress(binaries, [header.CodeSize for header in headers], coder))
+            restored = self._decoder(self._quantizer.decompress(binaries, [header.CodeSize for header in headers], coder, **layout))
         imageSize = headers[0].ImageSize
         H, W = restored.shape[-2], restored.shape[-1]
         h, w = imageSize.height, imageSize.width

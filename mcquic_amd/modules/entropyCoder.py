@@ -156,6 +156,70 @@ def ransDecodeBatchWithIndexes(binaries: List[bytes], indexes: np.ndarray, t: _T
     return out
 
 
+# ---- the lane-interleaved layout on the host (csrc/rans.cpp; include/mcquic_hip.h has the layout) ------------------------------------
+LANES_WIDTHS = (1, 2, 4, 8, 16, 32, 64)
+LANES_MAGIC = b"MQL"
+NOT_PLAIN = "Got a lane-interleaved rANS stream: decode it with lanes=True."
+NOT_LANES = "Got a stream without the lanes prefix: decode it with lanes=False."
+
+
+def lanesAuto(symbols: int) -> int:
+    """W of lanes="auto" for a stream of `symbols` codes: the largest power of two <= symbols / 512, clamped to [1, 64]
+    (`mcq_rans_lanes_auto`).  The 2 W flush words then cost at most symbols / 64 bytes: 1/8 bit per symbol."""
+    return int(_lib.load().mcq_rans_lanes_auto(int(symbols)))
+
+
+def lanesWidth(lanes) -> int:
+    """A `lanes` argument for one level as the C ABI's int: "auto" -> 0, one of LANES_WIDTHS -> itself."""
+    if isinstance(lanes, str) and lanes == "auto":
+        return 0
+    if isinstance(lanes, int) and not isinstance(lanes, bool) and lanes in LANES_WIDTHS:
+        return int(lanes)
+    raise ValueError(f"lanes must be 'auto' or a power of two <= {LANES_WIDTHS[-1]}, got {lanes!r}")
+
+
+def isLanesStream(binary) -> bool:
+    """True when `binary` opens with a lanes prefix ('M' 'Q' 'L' W, W one of the seven widths) and is long enough to hold its 2 W state
+    words.  A plain stream opens with the low word of its final state: it reads as such a prefix seven times in 2^32."""
+    b = bytes(binary[:4])
+    return len(b) == 4 and b[:3] == LANES_MAGIC and b[3] in LANES_WIDTHS and len(binary) >= 4 * (1 + 2 * b[3])
+
+
+def ransLanesEncodeBatch(symbols: np.ndarray, m: int, hw: int, cdfs: np.ndarray, lanes="auto", threads: int = 0) -> List[bytes]:
+    """symbols [n_streams, m * hw] ([m, hw] order per row) under `cdfs` uint32 [m, k + 1] -> one lanes stream per row, ONE C call over the
+    host thread pool (mcq_rans_lanes_encode_batch)."""
+    symbols = np.ascontiguousarray(symbols, dtype=np.int32)
+    cdfs = np.ascontiguousarray(cdfs, dtype=np.uint32).reshape(m, -1)
+    ns, n = symbols.shape
+    if n != m * hw:
+        raise ValueError(f"ransLanesEncodeBatch: rows of m * hw = {m * hw} symbols expected, got {n}")
+    stride = 4 * n + 8 + 4 * (1 + 2 * LANES_WIDTHS[-1])
+    out = np.empty((ns, stride), dtype=np.uint8)
+    sizes = np.zeros(ns, dtype=np.int64)
+    rc = _lib.load().mcq_rans_lanes_encode_batch(_vp(symbols), ns, m, hw, _vp(cdfs), cdfs.shape[1] - 1, lanesWidth(lanes), _vp(out), stride,
+                                                 _vp(sizes), _poolThreads(threads, symbols.size))
+    if rc != 0:
+        raise RuntimeError(f"rANS encode failed ({rc}): a code index outside [0, k), or a malformed table")
+    return [out[i, :sizes[i]].tobytes() for i in range(ns)]
+
+
+def ransLanesDecodeBatch(binaries: List[bytes], m: int, hw: int, cdfs: np.ndarray, threads: int = 0, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """One lanes stream per row -> int32 [n_streams, m * hw]; each stream's width comes from its own prefix (mcq_rans_lanes_decode_batch)."""
+    cdfs = np.ascontiguousarray(cdfs, dtype=np.uint32).reshape(m, -1)
+    offs = np.zeros(len(binaries) + 1, dtype=np.int64)
+    np.cumsum([len(b) for b in binaries], out=offs[1:])
+    buf = np.frombuffer(b"".join(bytes(b) for b in binaries) + b"\0", dtype=np.uint8)       # (an empty blob still needs an address)
+    if out is None:
+        out = np.empty((len(binaries), m * hw), dtype=np.int32)
+    elif out.dtype != np.int32 or out.shape != (len(binaries), m * hw) or not out.flags.c_contiguous:
+        raise ValueError("ransLanesDecodeBatch: `out` must be a C-contiguous int32 [n_streams, m * hw] array")
+    rc = _lib.load().mcq_rans_lanes_decode_batch(_vp(buf), buf.size - 1, _vp(offs), len(binaries), m, hw, _vp(cdfs), cdfs.shape[1] - 1, _vp(out),
+                                                 _poolThreads(threads, out.size))
+    if rc != 0:
+        raise RuntimeError("Got a truncated or malformed rANS stream.")
+    return out
+
+
 class EntropyCoder(nn.Module):
     def __init__(self, m: int, k: List[int], ema: float = 0.9):
         super().__init__()
@@ -359,7 +423,7 @@ class EntropyCoder(nn.Module):
     # ---- byte streams made and read on the device (csrc/rans_dev.hip) ---------------------------------------------------------------
     @torch.no_grad()
     def compressDevice(self, codes: List[torch.Tensor], normalize: bool = False, cdfs: Optional[List[torch.Tensor]] = None,
-                       out: Optional["DeviceStreams"] = None) -> "DeviceStreams":
+                       out: Optional["DeviceStreams"] = None, lanes=None) -> "DeviceStreams":
         """codes: level-length list of int64 [n, m, h, w] on the device -> the streams of `compress`, byte for byte, coded there under
         `deviceCDFs(normalize)`, or the tables given as `cdfs` (`ops.rans_encode_dev`: three launches for all levels and images, nothing copied to the host and nothing
         waited for, so the call captures into a graph together with `deviceCDFs(normalize=True)`).  With normalize=False the tables are
@@ -367,30 +431,40 @@ class EntropyCoder(nn.Module):
         A code outside [0, k) does not raise here: it sets the stream's status, which `DeviceStreams.check()` / `.tobytes()` turn into
         `compress`'s RuntimeError.  The host coder's bypass digits are not implemented on the device (no code in [0, k) reaches them).
         `out`: the DeviceStreams of an earlier call with codes of these shapes, whose buffers are then written in place.  Same shape
-        checks and errors as `compress`."""
+        checks and errors as `compress`.  `lanes`: None for the reference's layout; "auto", a power of two <= 64, or one of either per
+        level for the lane-interleaved layout (csrc/rans_lanes.hip), byte for byte `compress(codes, lanes=...)`."""
         from .. import ops
         n, m = self._checkShape(codes)
         if len(codes) != len(self._freqEMA):
             raise RuntimeError(f"expected {len(self._freqEMA)} code levels, got {len(codes)}")
-        encoded = ops.rans_encode_dev(codes, self.deviceCDFs(normalize) if cdfs is None else cdfs, None if out is None else out.encoded)
+        encoded = ops.rans_encode_dev(codes, self.deviceCDFs(normalize) if cdfs is None else cdfs, None if out is None else out.encoded,
+                                      **({} if lanes is None else {"lanes": lanes}))
         heights, widths = [int(c.shape[2]) for c in codes], [int(c.shape[3]) for c in codes]
-        return DeviceStreams(encoded, n, len(codes), [CodeSize([m] * len(codes), heights, widths, list(self._k)) for _ in range(n)])
+        streams = DeviceStreams(encoded, n, len(codes), [CodeSize([m] * len(codes), heights, widths, list(self._k)) for _ in range(n)])
+        streams.lanes = lanes is not None
+        return streams
 
     @torch.no_grad()
-    def decompressDevice(self, binaries, codeSizes: List[CodeSize], check: bool = True) -> List[torch.Tensor]:
+    def decompressDevice(self, binaries, codeSizes: List[CodeSize], check: bool = True, lanes: bool = False) -> List[torch.Tensor]:
         """`decompress` with the decoder on the device (`ops.rans_decode_dev`, ONE launch): `binaries` is binaries[n][level] of host
         `bytes` -- uploaded as one blob plus offsets -- or a `DeviceStreams`, which never leaves the device.  Returns the level-length
         list of int64 [n, m, h, w], written by the kernel as int64.  The headers pass `_checkHeaders` first, as in `decompress`; the
         streams are untrusted too, and one that is truncated or malformed leaves its codes zero and sets its word of `decodeStatus()`.
         `check`: read that status back (one synchronisation) and raise `decompress`'s RuntimeError if any is set; never while a
-        stream is capturing."""
+        stream is capturing.  `lanes`: True for lane-interleaved streams (each carries its width in its prefix); a stream of the other
+        layout is refused either way -- here where the layout can be told without decoding, by its status word otherwise."""
         from .. import ops
+        lanes = bool(lanes)
         onDevice = isinstance(binaries, DeviceStreams)
         if onDevice:
             first = self._checkHeaders([[None] * binaries.levels for _ in range(binaries.n)], codeSizes)
             blob, offsets = binaries.blob, binaries.offsets
+            if binaries.lanes != lanes:
+                raise RuntimeError(NOT_PLAIN if binaries.lanes else NOT_LANES)
         else:
             first = self._checkHeaders(binaries, codeSizes)
+            if not lanes:
+                self._refuseLanesStreams(binaries)
         levels = len(self._freqEMA)
         n = len(codeSizes)
         device = self._freqEMA[0].device
@@ -404,7 +478,7 @@ class EntropyCoder(nn.Module):
             blob = host.pin_memory().to(device, non_blocking=True)
             offsets = lengths.cumsum(0).pin_memory().to(device, non_blocking=True)
         shapes = [(n, self._m, int(first.heights[lv]), int(first.widths[lv])) for lv in range(levels)]
-        codes, status = ops.rans_decode_dev(blob, offsets, self.deviceCDFs(), shapes)
+        codes, status = ops.rans_decode_dev(blob, offsets, self.deviceCDFs(), shapes, **({"lanes": True} if lanes else {}))
         self.__dict__["_decodeStatus"] = status
         if check and not torch.cuda.is_current_stream_capturing() and bool(status.any()):
             raise RuntimeError("Got a truncated or malformed rANS stream.")
@@ -417,12 +491,22 @@ class EntropyCoder(nn.Module):
             raise RuntimeError("decodeStatus: no `decompressDevice` call has run yet")
         return status
 
+    @staticmethod
+    def _refuseLanesStreams(binaries) -> None:
+        """The plain decoders cannot tell a lanes stream from their own: it is told by its prefix here, before anything is decoded."""
+        if any(isLanesStream(b) for binary in binaries for b in binary):
+            raise RuntimeError(NOT_PLAIN)
+
     # ---- byte streams (entropyCoder.py:95-154) ----------------------------------------------------------------
     @torch.inference_mode()
-    def compress(self, codes: List[torch.Tensor]) -> Tuple[List[List[bytes]], List[CodeSize]]:
+    def compress(self, codes: List[torch.Tensor], lanes=None) -> Tuple[List[List[bytes]], List[CodeSize]]:
         """codes: level-length list of [n, m, h, w] -> (binaries[n][level], CodeSize per image).
         Per level: one device-to-host copy (all levels' copies are enqueued before the first one is waited for) and ONE
-        call into the host coder, which spreads the n images' streams over a thread pool."""
+        call into the host coder, which spreads the n images' streams over a thread pool.
+        `lanes`: None for the reference's layout; "auto", a power of two <= 64, or one of either per level for the lane-interleaved
+        layout (`ransLanesEncodeBatch`), which `decompress(..., lanes=True)` and the device decoder read."""
+        if lanes is not None:
+            return self._compressLanes(codes, lanes)
         n, m = self._checkShape(codes)
         self.CDFs  # refresh the tables if the EMA changed
         if len(codes) != len(self._tables):
@@ -448,6 +532,28 @@ class EntropyCoder(nn.Module):
                 compressed[i].append(b)
         return compressed, [CodeSize([m] * len(codes), heights, widths, list(self._k)) for _ in range(n)]
 
+    def _compressLanes(self, codes: List[torch.Tensor], lanes):
+        """`compress` in the lanes layout: the same copies and tables, `ransLanesEncodeBatch` per level."""
+        n, m = self._checkShape(codes)
+        self.CDFs
+        if len(codes) != len(self._tables):
+            raise RuntimeError(f"expected {len(self._tables)} code levels, got {len(codes)}")
+        per = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes] * len(codes)
+        if len(per) != len(codes):
+            raise ValueError(f"one lanes entry per level ({len(codes)}), got {len(per)}")
+        for w in per:
+            lanesWidth(w)                                     # (refused before anything is copied)
+        hosts = [code.detach().to(torch.int32).cpu() for code in codes]
+        compressed: List[List[bytes]] = [[] for _ in range(n)]
+        heights, widths = [], []
+        for host, table, w in zip(hosts, self._tables, per):
+            _, _, h, wd = host.shape
+            heights.append(h)
+            widths.append(wd)
+            for i, b in enumerate(ransLanesEncodeBatch(host.numpy().reshape(n, m * h * wd), m, h * wd, table.cdfs, w)):
+                compressed[i].append(b)
+        return compressed, [CodeSize([m] * len(codes), heights, widths, list(self._k)) for _ in range(n)]
+
     # ---- the same, overlapped with the kernels that make / use the codes (round 6) ---------------------------------------------
     # `compress` above copies every level, waits for the whole stream, then codes on the host; `decompress` decodes every level
     # before the first kernel of the decoder is enqueued.  But level 0's codes (3/4 of the symbols) exist long before levels 1 .. are
@@ -466,6 +572,7 @@ class EntropyCoder(nn.Module):
 
     def beginDecompress(self, binaries: List[List[bytes]], codeSizes: List[CodeSize]) -> "_DecompressJob":
         first = self._checkHeaders(binaries, codeSizes)
+        self._refuseLanesStreams(binaries)
         return _DecompressJob(self, binaries, first)
 
     # what a header may ask the decoder to allocate: a side of 2^15 latent positions is a 2-megapixel-wide image 64 times over
@@ -502,15 +609,24 @@ class EntropyCoder(nn.Module):
         return first
 
     @torch.inference_mode()
-    def decompress(self, binaries: List[List[bytes]], codeSizes: List[CodeSize]) -> List[torch.Tensor]:
+    def decompress(self, binaries: List[List[bytes]], codeSizes: List[CodeSize], lanes: bool = False) -> List[torch.Tensor]:
         """binaries[n][level] -> level-length list of int64 [n, m, h, w] on the coder's device.  Header fields are
         untrusted input (they come out of a `.mcq` file): m / k must be this model's, sizes positive and bounded, all
-        images of a batch alike -- checked before anything is allocated."""
+        images of a batch alike -- checked before anything is allocated.  `lanes`: True for lane-interleaved streams
+        (`ransLanesDecodeBatch`; each stream's width comes from its prefix); a stream of the other layout raises."""
         first = self._checkHeaders(binaries, codeSizes)
         levels = len(self._tables)
         device = self._freqEMA[0].device
         n = len(binaries)
         out = []
+        if lanes:
+            for lv, table in enumerate(self._tables):
+                h, w = int(first.heights[lv]), int(first.widths[lv])
+                host = torch.empty((n, self._m * h * w), dtype=torch.int32, pin_memory=device.type == "cuda")
+                ransLanesDecodeBatch([binary[lv] for binary in binaries], self._m, h * w, table.cdfs, out=host.numpy())
+                out.append(host.to(device, non_blocking=True).to(torch.int64).reshape(n, self._m, h, w))
+            return out
+        self._refuseLanesStreams(binaries)
         for lv, table in enumerate(self._tables):
             h, w = int(first.heights[lv]), int(first.widths[lv])
             idx = np.repeat(np.arange(self._m, dtype=np.int32), h * w)
@@ -528,7 +644,10 @@ class DeviceStreams:
     """The streams of one `EntropyCoder.compressDevice` call, still on the device: `blob` (uint8; stream i * levels + l, image-major, is
     blob[offsets[s] : offsets[s + 1]]), `offsets` (int64 [n * levels + 1]), `status` (int32 [n * levels], non-zero where a code lay
     outside [0, k)), and `n`, `levels`, `codeSizes` (one CodeSize per image, as `compress` returns them).  `encoded` is the
-    `ops.RansEncoded` behind them, whose buffers a later `compressDevice(..., out=this)` writes in place."""
+    `ops.RansEncoded` behind them, whose buffers a later `compressDevice(..., out=this)` writes in place.  `lanes`: whether the streams
+    are lane-interleaved (`compressDevice(..., lanes=...)`)."""
+
+    lanes = False
 
     def __init__(self, encoded, n: int, levels: int, codeSizes: List[CodeSize]):
         self.encoded = encoded

@@ -396,23 +396,34 @@ class BaseQuantizer(nn.Module):
                                       "writes raw codes and keeps no 16-bit tables to take the penalties from")
         return rateLambdas(rd_lambda, len(self._k))
 
-    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None):
+    def _checkLanes(self, lanes) -> dict:
+        """The coder's `lanes` keyword for a request of the lane-interleaved layout, {} for the plain one (None / False): the plain
+        calls stay as they were.  Coders that write raw codes have no rANS streams to interleave."""
+        if lanes is None or lanes is False:
+            return {}
+        if not isinstance(self._entropyCoder, EntropyCoder):
+            raise NotImplementedError(f"{type(self._entropyCoder).__name__} writes raw codes, not rANS streams: it has no lanes layout")
+        return {"lanes": lanes}
+
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None, lanes=None):
         device = self._checkCoder(coder)
+        layout = self._checkLanes(lanes)
         rate = {}
         if rd_lambda is not None or rd_map is not None:
             self.rateLambdas(1.0 if rd_lambda is None else rd_lambda)          # (quantizers without tables refuse here)
             rate = dict(rd_lambda=rd_lambda, rd_map=rd_map)
         codes = self.encode(x, **rate)
         if device:
-            streams = self._entropyCoder.compressDevice(codes)
+            streams = self._entropyCoder.compressDevice(codes, **layout)
             return codes, streams.tobytes(), streams.codeSizes
-        binaries, codeSize = self._entropyCoder.compress(codes)
+        binaries, codeSize = self._entropyCoder.compress(codes, **layout)
         return codes, binaries, codeSize
 
-    def decompress(self, binaries, codeSize, coder: str = "host") -> torch.Tensor:
+    def decompress(self, binaries, codeSize, coder: str = "host", lanes: bool = False) -> torch.Tensor:
+        layout = self._checkLanes(lanes)
         if self._checkCoder(coder):
-            return self.decode(self._entropyCoder.decompressDevice(binaries, codeSize))
-        return self.decode(self._entropyCoder.decompress(binaries, codeSize))
+            return self.decode(self._entropyCoder.decompressDevice(binaries, codeSize, **layout))
+        return self.decode(self._entropyCoder.decompress(binaries, codeSize, **layout))
 
 
 class UMGMQuantizer(BaseQuantizer):
@@ -579,12 +590,15 @@ class UMGMQuantizer(BaseQuantizer):
         self._cascade(y, self._levelOperands(y), lambda lv, code, qin: inputs.append(qin))
         return inputs
 
-    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None):
+    def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None, lanes=None):
         """`encode` + the entropy coder (mcquic/modules/entropyCoder.py:108-126) with the coder taken level by level: a level's codes
         leave for the host (a copy in stream order, then a host thread) as soon as they are enqueued, while the GPU computes the levels below it --
         level 0 holds three quarters of the symbols and is ready first.  Same codes, same bytes as encode() + coder.compress().
-        `rd_lambda`, `rd_map`: as for `encode` (the same overlap with either)."""
+        `rd_lambda`, `rd_map`: as for `encode` (the same overlap with either).  `lanes`: the lane-interleaved layout
+        (`EntropyCoder.compress`), which takes the all-levels path as the device coder does."""
         from .entropyCoder import CODER_OVERLAP
+        if self._checkLanes(lanes):
+            return super().compress(x, coder, rd_lambda, rd_map, lanes=lanes)
         if self._checkCoder(coder) or not (CODER_OVERLAP and x.is_cuda):     # (the device coder takes all levels in one launch)
             return super().compress(x, coder, rd_lambda, rd_map)
         hows = self._levelOperands(x, rd_lambda, rd_map=rd_map)
@@ -593,11 +607,13 @@ class UMGMQuantizer(BaseQuantizer):
         binaries, codeSize = job.finish()
         return codes, binaries, codeSize
 
-    def decompress(self, binaries, codeSize, coder: str = "host") -> torch.Tensor:
+    def decompress(self, binaries, codeSize, coder: str = "host", lanes: bool = False) -> torch.Tensor:
         """The coder's streams -> `decode` (entropyCoder.py:141-154) with the levels decoded on a host thread in the order the decoder
         cascade consumes them -- the last (smallest) level first: its kernels are enqueued while the larger levels are still being
-        decoded."""
+        decoded.  `lanes`: True for lane-interleaved streams (the all-levels path)."""
         from .entropyCoder import CODER_OVERLAP
+        if self._checkLanes(lanes):
+            return super().decompress(binaries, codeSize, coder, lanes=lanes)
         if self._checkCoder(coder) or not (CODER_OVERLAP and self._entropyCoder._freqEMA[0].is_cuda):
             return super().decompress(binaries, codeSize, coder)
         job = self._entropyCoder.beginDecompress(binaries, codeSize)

@@ -1314,7 +1314,28 @@ def _rans_levels(codes_shapes, ts, who: str):
     return (n, [int(s[1]) for s in codes_shapes], [int(t.shape[1]) - 1 for t in ts], [int(s[2]) * int(s[3]) for s in codes_shapes])
 
 
-def rans_encode_dev(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor], out: Optional[RansEncoded] = None) -> RansEncoded:
+RANS_LANES_MAX = _lib.MCQ_RANS_LANES_MAX                 # the widest lanes stream: one state per lane of a wave
+RANS_LANES_HEAD = 4 * (1 + 2 * RANS_LANES_MAX)          # bytes of prefix and state words at that width
+
+
+def rans_lanes_widths(lanes, levels: int, who: str = "lanes"):
+    """A `lanes` argument as one int per level for the C ABI: "auto" -> 0 (the library's rule, `mcq_rans_lanes_auto`), a power of two
+    <= RANS_LANES_MAX -> itself, a sequence -> one of either per level.  None / False (the plain layout) is not a width."""
+    per = list(lanes) if isinstance(lanes, (list, tuple)) else [lanes] * levels
+    if len(per) != levels:
+        raise ValueError(f"{who}: one lanes entry per level ({levels}), got {len(per)}")
+    out = []
+    for w in per:
+        if isinstance(w, str) and w == "auto":
+            out.append(0)
+        elif isinstance(w, int) and not isinstance(w, bool) and 1 <= w <= RANS_LANES_MAX and w & (w - 1) == 0:
+            out.append(int(w))
+        else:
+            raise ValueError(f"{who}: lanes must be 'auto' or a power of two <= {RANS_LANES_MAX}, got {w!r}")
+    return out
+
+
+def rans_encode_dev(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor], out: Optional[RansEncoded] = None, lanes=None) -> RansEncoded:
     """The coder's byte streams made on the device (mcq_rans_encode_dev + mcq_rans_pack_dev: three launches for all levels and images,
     nothing read by the host, so the call captures): `codes[l]` int64 [n, m_l, h_l, w_l] under `cdfs[l]` uint32 [m_l, k_l + 1] (the
     tables of `pmf_to_quantized_cdf_dev`) -> (blob, offsets, status).  Stream s = i * levels + l (image-major) is
@@ -1323,8 +1344,12 @@ def rans_encode_dev(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor],
     of it mean anything.  `status` int32 [n * levels]: RANS_OK, or RANS_BAD_SYMBOL where a code lay outside [0, k_l) or met an empty
     bin -- the host coder's RuntimeError -- and then the stream's size is 0.  The bypass digits of the host coder are not implemented:
     no code in [0, k) reaches them.  `out`: the result of an earlier call with codes of these shapes (its buffers are written in place:
-    a captured launch keeps their addresses), or None for fresh ones."""
+    a captured launch keeps their addresses), or None for fresh ones.
+    `lanes`: None for the layout above; "auto", a power of two <= 64, or one of either per level for the lane-interleaved layout
+    (mcq_rans_lanes_encode_dev, csrc/rans_lanes.hip: one wave per stream, the same pack launches) -- byte for byte the host lanes coder's
+    streams; the blob's worst case is then 4 (1 + 2 * 64) bytes per stream larger.  `out` must come from a call of the same layout."""
     who = "rans_encode_dev"
+    widths = None if lanes is None else rans_lanes_widths(lanes, len(codes), who)
     cs = [_dev(c.detach(), "codes", torch.int64) for c in codes]
     ts = [_dev(t, "cdf", torch.uint32) for t in cdfs]
     levels = len(cs)
@@ -1336,12 +1361,13 @@ def rans_encode_dev(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor],
     n, ms, ks, hws = _rans_levels([tuple(c.shape) for c in cs], ts, who)
     counts = [m * hw for m, hw in zip(ms, hws)]
     streams = n * levels
-    cap = 4 * max(counts) + 64                               # per-stream slot, the host coder's own allowance (4 (count + 2) is the bound)
-    key = (n, tuple(tuple(c.shape[1:]) for c in cs), dev)
+    head = 0 if widths is None else RANS_LANES_HEAD          # a lanes stream's prefix and state words at the widest W
+    cap = 4 * max(counts) + 64 + head                        # per-stream slot, the host coder's own allowance (4 (count + 2) is the bound)
+    key = (n, tuple(tuple(c.shape[1:]) for c in cs), dev) + (() if widths is None else ("lanes",))
     if out is None:
         meta = torch.empty(RansEncoded.meta_words(streams), dtype=torch.int64, device=dev)
         offsets, sizes, status = RansEncoded.split(meta, streams)
-        out = RansEncoded(torch.empty(n * sum(4 * c + 8 for c in counts), dtype=torch.uint8, device=dev), offsets, status, sizes,
+        out = RansEncoded(torch.empty(n * sum(4 * c + 8 + head for c in counts), dtype=torch.uint8, device=dev), offsets, status, sizes,
                           torch.empty(streams * cap, dtype=torch.uint8, device=dev), meta, key)
     elif not isinstance(out, RansEncoded) or out.key != key:
         raise ValueError(f"{who}: `out` must be the result of an earlier call with codes of these shapes on {dev} (it is written in place)")
@@ -1351,6 +1377,13 @@ def rans_encode_dev(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor],
         for l0 in range(0, levels, limit):
             sl = slice(l0, min(levels, l0 + limit))
             nl = sl.stop - l0
+            if widths is not None:
+                check(lib.mcq_rans_lanes_encode_dev((ctypes.c_void_p * nl)(*[c.data_ptr() for c in cs[sl]]),
+                                                    (ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts[sl]]), (ctypes.c_int32 * nl)(*ms[sl]),
+                                                    (ctypes.c_int32 * nl)(*ks[sl]), (ctypes.c_int32 * nl)(*hws[sl]), (ctypes.c_int32 * nl)(*widths[sl]),
+                                                    nl, n, l0, levels, _ptr(out.scratch), cap, _ptr(out.sizes), _ptr(out.status), _stream()),
+                      "mcq_rans_lanes_encode_dev")
+                continue
             check(lib.mcq_rans_encode_dev((ctypes.c_void_p * nl)(*[c.data_ptr() for c in cs[sl]]), (ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts[sl]]),
                                           (ctypes.c_int32 * nl)(*ms[sl]), (ctypes.c_int32 * nl)(*ks[sl]), (ctypes.c_int32 * nl)(*hws[sl]), nl, n, l0,
                                           levels, _ptr(out.scratch), cap, _ptr(out.sizes), _ptr(out.status), _stream()), "mcq_rans_encode_dev")
@@ -1359,13 +1392,15 @@ def rans_encode_dev(codes: Sequence[torch.Tensor], cdfs: Sequence[torch.Tensor],
     return out
 
 
-def rans_decode_dev(blob: torch.Tensor, offsets: torch.Tensor, cdfs: Sequence[torch.Tensor], shapes: Sequence[Sequence[int]], out=None):
+def rans_decode_dev(blob: torch.Tensor, offsets: torch.Tensor, cdfs: Sequence[torch.Tensor], shapes: Sequence[Sequence[int]], out=None, lanes: bool = False):
     """The inverse, in ONE launch (mcq_rans_decode_dev): stream s = i * levels + l is blob[offsets[s] : offsets[s + 1]] (`blob` uint8,
     `offsets` int64 [n * levels + 1], both on the device) and decodes under `cdfs[l]` straight into int64 [n, m_l, h_l, w_l] --
     `shapes[l]`.  Returns (codes, status): `status` int32 [n * levels] is RANS_OK, or RANS_BAD_STREAM for a stream that is shorter than 8
     bytes, not a multiple of 4 long, lies outside the blob, or runs out of words -- the host coder's "truncated or malformed" -- and
     that stream's codes are ZERO; the others decode.  The streams are untrusted input and no content of `blob` or `offsets` leads to a
-    read outside them.  `out`: the (codes, status) of an earlier call with these shapes, written in place, or None for fresh ones."""
+    read outside them.  `out`: the (codes, status) of an earlier call with these shapes, written in place, or None for fresh ones.
+    `lanes`: True when the streams are lane-interleaved (mcq_rans_lanes_decode_dev): each stream's width comes from its own prefix, and
+    a stream without that prefix -- a plain one among them -- is RANS_BAD_STREAM like any other malformed stream."""
     who = "rans_decode_dev"
     blob = _dev(blob, "blob", torch.uint8)
     offsets = _dev(offsets, "offsets", torch.int64)
@@ -1395,10 +1430,10 @@ def rans_decode_dev(blob: torch.Tensor, offsets: torch.Tensor, cdfs: Sequence[to
         for l0 in range(0, levels, limit):
             sl = slice(l0, min(levels, l0 + limit))
             nl = sl.stop - l0
-            check(lib.mcq_rans_decode_dev(_ptr(blob), nbytes, _ptr(offsets), (ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts[sl]]),
-                                          (ctypes.c_int32 * nl)(*ms[sl]), (ctypes.c_int32 * nl)(*ks[sl]), (ctypes.c_int32 * nl)(*hws[sl]), nl, n, l0,
-                                          levels, (ctypes.c_void_p * nl)(*[c.data_ptr() for c in codes[sl]]), _ptr(status), _stream()),
-                  "mcq_rans_decode_dev")
+            entry = "mcq_rans_lanes_decode_dev" if lanes else "mcq_rans_decode_dev"       # (one argument list for both)
+            check(getattr(lib, entry)(_ptr(blob), nbytes, _ptr(offsets), (ctypes.c_void_p * nl)(*[t.data_ptr() for t in ts[sl]]),
+                                      (ctypes.c_int32 * nl)(*ms[sl]), (ctypes.c_int32 * nl)(*ks[sl]), (ctypes.c_int32 * nl)(*hws[sl]), nl, n, l0,
+                                      levels, (ctypes.c_void_p * nl)(*[c.data_ptr() for c in codes[sl]]), _ptr(status), _stream()), entry)
     return codes, status
 
 

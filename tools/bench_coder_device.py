@@ -5,7 +5,9 @@ process and under the same tables, at the qp=2 shape m = 2, k = [8192, 2048, 512
 Every arm starts from codes (or bytes) where its caller has them -- codes on the device, bytes on the host -- and ends with bytes on the
 host (or codes on the device), so copies and synchronisations are inside the window: wall time around a call that ends in a device
 synchronise, after a warm-up, median of `--reps`; for the device arms also the device time alone from events around 10 calls.  The
-bytes of the two sides are compared before anything is timed.  Prints one JSON document (and writes it to --out).
+bytes of the two sides are compared before anything is timed.  Section 33's columns follow in the same process and protocol: the
+lane-interleaved layout on the host (`compress(codes, lanes="auto")`), on the device at auto and on the device forced to 64 lanes
+(csrc/rans_lanes.hip), with each arm's bytes over the plain streams' bytes.  Prints one JSON document (and writes it to --out).
 
     python tools/bench_coder_device.py [--reps 15] [--out FILE]"""
 import argparse
@@ -73,6 +75,22 @@ for name, (n, height, width) in SHAPES.items():
            "decompress_host": wall(lambda: coder.decompress(binaries, sizes), args.reps),
            "decompress_device_from_bytes": wall(lambda: coder.decompressDevice(binaries, sizes), args.reps),
            "decompress_device_kernel_event_ms": events(lambda: coder.decompressDevice(streams, sizes, check=False))}
+    # the lanes layout (section 30): the host lanes coder, the device at auto and the device forced to 64, same protocol; sizes beside
+    lanes_host, _ = coder.compress(codes, lanes="auto")
+    for tag, lanes in (("auto", "auto"), ("64", 64)):
+        dev_streams = coder.compressDevice(codes, lanes=lanes)
+        lanes_bytes = dev_streams.tobytes()
+        assert lanes_bytes == coder.compress(codes, lanes=lanes)[0], "the device lanes coder's bytes differ from the host lanes coder's"
+        assert all(torch.equal(a, b) for a, b in zip(coder.decompressDevice(lanes_bytes, sizes, lanes=True), codes))
+        row[f"lanes_{tag}"] = {
+            "widths": [int(b[3]) for b in lanes_bytes[0]], "bytes": sum(len(b) for binary in lanes_bytes for b in binary),
+            "size_over_plain": sum(len(b) for binary in lanes_bytes for b in binary) / row["bytes"],
+            "compress_device_tobytes": wall(lambda: coder.compressDevice(codes, lanes=lanes).tobytes(), args.reps),
+            "compress_device_kernels_event_ms": events(lambda: coder.compressDevice(codes, out=dev_streams, lanes=lanes)),
+            "decompress_device_from_bytes": wall(lambda: coder.decompressDevice(lanes_bytes, sizes, lanes=True), args.reps),
+            "decompress_device_kernel_event_ms": events(lambda: coder.decompressDevice(dev_streams, sizes, check=False, lanes=True))}
+    row["lanes_host_auto"] = {"compress_host": wall(lambda: coder.compress(codes, lanes="auto"), args.reps),
+                              "decompress_host": wall(lambda: coder.decompress(lanes_host, sizes, lanes=True), args.reps)}
     out[name] = row
     print(name, json.dumps(row), flush=True)
 if args.out:
