@@ -281,6 +281,29 @@ int mcq_rate_search_step(const double* bits, const double* target, float* lam, f
                          float* trace_lam /* or NULL */, double* trace_bpp /* or NULL */, int32_t n, int32_t levels, double pixels,
                          float lambda_max, int32_t trial, int32_t trials, void* stream);
 
+/* ---- adaptive quantisation: a rate map made from the image (csrc/rate_activity.hip) ---- */
+/* x float32 [n, 3, H, W] (contiguous) -> a float32 [n, h0, w0], (h0, w0) = the image reflect-padded to multiples of `base` (a multiple
+ * of 16; padTop = hPad / 2, padLeft = wPad / 2, read in place through the reflected index) in 16 x 16 cells.  Per pixel
+ * Y = fmaf(0.114f, B, fmaf(0.587f, G, 0.299f * R)); per cell, in two passes, mu = sum Y / 256, v = sum (Y - mu)^2 / 256 (both sums
+ * balanced trees of depth 8 in a fixed order), a = log2f(v + 0x1p-14f).  A cell with a non-finite luma (or an overflowing v) gets a = 0,
+ * mask = 1 (mask int32 [n, h0, w0], written 0 or 1) and sets error[image] = 1 (error int32 [n], zeroed on the stream by every call).  No
+ * atomics, no host read; equal images give equal bits wherever they stand in the batch.  MCQ_EINVAL before any launch for a NULL
+ * pointer, a non-positive size, a base that is no multiple of 16, or padding that reflect cannot make (a side's padding must be smaller
+ * than the image's side). */
+int mcq_activity_cells_f32(const float* x, int32_t n, int32_t H, int32_t W, int32_t base, float* a, int32_t* mask, int32_t* error,
+                           void* stream);
+
+/* The map of one use from the cell activities, one workgroup per image: abar = the mean of `a` over the image's unmasked cells (double
+ * sums of consecutive row-major runs added in run order, one division, one rounding to float32; 0 when every cell is masked),
+ * e = clamp(strength * (a - abar), -clip, +clip), w = exp2f(e), 1 for a masked cell; out[i, y, x] = (w * roi) * lam[i].  `roi` (or NULL
+ * = 1): the caller's own map at roi[i * stride_n + y * stride_y + x * stride_x], element strides >= 0 ((1, 0, 0): one value per image);
+ * a negative, NaN or infinite value is written as NaN, which mcq_rate_map_levels_f32 counts as 0 and reports.  `lam` (or NULL = 1):
+ * float32 [n] on the device.  MCQ_EINVAL before any launch for a NULL a / mask / out, a non-positive size, a strength that is not finite
+ * and >= 0, a clip that is not finite and > 0, or a negative stride. */
+int mcq_activity_weights_f32(const float* a, const int32_t* mask, int32_t n, int32_t h0, int32_t w0, float strength, float clip,
+                             const float* roi /* or NULL */, int64_t stride_n, int64_t stride_y, int64_t stride_x,
+                             const float* lam /* or NULL */, float* out, void* stream);
+
 /* out[n, g*d + j, y, x] = codebook[g, codes[n, g, y, x], j]
  * (mcquic/modules/quantizer.py:249-259 _multiCodebookDeQuantization.decode).
  * Returns MCQ_OK; indices outside [0, k) are clamped (the reference would raise IndexError). */

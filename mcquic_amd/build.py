@@ -18,7 +18,7 @@ LIB = os.path.join(HERE, "libmcquic_hip.so")
 # conv_mfma_kernel's instances are spread over conv_tiles_*.hip / conv_wino32.hip (build section, has their compile
 # times); conv_launch.hip and conv_pack.hip hold none, so an edit to the launcher or the pack layout rebuilds in seconds.
 SOURCES = ["conv_tiles_128.hip", "conv_wino32.hip", "conv_tiles_41.hip", "conv_tiles_32.hip", "conv_tiles_64.hip", "conv_launch.hip",
-           "conv_pack.hip", "conv_wino16.hip", "vq.hip", "vq_rate_map.hip", "vq_kmeans.hip", "vq_reassign.hip", "vq_cdf.hip", "vq_train.hip", "vq_bwd_mfma.hip", "codebook_cos.hip", "train_ops.hip", "adam.hip",
+           "conv_pack.hip", "conv_wino16.hip", "vq.hip", "vq_rate_map.hip", "rate_activity.hip", "vq_kmeans.hip", "vq_reassign.hip", "vq_cdf.hip", "vq_train.hip", "vq_bwd_mfma.hip", "codebook_cos.hip", "train_ops.hip", "adam.hip",
            "lamb.hip", "sgd.hip", "ema.hip", "schedule.hip", "step_guard.hip", "step_ops.hip", "step_meter.hip", "param_stats.hip", "step_snapshot.hip", "wgrad_rows.hip", "metrics.hip", "msssim_loss.hip", "norm.hip", "augment.hip", "rans.cpp", "rans_dev.hip", "rans_lanes.hip"]
 # -ffp-contract=off: element-wise epilogues keep the reference's one-rounding-per-op sequence
 #   (e.g. a * sigmoid(b) then + x are two torch kernels in mcquic/nn/blocks.py:286-287).

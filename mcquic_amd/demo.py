@@ -1,6 +1,6 @@
 """Single-image compress / restore on the HIP path (reference: mcquic/demo.py:35-134, mcquic/cli.py:40-61).
 
-    python -m mcquic_amd [-qp N] [--local model.mcquic] [--crop] INPUT [OUTPUT]
+    python -m mcquic_amd [-qp N] [--local model.mcquic] [--crop] [--rd-lambda F | --target-bpp F] [--aq F [--aq-clip F]] INPUT [OUTPUT]
 
 INPUT an image (.png/.jpg/.jpeg) -> compress to a `.mcq` document; INPUT a `.mcq` document -> restore to .png.
 Differences from the reference CLI, all forced by this environment: there is no network, so a model is either a
@@ -58,15 +58,26 @@ def detectLocalFile(qp: str):
     return None
 
 
-def compressImage(image: torch.Tensor, model: Compressor, crop: bool) -> File:
-    """uint8 [c, h, w] -> File (reference: demo.py:109-122)."""
+def compressImage(image: torch.Tensor, model: Compressor, crop: bool, rd_lambda=None, target_bpp=None, aq=None, say=None) -> File:
+    """uint8 [c, h, w] -> File (reference: demo.py:109-122).  `rd_lambda`, `aq`: `Compressor.compress`'s rate knobs; `target_bpp`: the
+    lambda comes from `Compressor.encode_to_rate` (under `aq` when given), whose answer -- the lambda and the bits per pixel the coder's
+    tables charge, at or below the target -- goes to `say`; the file's own bpp, printed after, also counts the header and the coder's
+    flush bytes."""
     image = image.to(torch.float32) / 255.0                            # convert_image_dtype for uint8 inputs
     if crop:
         h, w = image.shape[-2] // 128 * 128, image.shape[-1] // 128 * 128
         top, left = (image.shape[-2] - h) // 2, (image.shape[-1] - w) // 2
         image = image[..., top:top + h, left:left + w]                # AlignedCrop, data/transforms.py:57-78
     image = (image - 0.5) * 2
-    _, binaries, headers = model.compress(image[None, ...].contiguous())
+    x = image[None, ...].contiguous()
+    if target_bpp is not None:
+        _, rd_lambda, bpp = model.encode_to_rate(x, target_bpp, aq=aq)
+        if say is not None:
+            say(f"target {target_bpp:.4f} bpp: lambda {rd_lambda:.6g}, {bpp:.4f} bpp by the coder's tables")
+    if rd_lambda is None and aq is None:
+        _, binaries, headers = model.compress(x)
+    else:
+        _, binaries, headers = model.compress(x, rd_lambda=rd_lambda, aq=aq)
     return File(headers[0], binaries[0])
 
 
@@ -77,15 +88,35 @@ def decompressImage(sourceFile: File, model: Compressor) -> torch.Tensor:
     return ops.detransform(restored[0].contiguous())
 
 
-def main(argv=None) -> int:
+def parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(prog="mcquic_amd", description="Compress / restore a file on MI355X.")
     ap.add_argument("-qp", type=int, default=2, choices=range(0, 14), metavar="[0-13]")
     ap.add_argument("--local", type=pathlib.Path, default=None, help="local model checkpoint")
     ap.add_argument("--crop", action="store_true", help="crop to multiples of 128 instead of padding")
+    rate = ap.add_argument_group("rate control (compressing only; a .mcq restores without them)")
+    rate.add_argument("--rd-lambda", type=float, default=None, metavar="F", help="entropy-constrained assignment: distance + F * bits")
+    rate.add_argument("--target-bpp", type=float, default=None, metavar="F", help="search the lambda that brings the codes to F bits per pixel")
+    rate.add_argument("--aq", type=float, default=None, metavar="F", help="adaptive quantisation of strength F: lambda follows the local activity")
+    rate.add_argument("--aq-clip", type=float, default=None, metavar="F", help="clip of the --aq exponent (default 2: weights in [1/4, 4])")
     ap.add_argument("-q", "--quiet", action="store_true")
     ap.add_argument("input", type=pathlib.Path)
     ap.add_argument("output", type=pathlib.Path, nargs="?")
-    a = ap.parse_args(argv)
+    return ap
+
+
+def rateOptions(a: argparse.Namespace) -> dict:
+    """The rate keywords of `compressImage` from the parsed command line; ValueError for combinations that mean nothing."""
+    if a.rd_lambda is not None and a.target_bpp is not None:
+        raise ValueError("--rd-lambda and --target-bpp exclude each other: the search chooses the lambda")
+    if a.aq_clip is not None and a.aq is None:
+        raise ValueError("--aq-clip needs --aq")
+    aq = None if a.aq is None else a.aq if a.aq_clip is None else (a.aq, a.aq_clip)
+    return dict(rd_lambda=a.rd_lambda, target_bpp=a.target_bpp, aq=aq)
+
+
+def main(argv=None) -> int:
+    a = parser().parse_args(argv)
+    rate = rateOptions(a)
     if not torch.cuda.is_available():
         print("mcquic_amd needs a HIP device (the kernels have no CPU fallback)", file=sys.stderr)
         return 2
@@ -96,7 +127,7 @@ def main(argv=None) -> int:
             from PIL import Image
             model = loadModel(a.qp, a.local, device)
             image = torch.from_numpy(np.array(Image.open(a.input).convert("RGB"))).permute(2, 0, 1).to(device)
-            target = compressImage(image, model, a.crop)
+            target = compressImage(image, model, a.crop, say=say, **rate)
             raw = a.input.stat().st_size
             say(f"{target.FileHeader.ImageSize} -> {target.size(True)}, {target.BPP:.4f} bpp "
                 f"({raw} B => {target.size()} B, compression ratio {(raw - target.size()) / raw * 100:.2f}%)")

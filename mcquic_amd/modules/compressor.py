@@ -255,7 +255,58 @@ class BaseCompressor(nn.Module):
             y = self._encoder[i](y)
         return y
 
-    def encode(self, x: torch.Tensor, rd_lambda=None, rd_map=None) -> List[torch.Tensor]:
+    AQ_CLIP = 2.0                    # the clip of a bare `aq` strength: w in [1/4, 4]
+
+    def _aqArgs(self, aq):
+        """`aq` of encode / compress / encode_to_rate checked before any device work: None, or (strength, clip) as the float32 values
+        the kernel takes -- a bare float means clip = AQ_CLIP.  ValueError unless strength is finite and >= 0 and clip finite and > 0."""
+        if aq is None:
+            return None
+        from .. import ops
+        pair = tuple(aq) if isinstance(aq, (list, tuple)) else (aq, self.AQ_CLIP)
+        try:
+            if len(pair) != 2 or any(isinstance(v, bool) or torch.is_tensor(v) and v.dim() > 0 for v in pair):
+                raise TypeError
+            strength, clip = ops.lambda_f32(pair[0]), ops.lambda_f32(pair[1])
+        except (TypeError, ValueError):
+            raise ValueError(f"aq: a strength >= 0, or (strength, clip) with clip > 0, finite float32 values; got {aq!r}") from None
+        if not (clip > 0.0):
+            raise ValueError(f"aq: clip must be > 0, got {aq!r}")
+        return strength, clip
+
+    def _aqMap(self, x: torch.Tensor, aq: tuple, rd_map=None) -> torch.Tensor:
+        """The effective map float32 [n, h0, w0] of a call with `aq` = (strength, clip) (checked): w, or w * rd_map -- two eager launches
+        (`ops.activity_cells`, `ops.activity_weights`) in front of the encoder, nothing read on the host.  The activity error word of
+        the call is kept for `activityError()`."""
+        from .. import ops
+        a, mask, self.__dict__["_aqErr"] = ops.activity_cells(x, self._padding._base)
+        return ops.activity_weights(a, mask, aq[0], aq[1], roi=rd_map)
+
+    def activityWeights(self, x: torch.Tensor, aq) -> torch.Tensor:
+        """The adaptive-quantisation map of `x` alone: float32 [n, h0, w0] on the level-0 code grid, what `encode(x, aq=aq)` multiplies
+        lambda by.  Per 16 x 16 cell of the aligned image a = log2(variance of the luma + 2^-14), the variance centred (two passes);
+        w = 2^clamp(strength (a - mean a), -clip, +clip): above 1 (fewer bits) where texture masks the error, below 1 where the picture
+        is flat, geometric mean 1 over an image while nothing clips.  `aq`: a strength >= 0, or (strength, clip); a bare strength takes
+        clip = 2 (w in [1/4, 4]) -- a design choice that nothing here could tune: there is no trained checkpoint to tune it on."""
+        aq = self._aqArgs(aq)
+        if aq is None:
+            raise ValueError("activityWeights: `aq` must be a strength or (strength, clip)")
+        self._quantizer.rateLambdas(1.0)                     # (a quantizer without tables refuses here)
+        self._check(x)
+        if x.shape[0] == 0:
+            raise ValueError("aq: an empty batch has no map")
+        with torch.no_grad():
+            return self._aqMap(x, aq)
+
+    def activityError(self) -> torch.Tensor:
+        """int32 [n] on the device, from the last call with `aq`: 1 where an image held a cell with a non-finite luma (that cell took
+        w = 1).  Nothing is read on the host."""
+        err = self.__dict__.get("_aqErr")
+        if err is None:
+            raise RuntimeError("activityError: no call with `aq` has run yet")
+        return err
+
+    def encode(self, x: torch.Tensor, rd_lambda=None, rd_map=None, aq=None) -> List[torch.Tensor]:
         """`rd_lambda`: None = nearest codeword; a float >= 0 (or one per level) = the entropy-constrained assignment
         argmin_k (distance + lambda * bits_k) under the coder's current tables (`UMGMQuantizer.encode`): one model, a continuous
         rate knob; `decode` / `decompress` and the stream format do not know about it.  Inside a caller's own stream capture
@@ -265,12 +316,19 @@ class BaseCompressor(nn.Module):
         `rd_map`: rate control per image ([n]) or per level-0 code cell ([n, H / 16, W / 16] of the 128-aligned image), a float32
         device tensor; `rd_lambda` is then the per-level scale (`UMGMQuantizer.encode`).  The map is an operand: under `enableGraphs`
         one capture per image shape and map form serves every map and every scale; inside a caller's capture it works once a call
-        outside it has made the tables' bits sections."""
-        lams, empty = self._rateArgs(x, rd_lambda, rd_map)
+        outside it has made the tables' bits sections.
+        `aq`: adaptive quantisation, None (off) or a strength >= 0 or (strength, clip) (`activityWeights`): the map w made from the image
+        on the device becomes the effective map, w * rd_map with a map given, w alone without; `rd_lambda` stays the per-level scale.
+        The two launches that make it run eagerly in front of the `rd_map` path, whose capture it shares (the key is the map's shape)."""
+        aq = self._aqArgs(aq)
+        lams, empty = self._rateArgs(x, rd_lambda, rd_map, aq)
         if empty:
             # an empty shard (fewer images than ranks, parallel.shard_range): PyTorch's layers hand back empty tensors of the
             # right geometry (the reference's behaviour); the kernels refuse empty launches, so the geometry comes from one blank image
             return [c[:0] for c in self.encode(x.new_zeros((1,) + tuple(x.shape[1:])), rd_lambda=lams)]
+        if aq is not None:
+            with torch.no_grad():
+                rd_map = self._aqMap(x, aq, rd_map)
         if rd_map is not None:
             return self._encodeRateMap(x, lams, rd_map)
         if lams is not None:
@@ -280,19 +338,24 @@ class BaseCompressor(nn.Module):
                 return self._graphed("encode", lambda t: self._quantizer.encode(self._encode_latent(t)), [x.contiguous()])
             return self._quantizer.encode(self._encode_latent(x))
 
-    def _rateArgs(self, x: torch.Tensor, rd_lambda, rd_map):
+    def _rateArgs(self, x: torch.Tensor, rd_lambda, rd_map, aq=None):
         """The arguments of `encode` / `compress` checked, in this order, before any device work: `rd_lambda` (`rateLambdas`: quantizers
         without tables refuse first), the image batch, the map against its level-0 code grid.  Returns (lams, empty): lams = None for
         the plain path, the lambdas of the scalar knob, or with a map the per-level scales (None = 1); empty: a batch of no images (with
-        a map that raises: it has no batch to belong to)."""
+        a map that raises: it has no batch to belong to).  `aq` (already checked, `_aqArgs`) makes a map, so it counts as one."""
         lams = None
-        if rd_lambda is not None or rd_map is not None:
+        if rd_lambda is not None or rd_map is not None or aq is not None:
             lams = self._quantizer.rateLambdas(1.0 if rd_lambda is None else rd_lambda)
         self._check(x)
         if rd_map is not None:
             self._quantizer.checkRateMap(rd_map, *self._rateGrid(x), x.device)
         if x.shape[0] == 0 and rd_map is not None:
             raise ValueError("rd_map: an empty batch has no map")
+        if aq is not None:
+            from .. import ops
+            if x.shape[0] == 0:
+                raise ValueError("aq: an empty batch has no map")
+            ops.activity_grid(x.shape[-2], x.shape[-1], self._padding._base)      # (padding that reflect cannot make: refused here)
         return lams, x.shape[0] == 0
 
     def _replays(self, t: torch.Tensor) -> bool:
@@ -364,7 +427,7 @@ class BaseCompressor(nn.Module):
         return self._quantizer.rateMapError()
 
     def encode_to_rate(self, x: torch.Tensor, target_bpp, iters: int = 12, lambda_max: float = 64.0, per_image: bool = False,
-                       trace: bool = False):
+                       trace: bool = False, aq=None, rd_map=None):
         """Codes of `x` that the coder's tables charge at most `target_bpp` bits per pixel for, by a search over ONE lambda for the
         whole batch: returns (codes, lam, bpp) with bpp = codeBits(codes).sum() / (n h w) <= target_bpp.  The image-side encoder runs
         once; each of the at most `iters` + 2 trials re-runs the quantizer cascade only and reads one number back (so the search runs
@@ -372,12 +435,26 @@ class BaseCompressor(nn.Module):
         lam = 0.  Then `lambda_max`: if even that misses, ValueError names the bpp it reached.  Then the bracket (0, lambda_max] is
         narrowed `iters` times -- a sixteenth of the upper end while the lower end is still 0 (the useful lambdas span decades and
         depend on the latents' scale), the geometric mean after -- and the smallest lambda visited that met the target is returned.
-        Rate is not strictly monotone in lambda below level 0 (a level's residual depends on the level above), hence "visited"."""
+        Rate is not strictly monotone in lambda below level 0 (a level's residual depends on the level above), hence "visited".
+        `aq`, `rd_map`: the search runs over a spatial map -- `aq` as for `encode` (the map w made from the image, once), `rd_map` the
+        caller's own ([n] or [n, h0, w0]); the effective map is w * rd_map (w = 1 without `aq`).  The batch form then tries
+        `encode(x, rd_lambda=lambda, rd_map=w * rd_map)` and what it returns reproduces through `encode(x, rd_lambda=lam, aq=aq,
+        rd_map=rd_map)`; the per-image form makes every trial's map (w * rd_map) * lam[n] with one `ops.activity_weights` launch, `lam`
+        the multiplier the search is over, and still reads nothing on the host.  With neither, the code path is the one without maps."""
         from .. import ops
+        aq = self._aqArgs(aq)
         self._quantizer.rateLambdas(0.0)                     # (a quantizer without tables refuses here)
         self._check(x)
+        cells = None
+        if aq is not None or rd_map is not None:
+            if rd_map is not None:
+                self._quantizer.checkRateMap(rd_map, *self._rateGrid(x), x.device)
+            if x.shape[0] == 0:
+                raise ValueError("encode_to_rate: an empty batch has no rate")
+            ops.activity_grid(x.shape[-2], x.shape[-1], self._padding._base)
+            cells = (0.0, self.AQ_CLIP) if aq is None else aq          # (a map without `aq`: strength 0, w = 1)
         if per_image:
-            return self._encodeToRatePerImage(x, target_bpp, int(iters), lambda_max, bool(trace))
+            return self._encodeToRatePerImage(x, target_bpp, int(iters), lambda_max, bool(trace), cells, rd_map)
         target, iters = float(target_bpp), int(iters)
         lambda_max = ops.lambda_f32(lambda_max)
         if not (target > 0.0) or not (lambda_max > 0.0) or iters < 0:
@@ -389,10 +466,14 @@ class BaseCompressor(nn.Module):
             raise RuntimeError("encode_to_rate reads the rate back every trial: it cannot be captured")
         pixels = float(x.shape[0] * x.shape[-2] * x.shape[-1])
         with torch.no_grad():
+            wmap = None if cells is None else self._aqMap(x, cells, rd_map)
             y = self._encode_latent(x)
 
             def trial(lam: float):
-                codes = self._quantizer.encode(y) if lam == 0.0 else self._quantizer.encode(y, rd_lambda=lam)
+                if wmap is not None:
+                    codes = self._quantizer.encode(y, rd_lambda=lam, rd_map=wmap)
+                else:
+                    codes = self._quantizer.encode(y) if lam == 0.0 else self._quantizer.encode(y, rd_lambda=lam)
                 return codes, float(self.codeBits(codes).sum()) / pixels
 
             codes, bpp = trial(0.0)
@@ -413,7 +494,7 @@ class BaseCompressor(nn.Module):
                     lo = mid
         return best[0], hi, best[1]
 
-    def _encodeToRatePerImage(self, x: torch.Tensor, target_bpp, iters: int, lambda_max, trace: bool):
+    def _encodeToRatePerImage(self, x: torch.Tensor, target_bpp, iters: int, lambda_max, trace: bool, aq=None, roi=None):
         """`encode_to_rate(per_image=True)`: every image is brought to ITS target by its own lambda, the search's state on the device.
         `target_bpp`: a float, or a device tensor [n].  The image-side encoder runs once; then `iters` + 2 lockstep trials of the
         quantizer cascade with rd_map = lambda[n], each followed by `codeBits` and one `ops.rate_search_step` launch; then the final
@@ -423,7 +504,10 @@ class BaseCompressor(nn.Module):
         Nothing is read on the host: with the bits sections made beforehand (any `encode(x, rd_map=...)` outside) the whole call
         captures into a caller's graph.  Returns (codes, lam float32 [n], bpp float64 [n]) on the device, bpp = the final run's
         codeBits summed over the levels / (H W); an unreachable target does not raise: the image ends at `lambda_max` and its bpp
-        shows it.  `trace`: also (lams float32, bpps float64) [trials, n], what every trial ran at and reached."""
+        shows it.  `trace`: also (lams float32, bpps float64) [trials, n], what every trial ran at and reached.
+        `aq` = (strength, clip) (checked), `roi`: the spatial form -- the cell activities are made once, every trial's map
+        (w * roi) * lam[n] by one `ops.activity_weights` launch into one buffer, and the cascade runs with that map; the search's state,
+        its step and the return values are the same, `lam` now the per-image multiplier of the map."""
         from .. import ops
         lambda_max = ops.lambda_f32(lambda_max)
         if not (lambda_max > 0.0) or iters < 0:
@@ -451,26 +535,35 @@ class BaseCompressor(nn.Module):
             done = torch.empty(n, dtype=torch.int32, device=dev)
             tlam = torch.empty((trials + 1, n), dtype=torch.float32, device=dev)
             tbpp = torch.empty((trials + 1, n), dtype=torch.float64, device=dev)
+            if aq is not None:
+                a, mask, self.__dict__["_aqErr"] = ops.activity_cells(x, self._padding._base)
+                trial_map = torch.empty_like(a)
             y = self._encode_latent(x)
             for t in range(trials + 1):                       # (the last one is the final run: recorded, nothing decided)
-                codes = self._quantizer.encode(y, rd_map=lam)
+                if aq is None:
+                    codes = self._quantizer.encode(y, rd_map=lam)
+                else:
+                    codes = self._quantizer.encode(y, rd_map=ops.activity_weights(a, mask, aq[0], aq[1], roi=roi, lam=lam, out=trial_map))
                 ops.rate_search_step(self.codeBits(codes), tgt, lam, bracket, done, tlam, tbpp, pixels, lambda_max, t, trials)
         out = (codes, lam, tbpp[trials].clone())
         return out + (tlam[:trials], tbpp[:trials]) if trace else out
 
     def compress(self, x: torch.Tensor, coder: str = "host", rd_lambda=None, rd_map=None,
-                 lanes=None) -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
+                 lanes=None, aq=None) -> Tuple[List[torch.Tensor], List[List[bytes]], List[FileHeader]]:
         """`coder`: "host" (the default) codes the streams with csrc/rans.cpp on host threads, "device" with csrc/rans_dev.hip where
-        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same.  `rd_lambda`, `rd_map`: as for `encode`.
+        the codes are (`EntropyCoder.compressDevice`); the bytes and headers are the same.  `rd_lambda`, `rd_map`, `aq`: as for `encode`.
         `lanes`: None (the default) for the reference's streams; "auto" or a power of two <= 64 for the lane-interleaved layout
         (DESIGN.md section 3), whose streams `decompress(..., lanes=True)` reads -- the same bytes under either coder."""
         self._quantizer._checkCoder(coder)
         layout = self._quantizer._checkLanes(lanes)
-        lams, empty = self._rateArgs(x, rd_lambda, rd_map)
+        aq = self._aqArgs(aq)
+        lams, empty = self._rateArgs(x, rd_lambda, rd_map, aq)
         if empty:                                             # (empty shard: no streams, no headers)
             return self.encode(x), [], []
         n, c, h, w = x.shape
         with torch.no_grad():
+            if aq is not None:
+                rd_map = self._aqMap(x, aq, rd_map)
             codes, binaries, codeSizes = self._quantizer.compress(self._encode_latent(x), coder, rd_lambda=lams, rd_map=rd_map, **layout)
         header = [FileHeader(__version__, self._qp, codeSize, ImageSize(height=h, width=w, channel=c)) for codeSize in codeSizes]
         return codes, binaries, header

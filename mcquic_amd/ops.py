@@ -871,6 +871,77 @@ def rate_search_step(bits: torch.Tensor, target: torch.Tensor, lam: torch.Tensor
               "mcq_rate_search_step")
 
 
+def activity_grid(h: int, w: int, base: int = 128):
+    """(h0, w0): the 16 x 16 cells of an h x w image reflect-padded to multiples of `base` (`AlignedPadding`).  RuntimeError where
+    reflect cannot make that padding -- a side's padding must be smaller than the image's side -- in the words of torch's reflect pad."""
+    h, w, base = int(h), int(w), int(base)
+    if base <= 0 or base % 16 != 0:
+        raise ValueError(f"activity_cells: `base` must be a positive multiple of 16, got {base}")
+    if h <= 0 or w <= 0:
+        raise ValueError(f"activity_cells: an empty image ({h} x {w})")
+    hpad, wpad = (base - h % base) % base, (base - w % base) % base
+    if hpad - hpad // 2 > h - 1 or wpad - wpad // 2 > w - 1:
+        raise RuntimeError(f"activity_cells: Padding size should be less than the corresponding input dimension, but got: padding "
+                           f"({wpad // 2}, {wpad - wpad // 2}) x ({hpad // 2}, {hpad - hpad // 2}) for an image {h} x {w}")
+    return (h + hpad) // 16, (w + wpad) // 16
+
+
+def activity_cells(x: torch.Tensor, base: int = 128):
+    """The activity of every level-0 code cell of an image batch in ONE launch (mcq_activity_cells_f32).  `x`: float32 [n, 3, H, W] on
+    the device.  Returns (a, mask, error): a float32 [n, h0, w0] = log2(variance of the cell's luma + 2^-14) over the 16 x 16 cells of the
+    image reflect-padded to multiples of `base` (read in place, no padded copy; centred two-pass variance); mask int32 [n, h0, w0] = 1
+    where a cell holds a non-finite luma (its `a` is 0); error int32 [n] = 1 for an image with such a cell.  Nothing is read on the host."""
+    who = "activity_cells"
+    if not (torch.is_tensor(x) and x.dim() == 4 and x.shape[1] == 3 and x.shape[0] > 0):
+        raise ValueError(f"{who}: `x` must be a non-empty image batch [n, 3, H, W], got {tuple(x.shape) if torch.is_tensor(x) else type(x).__name__}")
+    x = _dev(x, "x")
+    n, _, h, w = (int(s) for s in x.shape)
+    h0, w0 = activity_grid(h, w, base)
+    a = torch.empty((n, h0, w0), dtype=torch.float32, device=x.device)
+    mask = torch.empty((n, h0, w0), dtype=torch.int32, device=x.device)
+    error = torch.empty(n, dtype=torch.int32, device=x.device)
+    with _guard(x.device):
+        check(_lib.load().mcq_activity_cells_f32(_ptr(x), n, h, w, int(base), _ptr(a), _ptr(mask), _ptr(error), _stream()),
+              "mcq_activity_cells_f32")
+    return a, mask, error
+
+
+def activity_weights(a: torch.Tensor, mask: torch.Tensor, strength: float, clip: float, roi: Optional[torch.Tensor] = None,
+                     lam: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The rate map of one use from `activity_cells`' (a, mask) in ONE launch (mcq_activity_weights_f32): float32 [n, h0, w0] =
+    (w * roi) * lam with w = exp2(clamp(strength * (a - abar), -clip, +clip)), abar the image's mean of `a` over its unmasked cells, w = 1
+    for a masked cell.  `strength` finite >= 0, `clip` finite > 0.  `roi`: None (1), or a float32 device tensor [n] or [n, h0, w0], any
+    view with non-negative strides -- a negative, NaN or infinite value comes out as NaN, which `rate_map_levels` counts as 0 and reports.
+    `lam`: None (1) or float32 [n] on the device (the multiplier of the per-image search).  `out`: the caller's buffer, written in place."""
+    who = "activity_weights"
+    if not (torch.is_tensor(a) and a.is_cuda and a.dtype == torch.float32 and a.dim() == 3 and a.numel() > 0 and a.is_contiguous()):
+        raise ValueError(f"{who}: `a` must be a non-empty contiguous float32 device tensor [n, h0, w0]")
+    dev, (n, h0, w0) = a.device, (int(s) for s in a.shape)
+    if not (torch.is_tensor(mask) and mask.device == dev and mask.dtype == torch.int32 and mask.shape == a.shape and mask.is_contiguous()):
+        raise ValueError(f"{who}: `mask` must be contiguous int32 {tuple(a.shape)} on {dev}")
+    strength, clip = ctypes.c_float(float(strength)).value, ctypes.c_float(float(clip)).value
+    if not (strength >= 0.0) or math.isinf(strength) or not (clip > 0.0) or math.isinf(clip):
+        raise ValueError(f"{who}: `strength` must be a finite float32 >= 0 and `clip` a finite float32 > 0, got {strength!r}, {clip!r}")
+    strides = (0, 0, 0)
+    if roi is not None:
+        if not (torch.is_tensor(roi) and roi.device == dev and roi.dtype == torch.float32 and tuple(roi.shape) in ((n,), (n, h0, w0))):
+            raise ValueError(f"{who}: `roi` must be a float32 tensor [{n}] or [{n}, {h0}, {w0}] on {dev}")
+        if any(int(s) < 0 for s in roi.stride()):
+            raise ValueError(f"{who}: negative strides")
+        strides = (roi.stride(0), 0, 0) if roi.dim() == 1 else tuple(roi.stride())
+    if lam is not None and not (torch.is_tensor(lam) and lam.device == dev and lam.dtype == torch.float32 and tuple(lam.shape) == (n,)
+                                and lam.is_contiguous()):
+        raise ValueError(f"{who}: `lam` must be {n} contiguous float32 values on {dev}")
+    if out is None:
+        out = torch.empty((n, h0, w0), dtype=torch.float32, device=dev)
+    elif not (torch.is_tensor(out) and out.device == dev and out.dtype == torch.float32 and out.shape == a.shape and out.is_contiguous()):
+        raise ValueError(f"{who}: `out` must be contiguous float32 {tuple(a.shape)} on {dev}")
+    with _guard(dev):
+        check(_lib.load().mcq_activity_weights_f32(_ptr(a), _ptr(mask), n, h0, w0, strength, clip, _ptr(roi), int(strides[0]), int(strides[1]),
+                                                   int(strides[2]), _ptr(lam), _ptr(out), _stream()), "mcq_activity_weights_f32")
+    return out
+
+
 def vq_gather(codes: torch.Tensor, cb: PackedCodebook, dual_silu: bool = False) -> torch.Tensor:
     """fp32 [n, m*d, h, w] = codebook[g, codes] (mcq_vq_gather_f32)."""
     codes = _dev(codes, "codes", torch.int64)

@@ -98,27 +98,31 @@ def validate(model, images: torch.Tensor, group=None, msssim: bool = True, gathe
 
 
 @torch.inference_mode()
-def rate_sweep(model, x: torch.Tensor, lambdas: Sequence[float], bits: str = "estimated", msssim: bool = True) -> torch.Tensor:
+def rate_sweep(model, x: torch.Tensor, lambdas: Sequence[float], bits: str = "estimated", msssim: bool = True, aq=None) -> torch.Tensor:
     """One model over a range of rates: for every lambda of `lambdas` the rows of `validate(model, x, bits=bits)` with the images
     encoded by `model.encode(x, rd_lambda=lambda)`, averaged over the batch.  Returns float64 [len(lambdas), 4]: the existing columns
     [psnr_db, ms_ssim_db, bpp] plus `rd_lambda`.  `bits`: "estimated" or "exact", as for `validate` (the streams of "coded" are those
-    of "exact").  This rank's images only."""
+    of "exact").  `aq`: adaptive quantisation as for `Compressor.encode`, the same for every lambda.  This rank's images only."""
     if bits not in ("estimated", "exact"):
         raise ValueError(f"rate_sweep: bits must be 'estimated' or 'exact', got {bits!r}")
     lams = [model._quantizer.rateLambdas(lam) for lam in lambdas]             # all checked before any device work
+    aq = model._aqArgs(aq)
     rows = []
     for lam, per_level in zip(lambdas, lams):
-        r = _validate_on_device(model, x, None, msssim, False, bits, rd_lambda=per_level).mean(0)
+        r = _validate_on_device(model, x, None, msssim, False, bits, rd_lambda=per_level, aq=aq).mean(0)
         # (a per-level list shows as its first entry)
         rows.append(torch.cat([r, r.new_tensor([float(lam) if not isinstance(lam, (list, tuple)) else per_level[0]])]))
     return torch.stack(rows) if rows else torch.empty((0, 4), dtype=torch.float64, device=x.device)
 
 
-def _validate_on_device(model, images: torch.Tensor, group, msssim: bool, gather: bool, bits: str, rd_lambda=None) -> torch.Tensor:
+def _validate_on_device(model, images: torch.Tensor, group, msssim: bool, gather: bool, bits: str, rd_lambda=None, aq=None) -> torch.Tensor:
     """`validate` with the size of the codes taken on the device: from the coder's tables ("estimated") or from the device coder's
     streams ("exact": bytes * 8 / pixels in float64, the one division of the coded path).  The restored images are those of the coded path
     (the coder is lossless: `decompress` decodes to these codes), cropped from the padded reconstruction as `decompress` crops."""
-    codes = model.encode(images) if rd_lambda is None else model.encode(images, rd_lambda=rd_lambda)
+    if aq is not None:
+        codes = model.encode(images, rd_lambda=rd_lambda, aq=aq)
+    else:
+        codes = model.encode(images) if rd_lambda is None else model.encode(images, rd_lambda=rd_lambda)
     restored = model.decode(codes)
     h, w = images.shape[-2], images.shape[-1]
     top, left = (restored.shape[-2] - h) // 2, (restored.shape[-1] - w) // 2
